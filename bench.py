@@ -25,9 +25,14 @@ fixed-size per-step log records are gathered ONCE with an RCCL all_gather at log
 by `python -m torch.distributed.run` the ranks are taken from the environment; launched plainly (`python bench.py --gpus N`) this
 process — which never touches a GPU — starts the N rank processes itself and relays rank 0's line.
 
-Prints ONE JSON line (rank 0).  Extra legs after the timed region (rank 0, N = 1 only): per-kernel time with HIP events on the
-library's streams -> `roofline` of the time-dominant kernel (+ the whole step and the distance kernel against both rooflines),
-and the CPU baselines B1 / B2 of BASELINE.md §3 (oracle/, bounded samples).
+Prints ONE JSON line on stdout (rank 0): the measurement, `ms_per_step` = milliseconds of one timed step.  Extra legs after the
+timed region (rank 0, N = 1 only): per-kernel time with HIP events on the library's streams -> `roofline` of the time-dominant
+kernel (+ the whole step and the distance kernel against both rooflines), the CPU baselines B1 / B2 of BASELINE.md §3 (oracle/,
+bounded samples) and the other configurations; their reports go to stderr as one JSON line of their own (`legs_on_stderr` in the
+result line names them), so that the result line stays short enough to be read back from the end of a run's output.
+
+--dump-outputs DIR: after the timed steps, what the timed path handed its caller goes to DIR as float64 .npy files (dump_outputs).
+Every input is synthetic and seeded, so two builds run with the same arguments can be compared output for output.
 """
 from __future__ import annotations
 
@@ -55,6 +60,52 @@ F64_MATRIX_MEASURED = {"tool": "tools/src/mfma_f64_bench.hip", "TFLOPs_by_waves_
 N_SIMD = 256 * 4           # 256 CUs x 4 SIMDs (MI355X_MICROARCH.md)
 N_XCD = 8
 METRIC = "ICP-proposal MH iterations/sec (femur GPMM r=50, ~50k-vtx target)"
+# the keys of the result line on stdout; every other key of a line (the extra legs' reports) goes to stderr (print_result)
+RESULT_KEYS = ("metric", "value", "unit", "n_gpus", "steps", "warmup", "ms_per_step", "higher_is_better", "scaling", "vs_baseline", "dtype",
+               "data", "config", "multi_gpu", "runtime_stats")
+DUMP_BUDGET_BYTES = 64_000_000  # --dump-outputs: all files together, headers included
+
+
+def _strict(v):
+    """a JSON-able value with every non-finite float replaced by null (json.dumps would write NaN / Infinity: not JSON)"""
+    if isinstance(v, dict):
+        return {k: _strict(x) for k, x in v.items()}
+    if isinstance(v, (list, tuple)):
+        return [_strict(x) for x in v]
+    if isinstance(v, float) and not np.isfinite(v):
+        return None
+    return v
+
+
+def print_result(line):
+    """The result line on stdout, the extra legs' reports (every key of `line` outside RESULT_KEYS) as one line on stderr before it."""
+    legs = {k: v for k, v in line.items() if k not in RESULT_KEYS}
+    head = {k: v for k, v in line.items() if k in RESULT_KEYS}
+    if legs:
+        head["legs_on_stderr"] = list(legs)
+        print(json.dumps(_strict(legs), allow_nan=False), file=sys.stderr, flush=True)
+    print(json.dumps(_strict(head), allow_nan=False), flush=True)
+
+
+def dump_outputs(out_dir, records, steps):
+    """--dump-outputs: the per-step records the timed path returned ([chains x steps, 14 + r], chain after chain: step index, accepted,
+    leaf id, log value, theta) as DIR/records.npy, and every chain's record of the LAST timed step as DIR/last_step.npy.  Where all
+    records would take the files past DUMP_BUDGET_BYTES, records.npy holds a seeded sample of their rows instead (the same rows for the
+    same arguments) and DIR/records_rows.npy says which."""
+    os.makedirs(out_dir, exist_ok=True)
+    records = np.ascontiguousarray(records, dtype=np.float64)
+    last = np.ascontiguousarray(records[steps - 1::steps])
+    np.save(os.path.join(out_dir, "last_step.npy"), last)
+    rows_path = os.path.join(out_dir, "records_rows.npy")
+    fit = (DUMP_BUDGET_BYTES - 3 * 4096 - last.nbytes) // (records.shape[1] * 8 + 8)  # rows that fit, with their row numbers (4 KB per header)
+    if records.shape[0] > fit:
+        rows = np.sort(np.random.default_rng(0).choice(records.shape[0], size=fit, replace=False))
+        np.save(os.path.join(out_dir, "records.npy"), records[rows])
+        np.save(rows_path, rows.astype(np.float64))
+    else:
+        np.save(os.path.join(out_dir, "records.npy"), records)
+        if os.path.exists(rows_path):  # (left by an earlier, sampled dump)
+            os.remove(rows_path)
 
 
 # ---------------------------------------------------------------------------------------------- launcher
@@ -463,10 +514,15 @@ def main():
                     help="seconds of the B1_parallel leg of the CPU baseline (min(chains, cores) independent one-thread oracle chains at once; 0 = skip)")
     ap.add_argument("--events-out", type=str, default="",
                     help="also write the per-kernel HIP-event table of the roofline leg (durations WITHOUT device-side waits, the waits beside them) to this json file")
+    ap.add_argument("--dump-outputs", type=str, default="", metavar="DIR",
+                    help="after the timed steps, write what they returned to DIR as .npy files: records.npy (every chain's per-step records) "
+                         "and last_step.npy (every chain's record of the last step); at most 64 MB in all")
     ap.add_argument("--selftest-launcher", action="store_true", help=argparse.SUPPRESS)
     ap.add_argument("--b1-child", type=int, nargs=2, default=None, help=argparse.SUPPRESS)
     ap.add_argument("--leg", type=str, default="", help=argparse.SUPPRESS)  # "config3", "config3:cholesky-root", "config4": one extra leg, in a process of its own
     args = ap.parse_args()
+    if args.steps < 1:
+        ap.error("--steps must be at least 1")
     if args.b1_child is not None:
         b1_child(args)
         return
@@ -560,7 +616,7 @@ def main():
     t0 = time.perf_counter()
     rec = run_chains(args.steps)
     t_chain = time.perf_counter() - t0
-    gather_logs(rec)
+    gathered = gather_logs(rec)
     t_gather = time.perf_counter() - t0 - t_chain
     barrier()
     dt = time.perf_counter() - t0
@@ -568,6 +624,8 @@ def main():
         tt = torch.tensor([dt], dtype=torch.float64, device="cuda")
         dist.all_reduce(tt, op=dist.ReduceOp.MAX)
         dt = float(tt.item())
+    if args.dump_outputs and rank == 0:
+        dump_outputs(args.dump_outputs, gathered if dist is None else torch.cat(gathered).cpu().numpy(), args.steps)
     n_acc = int(rec[:, 1].sum())
     n_icp = int((rec[:, 2] < 2).sum())
     rate = world * B * args.steps / dt
@@ -739,7 +797,7 @@ def main():
     if rank == 0:
         # fall-back counters of the whole process (icp_ctx_runtime_stats): every device-side wait that timed out, every step done twice
         line["runtime_stats"] = pkg._native.runtime_stats()
-        print(json.dumps(line))
+        print_result(line)
     if dist is not None:
         dist.destroy_process_group()
 
@@ -1127,6 +1185,8 @@ def run_config4(pkg, args, dist, torch, rank, world, local_rank):
         per_rank = [[stats["contexts_built"], stats["items"], stats["gather_ms"], stats["chain_ms"]]]
     n_items = len(items)
     assert all(r is not None and r.shape == (args.steps, 14 + model.rank) for r in recs), "a work item's records are missing"
+    if args.dump_outputs and rank == 0:
+        dump_outputs(args.dump_outputs, np.concatenate(recs), args.steps)
     multi_gpu = rank_report(dist, torch, rank, world, local_rank, stats["chain_ms"], stats["gather_ms"])
     roofline = None
     if rank == 0 and world == 1:
@@ -1152,7 +1212,7 @@ def run_config4(pkg, args, dist, torch, rank, world, local_rank):
                            "chains_per_launch": cpl if cpl > 0 else max(1, min(32, (3 if args.steps >= 150 else 2 if args.steps >= 30 else 1) * args.chains)), "best_item": [int(v) for v in items[best]],
                            "accepted": int(sum(r[:, 1].sum() for r in recs)), "phase_ms_rank0": stats.get("phase_ms")},
                 "roofline": roofline, "cpu_baseline": None, "multi_gpu": multi_gpu, "runtime_stats": pkg._native.runtime_stats()}
-        print(json.dumps(line))
+        print_result(line)
 
 
 LAUNCH_BOUNDARY_US = 2.4   # dependent launch on one stream, measured (tools/ubench2; DESIGN §6 "measured building blocks")

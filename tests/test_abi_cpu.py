@@ -129,7 +129,9 @@ def test_round6_entry_points_reject_bad_arguments_before_device(pkg):
     out = (ctypes.c_int64 * 3)()
     assert lib.icp_chain_bind_stats(None, out) == -1
     assert lib.icp_ctx_expect(0, -1) == -1
-    assert lib.icp_ctx_expect(0, 8) == -2   # ICP_ERR_DEVICE: no HIP device in this container (on a GPU box: 0)
+    assert lib.icp_ctx_expect(1 << 20, 8) == -2  # ICP_ERR_DEVICE: an ordinal no machine has
+    if not _gpu_present():
+        assert lib.icp_ctx_expect(0, 8) == -2  # … and, without a GPU, device 0 (on a GPU box the hint is taken: 0)
 
 
 def test_model_arrays_are_frozen_once_the_model_key_is_taken(pkg, femur50):

@@ -69,3 +69,51 @@ def test_two_ranks_on_one_device_fail_the_run():
     with pytest.raises(SystemExit) as ei:
         bench.rank_report(FakeDist(), None, 0, 2, 0, 1.0, 0.1, cpu=True)
     assert "same device" in str(ei.value)
+
+
+def _strict_json(text):
+    def no_constants(c):
+        raise ValueError("not JSON: " + c)
+    return json.loads(text, parse_constant=no_constants)
+
+
+def test_result_line_is_short_strict_json(capsys):
+    """stdout carries ONE line with the measurement, valid JSON (no NaN / Infinity); the extra legs' reports go to stderr, named in it."""
+    sys.path.insert(0, ROOT)
+    import bench
+
+    legs = {"roofline": {"frac": float("nan")}, "cpu_baseline": None, "extra_configs": {"config3": {"value": float("inf"), "x": "y" * 20000}}}
+    bench.print_result({"metric": "m", "value": 10.0, "steps": 20, "warmup": 5, "ms_per_step": 0.1, "config": {"accepted": 3}, **legs})
+    out, err = capsys.readouterr()
+    assert len(out.splitlines()) == 1 and len(out) < 1000
+    head = _strict_json(out)
+    assert head["ms_per_step"] == 0.1 and head["steps"] == 20 and head["config"] == {"accepted": 3}
+    assert head["legs_on_stderr"] == list(legs)
+    rest = _strict_json(err.strip().splitlines()[-1])
+    assert rest["roofline"] == {"frac": None} and rest["extra_configs"]["config3"]["value"] is None
+
+
+def test_dump_outputs(tmp_path, monkeypatch):
+    """--dump-outputs: records.npy = the timed steps' records (chain after chain), last_step.npy = every chain's last row; past the
+    budget a seeded sample of rows (the same for the same shapes) and their row numbers, all files within the budget."""
+    sys.path.insert(0, ROOT)
+    import numpy as np
+    import bench
+
+    steps, chains, width = 9, 4, 64
+    rec = np.random.default_rng(3).normal(size=(chains * steps, width))
+    bench.dump_outputs(str(tmp_path), rec, steps)
+    assert np.array_equal(np.load(tmp_path / "records.npy"), rec)
+    assert np.array_equal(np.load(tmp_path / "last_step.npy"), rec[steps - 1::steps])
+    assert not (tmp_path / "records_rows.npy").exists()
+
+    budget = 3 * 4096 + chains * width * 8 + 10 * (width * 8 + 8)
+    monkeypatch.setattr(bench, "DUMP_BUDGET_BYTES", budget)
+    for d in ("a", "b"):
+        bench.dump_outputs(str(tmp_path / d), rec, steps)
+    rows = np.load(tmp_path / "a" / "records_rows.npy")
+    assert rows.dtype == np.float64 and len(rows) == 10 and np.all(np.diff(rows) > 0)
+    assert np.array_equal(np.load(tmp_path / "a" / "records.npy"), rec[rows.astype(np.int64)])
+    assert np.array_equal(np.load(tmp_path / "a" / "last_step.npy"), rec[steps - 1::steps])
+    assert np.array_equal(rows, np.load(tmp_path / "b" / "records_rows.npy"))
+    assert sum(f.stat().st_size for f in (tmp_path / "a").iterdir()) <= budget
