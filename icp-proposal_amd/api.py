@@ -553,14 +553,96 @@ def chain_step_prelaunch(evaluator: _Evaluator, proposals, theta_cur, generator:
     nat.check(nat.lib().icp_chain_step_prelaunch(evaluator.h, n, arr, int(generator), _d(a), _d(key)), "icp_chain_step_prelaunch")
 
 
+def direction_schedule(n_fits: int, n_recursions: int, seed) -> np.ndarray:
+    """ModelAndTargetSampling's per-recursion draw (api/other/IcpBasedSurfaceFitting.scala:63-69): ModelSampling (0) or
+    TargetSampling (1) with probability 1/2 each, [n_fits, n_recursions] uint8 from np.random.default_rng(seed).  The reference
+    draws from the unseeded global scala.util.Random, so only the distribution of the directions is the reference's; the
+    draw of one fit is not (per-fit equality with Scalismo is not defined)."""
+    if seed is None:
+        raise ValueError("ModelAndTargetSampling without a directions schedule needs a seed")
+    if n_fits < 0 or n_recursions < 0:
+        raise ValueError("negative size")
+    return np.random.default_rng(seed).integers(0, 2, size=(int(n_fits), int(n_recursions))).astype(np.uint8)
+
+
+def _direction_code(direction) -> int:
+    if direction in (ModelSampling, 0):
+        return 0
+    if direction in (TargetSampling, 1):
+        return 1
+    raise ValueError(f"unknown projection direction {direction!r}")
+
+
+def icp_fits(contexts, theta_inits, numIterations: int, iterationSeq=(1.0, 0.1, 0.01), projectionDirection=ModelSampling,
+             modelPointIds=None, targetPointSamples=None, stepLength: float = 1.0, directions=None, seed=None):
+    """Many deterministic ICP fits (IcpBasedSurfaceFitting.runfitting, api/other/IcpBasedSurfaceFitting.scala:46-126) in one call
+    (icp_fit_deterministic_many): fit b starts at theta_inits[b] on contexts[b] (one context, or one per fit; the fits of one
+    target may share its context).  `targetPointSamples` is one array for every fit or one per fit.
+    Directions: ModelSampling / TargetSampling for every recursion, or ModelAndTargetSampling — a fresh draw per recursion as the
+    reference makes it (:63-69): `directions` ([n_fits, len(iterationSeq)·(numIterations+1)] of 0 / 1) if given, else drawn by
+    direction_schedule(…, seed) (seed required).  The reference draws from the unseeded global scala.util.Random: per-fit equality
+    with Scalismo is not defined, only the distribution of the directions.
+    Returns (thetas [n_fits, 10+r], status [n_fits]): status 0, or ICP_ERR_NOT_SPD (-4) / ICP_ERR_NOT_FINITE (-3) for that fit
+    alone (its row is then theta_init).  Argument errors raise before anything runs."""
+    th = _f64(theta_inits)
+    if th.ndim != 2:
+        raise ValueError("theta_inits must be [n_fits, 10 + rank]")
+    n = th.shape[0]
+    ctxs = list(contexts) if isinstance(contexts, (list, tuple)) else [contexts] * n
+    if n == 0 or len(ctxs) != n:
+        raise ValueError("one context per fit (or one for all) and at least one fit")
+    r = ctxs[0].rank
+    if th.shape[1] != 10 + r or any(c.rank != r for c in ctxs):
+        raise ValueError("theta_inits and the contexts' rank disagree")
+    sig = _f64(iterationSeq).reshape(-1)
+    if numIterations < 0:
+        raise ValueError("numIterations must be >= 0")
+    R = sig.shape[0] * (int(numIterations) + 1)
+    if directions is not None:
+        dirs = np.ascontiguousarray(directions, dtype=np.uint8)
+        if dirs.shape != (n, R):
+            raise ValueError(f"directions must be [{n}, {R}]")
+    elif projectionDirection in (ModelAndTargetSampling, 2):
+        dirs = direction_schedule(n, R, seed)
+    else:
+        dirs = None
+    ids = np.ascontiguousarray(modelPointIds if modelPointIds is not None else np.zeros(0), dtype=np.int32).reshape(-1)
+    if targetPointSamples is None:
+        tps = [np.zeros((0, 3))] * n
+    elif isinstance(targetPointSamples, (list, tuple)):
+        tps = [_f64(t).reshape(-1, 3) for t in targetPointSamples]
+    else:
+        tps = [_f64(targetPointSamples).reshape(-1, 3)] * n
+    if len(tps) != n:
+        raise ValueError("targetPointSamples: one array, or one per fit")
+    code = _direction_code(projectionDirection) if dirs is None else 0
+    fps = [nat.FitParams(code, ids.shape[0], _i(ids), tp.shape[0], _d(tp), float(stepLength)) for tp in tps]
+    out = th.copy()
+    status = np.zeros(n, dtype=np.int32)
+    c_ctx = (C.c_void_p * n)(*[c.h for c in ctxs])
+    c_fp = (C.POINTER(nat.FitParams) * n)(*[C.pointer(fp) for fp in fps])
+    c_in = (nat.c_double_p * n)(*[_d(th[b]) for b in range(n)])
+    c_out = (nat.c_double_p * n)(*[_d(out[b]) for b in range(n)])
+    c_dirs = dirs.ctypes.data_as(nat.c_ubyte_p) if dirs is not None else None
+    rc = nat.lib().icp_fit_deterministic_many(n, c_ctx, c_fp, c_in, c_dirs, int(numIterations), sig.shape[0], _d(sig), c_out, _i(status))
+    if rc not in (0, -3, -4) or (rc != 0 and not np.any(status != 0)):
+        nat.check(rc, "icp_fit_deterministic_many")
+    return out, status
+
+
 class IcpBasedSurfaceFitting:
     """api/other/IcpBasedSurfaceFitting.scala:32 — the deterministic non-rigid ICP baseline (posterior MEAN, isotropic noise).
-    `modelPointIds` / `targetPointSamples` stand for the UniformMeshSampler3D draws of :51-53 (made by the caller)."""
+    `modelPointIds` / `targetPointSamples` stand for the UniformMeshSampler3D draws of :51-53 (made by the caller).
+    ModelAndTargetSampling draws the direction afresh for every recursion (:63-69); here from np.random.default_rng(seed)
+    (direction_schedule) — the reference draws from the unseeded global scala.util.Random, so only the distribution of the
+    directions is the reference's, not one fit's draw."""
 
     def __init__(self, ctx: IcpContext, stepLength: float = 1.0, projectionDirection=ModelSampling, modelPointIds=None,
-                 targetPointSamples=None):
+                 targetPointSamples=None, seed=1024):
         self.ctx, self.step = ctx, float(stepLength)
+        self.mixed = projectionDirection in (ModelAndTargetSampling, 2)
         self.direction = 1 if projectionDirection in (TargetSampling, "TargetSampling", 1) else 0
+        self.seed = seed
         self.ids = np.ascontiguousarray(modelPointIds if modelPointIds is not None else np.zeros(0), dtype=np.int32)
         self.tp = _f64(targetPointSamples if targetPointSamples is not None else np.zeros((0, 3))).reshape(-1, 3)
 
@@ -568,6 +650,11 @@ class IcpBasedSurfaceFitting:
         """:46-126; returns the final parameter vector (the reference returns the corresponding mesh: ctx.transformedMesh)."""
         th = _theta(initialModelParameters if initialModelParameters is not None else initial_parameters(self.ctx.model))
         sig = _f64(iterationSeq)
+        if self.mixed:  # one fit through icp_fit_deterministic_many with a seeded schedule
+            out, status = icp_fits(self.ctx, th[None, :], numIterations, sig, ModelAndTargetSampling, self.ids, self.tp, self.step,
+                                   seed=self.seed)
+            nat.check(int(status[0]), "icp_fit_deterministic_many")
+            return out[0]
         out = np.zeros_like(th)
         fp = nat.FitParams(self.direction, self.ids.shape[0], _i(self.ids), self.tp.shape[0], _d(self.tp), self.step)
         nat.check(nat.lib().icp_fit_deterministic(self.ctx.h, C.byref(fp), _d(th), int(numIterations), sig.shape[0], _d(sig), _d(out)),

@@ -660,4 +660,32 @@ SurfaceTask make_surface_task(int T, const double* verts, const int* tris, const
 VertexTask make_vertex_task(int V, const double* verts, int K, const double* P, int* hint, const QueryBuffers& qb, double* d2, int* idx);
 int query_batch(int K, int n_elems, size_t cand_capacity);
 
+// ---- many deterministic ICP fits in lockstep (kernels_fit.hip; icp_fit_deterministic_many)
+constexpr int kFitInstGroup = 8;  // fits whose instances one pass over the basis forms
+struct FitItem {  // one fit's record in device memory, the same for every recursion of the call
+  const uint8_t* dirs;  // [n_recursions] ICP_MODEL_SAMPLING (0) / ICP_TARGET_SAMPLING (1): the fit's schedule
+  double* coeffs;       // [r] shape coefficients (in / out)
+  Pose pose;
+  double* x;            // [N*3] instance
+  const int* ids;       // model side: sample ids (surf.K of them)
+  double* P;            // model side: their points on the instance
+  const double* tpts;   // target side: target samples (vert.K of them)
+  SurfaceTask surf;     // model side: P against the fit's target surface
+  VertexTask vert;      // target side: tpts against the instance
+  int fblocks_m, fblocks_t;  // filter workgroups of either side's search (filter_grid_blocks)
+  int splits_m, splits_t;    // regression_splits of either side's K
+  CorrBuffers cb;
+  double* Mpart;        // regression_splits(max K) · (r+1)² partial sums
+  double* alpha;
+  int* factor_status;   // the factorisation's status word (this recursion)
+  int* status;          // != 0: a factorisation of this fit failed (sticky)
+  double step;
+};
+int query_kpad(int K);  // K rounded up as the search tasks round it (SurfaceTask / VertexTask::Kpad)
+struct FitGrid { int kpad, kmax, filter, splits; };  // the launches' grid extents over every fit of a recursion
+void launch_fit_instance(hipStream_t st, int B, int N, int r, const double* Qp, const double* ref, const double* mean, const FitItem* items);
+void launch_fit_searches(hipStream_t st, int B, int rec, const FitGrid& g, int N, const double* ref, const double* mean, const FitItem* items);
+void launch_fit_regression(hipStream_t st, int B, int rec, const FitGrid& g, int r, const double* Q, double wt, const FitItem* items);
+void launch_fit_mean_step(hipStream_t st, int B, int r, const double* P, double sigma2, const FitItem* items);
+
 }  // namespace icp

@@ -238,8 +238,9 @@ ICP_API int icp_prior_log_value(int32_t rank, const double *theta, double *out);
  * sigma2 of the sequence (:36-40: 1, 0.1, 0.01) the recursion (:55-104) runs numIterations + 1 times: instance, correspondences
  * in one direction (:71-79), GP regression with ISOTROPIC noise sigma2 (:81), posterior MEAN (:82), its coefficients (:84), step
  * (:85).  The sample ids / sample points are drawn by Scalismo's UniformMeshSampler3D in the reference (:51-53) and are inputs
- * here; so is the per-iteration direction draw of ModelAndTargetSampling (:66-69: call once per iteration instead).  All
- * iterations run on the device without host round trips.  theta_out = theta_init with the fitted shape coefficients. */
+ * here; so is the per-iteration direction draw of ModelAndTargetSampling (:66-69: icp_fit_deterministic_many takes a schedule
+ * of directions).  All iterations run on the device without host round trips.  theta_out = theta_init with the fitted shape
+ * coefficients. */
 typedef struct {
   int32_t direction;             /* icp_direction */
   int32_t n_model_ids;           /* ModelSampling: pointIds (:53), any ids, repeats allowed */
@@ -250,6 +251,20 @@ typedef struct {
 } icp_fit_params;
 ICP_API int icp_fit_deterministic(icp_ctx *ctx, const icp_fit_params *params, const double *theta_init, int32_t n_iterations,
                                   int32_t n_sigma, const double *sigma2_seq, double *theta_out);
+
+/* Many deterministic fits in lockstep on one stream, one synchronisation per call (the study's 100 inits per target).
+ * ctxs[b]: fit b's context; repeats allowed (the inits of one target share its context).  All contexts share one device and one
+ * model.  directions: NULL (every recursion of fit b takes params[b]->direction) or [n_fits][n_sigma*(n_iterations+1)] bytes of
+ * ICP_MODEL_SAMPLING / ICP_TARGET_SAMPLING, recursion si*(n_iterations+1)+it — ModelAndTargetSampling's per-recursion draw (:63-69).
+ * A fit that uses a side needs a non-empty sample list for it.  Fit b's result is what icp_fit_deterministic gives when called once
+ * per recursion (n_iterations = 0, one sigma2, that recursion's direction), each theta_out chained into the next theta_init; its
+ * bits do not depend on the other fits of the call or their order.  The pose is left as it is.
+ * ICP_ERR_INVALID_ARG (null pointers, mixed models or devices, unknown direction byte, non-finite theta_init, id out of range, bad
+ * sigma2, missing samples): nothing has run, no theta_out is written.  Otherwise status[b] = ICP_OK / ICP_ERR_NOT_SPD /
+ * ICP_ERR_NOT_FINITE per fit (a failed fit's theta_out is left untouched) and the return value is ICP_OK or the first failing fit's. */
+ICP_API int icp_fit_deterministic_many(int32_t n_fits, icp_ctx *const *ctxs, const icp_fit_params *const *params,
+                                       const double *const *theta_init, const uint8_t *directions, int32_t n_iterations,
+                                       int32_t n_sigma, const double *sigma2_seq, double *const *theta_out, int32_t *status);
 
 /* ---------------------------------------------------------------- posterior variability maps
  * apps/util/PosteriorVariability.scala:30-73 over n_samples logged chain states (thetas [n_samples*(10+r)]):
