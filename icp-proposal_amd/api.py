@@ -679,3 +679,57 @@ def evaluate_reconstruction_to_ground_truth(ctx: IcpContext, theta) -> dict:
     return {"average2surface": out[0], "hausdorff": out[1], "average2surface_boundary_aware": out[2], "max_boundary_aware": out[3],
             "kept": int(out[4])}
 
+
+MAX_DICE_SAMPLES = 1 << 24
+
+
+def registration_metrics(contexts, thetas, dice_samples: int = 10000, seed: int = 1024) -> dict:
+    """The experiment summary's distance measures (apps/femur/StdIcpVsChainICPrandomInitComparisonAll.scala:43-64) of many meshes
+    in one call (icp_mesh_metrics_many): item b scores the mesh of thetas[b] against the target of contexts[b] (one context, or one
+    per item; contexts may repeat).  Returns arrays of n_items keyed "avg", "hausdorff", "dice", "average2surface_boundary_aware",
+    "max_boundary_aware", "kept", "n_inside_reconstruction", "n_inside_target", "n_inside_both".  avg / hausdorff / the
+    boundary-aware pair / kept are the bits of evaluate_reconstruction_to_ground_truth.  Dice: MeshMetrics.diceCoefficient as
+    recalled [SCALISMO-UNVERIFIED] — dice_samples points uniform in the union of the two boxes, drawn from orc_rng_uniform(seed, s, k),
+    each classified by the vertex normal of its nearest vertex (include/icp_proposal.h); meaningful for closed meshes only.
+    dice_samples = 0 skips it (NaN).  An item whose mesh is not finite has NaN everywhere and "status" != 0."""
+    th = _f64(thetas)
+    if th.ndim == 1:
+        th = th[None, :]
+    if th.ndim != 2:
+        raise ValueError("thetas must be [n_items, 10 + rank]")
+    n = th.shape[0]
+    ctxs = list(contexts) if isinstance(contexts, (list, tuple)) else [contexts] * n
+    if n == 0 or len(ctxs) != n:
+        raise ValueError("one context per item (or one for all) and at least one item")
+    if n > 65535:
+        raise ValueError("at most 65,535 items a call")
+    r = ctxs[0].rank
+    if th.shape[1] != 10 + r or any(c.rank != r for c in ctxs):
+        raise ValueError("thetas and the contexts' rank disagree")
+    if not np.all(np.isfinite(th)):
+        raise ValueError("thetas contain a non-finite value")
+    dice_samples = int(dice_samples)
+    if not 0 <= dice_samples <= MAX_DICE_SAMPLES:
+        raise ValueError(f"dice_samples must lie in [0, {MAX_DICE_SAMPLES}]")
+    seed = int(seed)
+    if not 0 <= seed < (1 << 64):
+        raise ValueError("seed must be an unsigned 64-bit integer")
+    out = np.zeros((n, 9))
+    status = np.zeros(n, dtype=np.int32)
+    c_ctx = (C.c_void_p * n)(*[c.h for c in ctxs])
+    c_th = (nat.c_double_p * n)(*[_d(th[b]) for b in range(n)])
+    rc = nat.lib().icp_mesh_metrics_many(n, c_ctx, c_th, dice_samples, seed, _d(out), _i(status))
+    if rc not in (0, -3) or (rc != 0 and not np.any(status != 0)):
+        nat.check(rc, "icp_mesh_metrics_many")
+    return {"avg": out[:, 0].copy(), "hausdorff": out[:, 1].copy(), "dice": out[:, 5].copy(),
+            "average2surface_boundary_aware": out[:, 2].copy(), "max_boundary_aware": out[:, 3].copy(), "kept": out[:, 4].copy(),
+            "n_inside_reconstruction": out[:, 6].copy(), "n_inside_target": out[:, 7].copy(), "n_inside_both": out[:, 8].copy(),
+            "status": status}
+
+
+def dice_coefficient(ctx: IcpContext, theta, samples: int = 10000, seed: int = 1024) -> float:
+    """MeshMetrics.diceCoefficient(mesh of theta, ctx's target) [SCALISMO-UNVERIFIED], one item of registration_metrics."""
+    m = registration_metrics(ctx, _theta(theta)[None, :], samples, seed)
+    nat.check(int(m["status"][0]), "icp_mesh_metrics_many")
+    return float(m["dice"][0])
+

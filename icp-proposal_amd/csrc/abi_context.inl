@@ -400,6 +400,7 @@ int icp_ctx_set_target(icp_ctx* ctx, const icp_mesh_desc* target) {
     }
     // what was cached against the old target: the states' surface points and nearest vertices, the search hints
     for (auto& s : ctx->slots) { s.valid = false; s.defo_valid = false; s.spheres_valid = false; s.n_surf = s.n_nnv = 0; s.lo_surf = s.hi_surf = s.lo_nnv = s.hi_nnv = 0; }
+    ctx->tgt_geo_valid = false;  // (Dice's target normals and box)
     seed_context_hints(*ctx);  // (the new pair's filed hints, or none)
     HIP_OK(hipStreamSynchronize(ctx->stream));
     ctx->stage_used = 0;

@@ -465,6 +465,11 @@ struct icp_ctx {
   // member of a batch between icp_chain_step_batched_issue and _collect / _abandon (set and cleared under `mu`, which is NOT
   // held in between): every other entry point on this context fails with ICP_ERR_BUSY meanwhile
   bool batch_busy = false;
+  // Dice (icp_mesh_metrics_many): the target's vertex-to-triangle adjacency, vertex normals and box [lo(3), hi(3)], made on the first
+  // call that needs them; dropped where the target is replaced (icp_ctx_set_target)
+  bool tgt_geo_valid = false;
+  DBuf<int> tgt_adj_off, tgt_adj;
+  DBuf<double> tgt_normals, tgt_box;
 
   Profiler prof;
   bool profiling = false;

@@ -688,4 +688,52 @@ void launch_fit_searches(hipStream_t st, int B, int rec, const FitGrid& g, int N
 void launch_fit_regression(hipStream_t st, int B, int rec, const FitGrid& g, int r, const double* Q, double wt, const FitItem* items);
 void launch_fit_mean_step(hipStream_t st, int B, int r, const double* P, double sigma2, const FitItem* items);
 
+// ---- registration metrics of many meshes (kernels_metrics.hip; icp_mesh_metrics_many)
+struct MetItem {        // one item's record (device)
+  double* x;            // [N*3] instance
+  float4* spheres;      // sphere_floats4(T): the instance's triangle spheres (tri_order)
+  double* normals;      // [N*3] vertex normals (Dice only)
+};
+struct MetBoxJob {      // axis-aligned box of n vertices -> out [lo(3), hi(3)], united with `with` (nullable); non-finite count (nullable)
+  const double* verts;
+  int n;
+  const double* with;
+  double* out;
+  int* nonfinite;
+};
+struct MetSearch {      // one search: a SurfaceTask (kind 0) or a VertexTask (kind 1)
+  int kind;
+  int fblocks;          // filter workgroups (filter_grid_blocks; 0: nothing to filter)
+  int hint_step;        // > 0: hint = nearest of every hint_step-th element; 0: hint = hint_tris[3 * hint_tri[k]]
+  const int* hint_tri;
+  const int* hint_tris;
+  SurfaceTask s;
+  VertexTask v;
+};
+struct MetStats {       // k_dist_stats of one distance list: out [Σ, max, count]
+  int K;
+  const double* d2;
+  const unsigned char* flags;
+  const int* idx;
+  int n_flags;
+  double* out;
+};
+struct MetDice {        // samples s0 .. s0+n-1 of one item's Dice
+  int n, s0;
+  const double* box;    // [6] evaluation box
+  double* P;            // [n*3] sample points
+  const int* idxA;      // nearest vertex of the item's mesh (A) / of the target (B)
+  const int* idxB;
+  const double* xA; const double* nA; int NA;
+  const double* xB; const double* nB; int NB;
+  unsigned* counts;     // [3] nA, nB, nAB (added to)
+};
+void launch_met_items(hipStream_t st, int B, int N, int T, const int* tris, const int* tri_order, const int* adj_off, const int* adj,
+                      bool normals, const MetItem* items);
+void launch_met_box(hipStream_t st, int n, const MetBoxJob* jobs);
+void launch_met_searches(hipStream_t st, int n, int kpad_max, int filter_max, int kmax, const MetSearch* jobs);
+void launch_met_stats(hipStream_t st, int n, bool big, const MetStats* jobs);
+void launch_met_samples(hipStream_t st, int n, int nmax, uint64_t seed, const MetDice* jobs);
+void launch_met_dice_count(hipStream_t st, int n, int nmax, const MetDice* jobs);
+
 }  // namespace icp

@@ -8,6 +8,9 @@ Mirrors the reference's on-disk format so that its replay tools can consume chai
   getBestFittingParsFromJSON: accepted record with the largest "product" value                         :142-146
   LogHelper.samplesFromLog (apps/util/LogHelper.scala:27-38): every N-th index, stepping back to the last accepted record.
 
+JSONExperimentLogger (api/sampling/loggers/JSONExperimentLogger.scala) writes the experiment summary of the femur study
+(apps/femur/StdIcpVsChainICPrandomInitComparisonAll.scala:43-64): one jsonExperimentFormat record per init, 17 fields (:29-30).
+
 Input here = the fixed-size per-step records of the host harness (host/icp_host.h): [index, status, leaf id, log value,
 theta(10 + r)], which is also what the multi-GPU gather ships.  Host I/O only; nothing here touches the device."""
 from __future__ import annotations
@@ -91,3 +94,59 @@ def samples_from_log(log, take_every_n: int = 50, total: int = 100, burn_in: int
         return i
     idx = [get_log_index(i) for i in range(burn_in, min(len(log), total), take_every_n)]
     return [(log[i], i) for i in idx][:min(total, len(idx))]
+
+
+# jsonExperimentFormat (api/sampling/loggers/JSONExperimentLogger.scala:29-30), in its field order
+EXPERIMENT_FIELDS = ("index", "modelPath", "targetPath", "samplingEuclideanLoggerPath", "samplingHausdorffLoggerPath", "coeffInit",
+                     "coeffSamplingEuclidean", "coeffSamplingHausdorff", "coeffIcp", "samplingEuclidean", "samplingHausdorff", "icp",
+                     "numOfEvaluationPoints", "numOfSamplePoints", "normalNoise", "datetime", "comment")
+EXPERIMENT_DATETIME_FORMAT = "%Y-%m-%d %H:%M:%S"  # SimpleDateFormat("yyyy-MM-dd HH:mm:ss") (:37)
+METRIC_KEYS = ("avg", "hausdorff", "dice")  # distMeasure of the study (StdIcpVsChainICPrandomInitComparisonAll.scala:43-50)
+
+
+class JSONExperimentLogger:
+    """api/sampling/loggers/JSONExperimentLogger.scala: the experiment summary (experiments.json) of the femur study.
+    The coeff* fields take the coefficient vectors they are given — the caller passes the thetas' own coefficients (theta[10:]),
+    where the reference logs model.coefficients(mesh), the regularised projection (sigma2 = 1e-5) of a mesh that is itself a model
+    instance (a stated deviation).  The metric maps are keyed avg / hausdorff / dice (registration_metrics gives all three)."""
+
+    def __init__(self, file_path, model_path: str = ""):
+        self.file_path = str(file_path)
+        self.model_path = model_path
+        parent = os.path.dirname(os.path.abspath(self.file_path))
+        if not os.path.isdir(parent):
+            raise IOError(f"JSON log path does not exist: {parent}!")  # :41-43
+        if os.path.exists(self.file_path) and not os.access(self.file_path, os.W_OK):
+            raise IOError(f"JSON file exist and cannot be overwritten: {self.file_path}!")  # :44-46
+        self.experiments = []
+
+    @staticmethod
+    def _metrics(m) -> dict:
+        return {k: float(v) for k, v in dict(m).items()}
+
+    def append(self, index: int, targetPath: str = "", samplingEuclideanLoggerPath: str = "", samplingHausdorffLoggerPath: str = "",
+               coeffInit=(), coeffSamplingEuclidean=(), coeffSamplingHausdorff=(), coeffIcp=(), samplingEuclidean=None,
+               samplingHausdorff=None, icp=None, numOfEvaluationPoints: int = 0, numOfSamplePoints: int = 0, normalNoise: float = 0.0,
+               comment: str = ""):
+        """:63-66; datetime = now, as the reference stamps it."""
+        rec = dict(zip(EXPERIMENT_FIELDS, (
+            int(index), self.model_path, targetPath, samplingEuclideanLoggerPath, samplingHausdorffLoggerPath,
+            [float(v) for v in np.asarray(coeffInit, dtype=np.float64).reshape(-1)],
+            [float(v) for v in np.asarray(coeffSamplingEuclidean, dtype=np.float64).reshape(-1)],
+            [float(v) for v in np.asarray(coeffSamplingHausdorff, dtype=np.float64).reshape(-1)],
+            [float(v) for v in np.asarray(coeffIcp, dtype=np.float64).reshape(-1)],
+            self._metrics(samplingEuclidean or {}), self._metrics(samplingHausdorff or {}), self._metrics(icp or {}),
+            int(numOfEvaluationPoints), int(numOfSamplePoints), float(normalNoise),
+            _dt.datetime.now().strftime(EXPERIMENT_DATETIME_FORMAT), comment)))
+        self.experiments.append(rec)
+        return rec
+
+    def write_log(self):
+        """:69-78 (a JSON list of the records, fields in jsonExperimentFormat order)."""
+        with open(self.file_path, "w") as f:
+            json.dump(self.experiments, f, indent=2)
+
+    def load_log(self):
+        """:81-84"""
+        with open(self.file_path) as f:
+            return json.load(f)

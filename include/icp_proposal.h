@@ -284,6 +284,25 @@ ICP_API int icp_posterior_variability(icp_ctx *ctx, int32_t n_samples, const dou
  *   out[4] = number of vertices kept by that filter. */
 ICP_API int icp_mesh_metrics(icp_ctx *ctx, const double *theta, double *out /* [5] */);
 
+/* Registration metrics of many meshes in one call, one synchronisation (the experiment summary of
+ * apps/femur/StdIcpVsChainICPrandomInitComparisonAll.scala:43-64: avg / hausdorff / dice of every scored mesh against its target).
+ * Item b scores the mesh of thetas[b], pose included, against ctxs[b]'s target.  Contexts may repeat; all share one device and one
+ * model, targets may differ.  out[9b+0..4] = the bits of icp_mesh_metrics(ctxs[b], thetas[b]); out[9b+5] = Dice; out[9b+6..8] =
+ * nA, nB, nAB.  With dice_samples == 0 Dice is skipped and out[9b+5..8] are NaN.
+ * Dice, MeshMetrics.diceCoefficient of Scalismo 0.90 as recalled [SCALISMO-UNVERIFIED]: S = dice_samples points uniform in the union
+ * of the two meshes' axis-aligned boxes, p_k = lo_k + u(s,k)·(hi_k − lo_k) (subtract, multiply, add, each rounded) with
+ * u(s,k) = orc_rng_uniform(dice_seed, s, k) — the same points whatever the item's place in the batch.  p is inside a mesh iff, with v
+ * its nearest vertex (ties: lowest index) and n v's vertex normal, (n.x(v.x−p.x) + n.y(v.y−p.y)) + n.z(v.z−p.z) > 0.  nA / nB =
+ * samples inside the reconstruction / the target, nAB = inside both, dice = 2·nAB / (nA + nB) (NaN when nA + nB == 0).  The rule is
+ * evaluated for any mesh but means something for closed meshes only; its parity with Scalismo's own sampler and inside test is not
+ * pinned (no Scalismo source here).
+ * ICP_ERR_INVALID_ARG (null pointers, n_items outside [1, 65535], dice_samples outside [0, 2^24], a non-finite theta, mixed devices
+ * or models): nothing has run, nothing is written.  ICP_ERR_BUSY: a context belongs to a batch in flight.  Otherwise status[b] =
+ * ICP_OK, or ICP_ERR_NOT_FINITE for an item whose mesh is not finite (its out row is NaN), and the return value is ICP_OK or the
+ * first failing item's.  An item's bits depend neither on the other items nor on their order. */
+ICP_API int icp_mesh_metrics_many(int32_t n_items, icp_ctx *const *ctxs, const double *const *thetas, int32_t dice_samples,
+                                  uint64_t dice_seed, double *out /* [n_items*9] */, int32_t *status /* [n_items] */);
+
 /* ---------------------------------------------------------------- fused chain step (measurement harness)
  * One call = all device work one Metropolis–Hastings step needs for a NEW state theta_prop proposed from
  * theta_cur, submitted as one stream sequence with a single synchronisation: the likelihood of theta_prop and,
