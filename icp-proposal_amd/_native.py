@@ -103,6 +103,8 @@ SIGNATURES = {
     "icp_fit_deterministic_many": (C.c_int, [C.c_int32, C.POINTER(C.c_void_p), C.POINTER(C.POINTER(FitParams)), C.POINTER(c_double_p),
                                              c_ubyte_p, C.c_int32, C.c_int32, c_double_p, C.POINTER(c_double_p), c_int_p]),
     "icp_posterior_variability": (C.c_int, [C.c_void_p, C.c_int32, c_double_p, C.c_int32, c_double_p, c_double_p]),
+    "icp_posterior_variability_many": (C.c_int, [C.c_int32, C.POINTER(C.c_void_p), c_int_p, C.POINTER(c_double_p), c_int_p,
+                                                 C.POINTER(c_double_p), C.POINTER(c_double_p), C.POINTER(c_double_p)]),
     "icp_mesh_metrics": (C.c_int, [C.c_void_p, c_double_p, c_double_p]),
     "icp_mesh_metrics_many": (C.c_int, [C.c_int32, C.POINTER(C.c_void_p), C.POINTER(c_double_p), C.c_int32, C.c_uint64, c_double_p,
                                         c_int_p]),

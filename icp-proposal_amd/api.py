@@ -672,6 +672,61 @@ def posterior_variability(ctx: IcpContext, thetas, mode: int = 0, theta_ref=None
     return out
 
 
+def posterior_variability_maps(contexts, sample_sets, mode=0, theta_refs=None, want_mean: bool = False):
+    """The variability maps of many chains' samples in one call (icp_posterior_variability_many): map m is
+    posterior_variability(contexts[m], sample_sets[m], mode[m], theta_refs[m]), bit for bit.  `contexts`: one context or one per map
+    (they may repeat and differ in model and rank; one device); `sample_sets`: per map an array [S_m, 10 + rank] with S_m >= 2;
+    `mode`: one int or one per map; `theta_refs`: per map the state whose mesh gives mode 1's normals (None elsewhere).  The sample
+    meshes stream through a fixed 64 MiB buffer on the device, so S_m may be every state of a long chain.  Returns the list of [N_m]
+    maps; with want_mean also the list of [N_m, 3] mean sample meshes."""
+    sets = list(sample_sets)
+    n = len(sets)
+    ctxs = list(contexts) if isinstance(contexts, (list, tuple)) else [contexts] * n
+    if len(ctxs) != n:
+        raise ValueError("one context per map (or one for all)")
+    modes = [int(v) for v in mode] if isinstance(mode, (list, tuple, np.ndarray)) else [int(mode)] * n
+    if len(modes) != n:
+        raise ValueError("one mode per map (or one for all)")
+    refs = list(theta_refs) if theta_refs is not None else [None] * n
+    if len(refs) != n:
+        raise ValueError("one theta_ref per map")
+    if n > 65535:
+        raise ValueError("at most 65,535 maps a call")
+    th, rf = [], []
+    for m in range(n):
+        a = _f64(sets[m])
+        if a.ndim != 2 or a.shape[1] != 10 + ctxs[m].rank:
+            raise ValueError(f"map {m}: samples must be [S, 10 + rank]")
+        if a.shape[0] < 2:
+            raise ValueError(f"map {m}: at least two samples are needed")
+        if modes[m] not in (0, 1, 2):
+            raise ValueError(f"map {m}: unknown mode {modes[m]}")
+        if modes[m] == 1 and refs[m] is None:
+            raise ValueError(f"map {m}: mode 1 needs a theta_ref")
+        if not np.all(np.isfinite(a)):
+            raise ValueError(f"map {m}: samples contain a non-finite value")
+        ref = None
+        if modes[m] == 1:
+            ref = _f64(refs[m]).reshape(-1)
+            if ref.shape[0] != 10 + ctxs[m].rank or not np.all(np.isfinite(ref)):
+                raise ValueError(f"map {m}: theta_ref must be 10 + rank finite values")
+        th.append(a)
+        rf.append(ref)
+    outs = [np.zeros(c.N) for c in ctxs]
+    means = [np.zeros((c.N, 3)) for c in ctxs] if want_mean else None
+    if n > 0:
+        c_ctx = (C.c_void_p * n)(*[c.h for c in ctxs])
+        c_n = np.array([a.shape[0] for a in th], dtype=np.int32)
+        c_mode = np.array(modes, dtype=np.int32)
+        c_th = (nat.c_double_p * n)(*[_d(a) for a in th])
+        c_rf = (nat.c_double_p * n)(*[_d(a) if a is not None else None for a in rf])
+        c_out = (nat.c_double_p * n)(*[_d(a) for a in outs])
+        c_mean = (nat.c_double_p * n)(*[_d(a) for a in means]) if want_mean else None
+        nat.check(nat.lib().icp_posterior_variability_many(n, c_ctx, _i(c_n), c_th, _i(c_mode), c_rf, c_out, c_mean),
+                  "icp_posterior_variability_many")
+    return (outs, means) if want_mean else outs
+
+
 def evaluate_reconstruction_to_ground_truth(ctx: IcpContext, theta) -> dict:
     """api/other/RegistrationComparison.scala:24-49 for the mesh of theta against the context's target."""
     out = np.zeros(5)

@@ -16,6 +16,7 @@
 #include "abi_methods.inl"  // C ABI: per-method entry points — proposals, evaluators, deterministic fit, variability maps, metrics, icp_chain_eval_step
 #include "abi_fit_many.inl"  // C ABI: icp_fit_deterministic_many (many deterministic fits in lockstep, kernels_fit.hip)
 #include "abi_metrics_many.inl"  // C ABI: icp_mesh_metrics_many (registration metrics and Dice of many meshes, kernels_metrics.hip)
+#include "abi_variability_many.inl"  // C ABI: icp_posterior_variability_many (variability maps of many chains, kernels_variability.hip)
 #include "abi_step.inl"  // the merged step (five launches): fronts, speculative decompositions, icp_chain_step / _prelaunch
 #include "abi_wide.inl"  // the wide step's host side (kernels_wide.hip)
 #include "abi_batched.inl"  // C ABI: icp_chain_step_batched_issue / _collect / _abandon

@@ -736,4 +736,38 @@ void launch_met_stats(hipStream_t st, int n, bool big, const MetStats* jobs);
 void launch_met_samples(hipStream_t st, int n, int nmax, uint64_t seed, const MetDice* jobs);
 void launch_met_dice_count(hipStream_t st, int n, int nmax, const MetDice* jobs);
 
+// ---- posterior variability maps of many chains (kernels_variability.hip; icp_posterior_variability_many)
+constexpr int kVarInstGroup = 8;  // samples whose meshes one pass over the basis forms
+struct VarSample {      // one sample mesh to instance (device)
+  const double* coeffs; // [r] shape coefficients
+  Pose pose;
+  double* x;            // [N*3] its slot in the chunk buffer
+};
+struct VarGroup {       // up to kVarInstGroup consecutive samples of one map: one pass over that model's basis
+  const double* Qp; const double* ref; const double* mean;
+  int N, r;
+  int first, n;         // samples[first .. first+n-1]
+};
+struct VarNormalJob {   // vertex normals of one mesh
+  const double* x;
+  const int* tris; const int* adj_off; const int* adj;
+  int N;
+  double* out;          // [N*3]
+};
+struct VarSeg {         // n consecutive samples of one map, resident in the chunk buffer
+  int N, n, S, mode;    // S: the map's sample count
+  int first, last;      // the map's first / last segment (a map within one round: both)
+  const double* x;      // [n][N*3] sample meshes
+  const double* nsm;    // mode 2: [n][N*3] their vertex normals
+  double* mean;         // [N*3] Σ x_s, the mean after the last segment
+  double* nrm;          // [N*3] modes 1, 2: the map's normals (mode 2: Σ n_s, scaled after the last segment)
+  double* acc;          // [N*3] (mode 0) / [N] (modes 1, 2): centred moments carried between segments
+  double* out;          // [N]
+  double nscale;        // mode 2: 1/S as the host divides it (launch_accumulate's scale_after)
+};
+void launch_var_instance(hipStream_t st, int n_groups, int Nmax, const VarGroup* groups, const VarSample* samples);
+void launch_var_normals(hipStream_t st, int n_jobs, int Nmax, const VarNormalJob* jobs);
+void launch_var_sum(hipStream_t st, int n_segs, int Nmax, const VarSeg* segs);
+void launch_var_centred(hipStream_t st, int n_segs, int Nmax, const VarSeg* segs);
+
 }  // namespace icp

@@ -12,7 +12,8 @@ JSONExperimentLogger (api/sampling/loggers/JSONExperimentLogger.scala) writes th
 (apps/femur/StdIcpVsChainICPrandomInitComparisonAll.scala:43-64): one jsonExperimentFormat record per init, 17 fields (:29-30).
 
 Input here = the fixed-size per-step records of the host harness (host/icp_host.h): [index, status, leaf id, log value,
-theta(10 + r)], which is also what the multi-GPU gather ships.  Host I/O only; nothing here touches the device."""
+theta(10 + r)], which is also what the multi-GPU gather ships.  Host I/O only, but for variability_from_logs, which hands the sub-sampled
+states of many logs to the device in one call."""
 from __future__ import annotations
 
 import datetime as _dt
@@ -94,6 +95,41 @@ def samples_from_log(log, take_every_n: int = 50, total: int = 100, burn_in: int
         return i
     idx = [get_log_index(i) for i in range(burn_in, min(len(log), total), take_every_n)]
     return [(log[i], i) for i in idx][:min(total, len(idx))]
+
+
+def variability_from_logs(contexts, logs, take_every_n: int = 50, total: int = 10000, burn_in: int = 200, mode=(2, 0), theta_refs=None,
+                          want_mean: bool = False) -> dict:
+    """PosteriorVariabilityToMeshColor (apps/femur/ and apps/bfm/) for many chains: samples_from_log of every log (its defaults here
+    are the apps': every 50th state behind a burn-in of 200), logSamples2shapes and the variability maps, in ONE batched device call
+    (api.posterior_variability_maps).  `contexts`: one context or one per log; `logs`: per chain the list loadLog gives; `mode`: one
+    mode or several — the apps show the normal variance (2, sumNormals = true) and the total variance (0); `theta_refs`: per log, the
+    state whose normals mode 1 takes (the apps' best fit).  Returns {"maps": {mode: [one [N] map per log]}, "indices": [per log the
+    log indices samples_from_log picked]} and, with want_mean, "means": [per log the [N, 3] mean sample mesh]."""
+    from . import api as _api
+    logs = list(logs)
+    modes = [int(m) for m in mode] if isinstance(mode, (list, tuple)) else [int(mode)]
+    if not modes:
+        raise ValueError("at least one mode")
+    ctxs = list(contexts) if isinstance(contexts, (list, tuple)) else [contexts] * len(logs)
+    if len(ctxs) != len(logs):
+        raise ValueError("one context per log (or one for all)")
+    refs = list(theta_refs) if theta_refs is not None else [None] * len(logs)
+    if len(refs) != len(logs):
+        raise ValueError("one theta_ref per log")
+    picked = [samples_from_log(lg, take_every_n=take_every_n, total=total, burn_in=burn_in) for lg in logs]
+    sets = []
+    for k, sub in enumerate(picked):
+        if len(sub) < 2:
+            raise ValueError(f"log {k}: fewer than two samples behind the burn-in")
+        sets.append(np.stack([JSONAcceptRejectLogger.sample_to_model_parameters(s) for s, _ in sub]))
+    n = len(logs)
+    got = _api.posterior_variability_maps(ctxs * len(modes), sets * len(modes), [m for m in modes for _ in range(n)], refs * len(modes),
+                                          want_mean=want_mean)
+    maps, means = got if want_mean else (got, None)
+    out = {"maps": {m: maps[j * n:(j + 1) * n] for j, m in enumerate(modes)}, "indices": [[i for _, i in sub] for sub in picked]}
+    if want_mean:
+        out["means"] = means[:n]
+    return out
 
 
 # jsonExperimentFormat (api/sampling/loggers/JSONExperimentLogger.scala:29-30), in its field order

@@ -303,6 +303,27 @@ ICP_API int icp_mesh_metrics(icp_ctx *ctx, const double *theta, double *out /* [
 ICP_API int icp_mesh_metrics_many(int32_t n_items, icp_ctx *const *ctxs, const double *const *thetas, int32_t dice_samples,
                                   uint64_t dice_seed, double *out /* [n_items*9] */, int32_t *status /* [n_items] */);
 
+/* Posterior variability maps of many chains in one call, one synchronisation (PosteriorVariabilityToMeshColor's maps for every chain
+ * of apps/femur/StdIcpVsChainICPrandomInitComparisonAll.scala).  Map m is computed from the n_samples[m] states thetas[m]
+ * ([n_samples[m] * (10 + rank of ctxs[m])], poses included, registered rotation matrices honoured) in modes[m] (0, 1, 2 as in
+ * icp_posterior_variability); theta_refs[m] is read where modes[m] == 1 and may be NULL elsewhere (theta_refs itself may be NULL when
+ * no map has mode 1).  Contexts may repeat and may differ in model and rank; all are on one device.
+ *   - Same bits as the one-map call: out[m] ([N_m]) equals, bit for bit, what icp_posterior_variability(ctxs[m], n_samples[m],
+ *     thetas[m], modes[m], theta_refs[m], .) returns, whatever else the batch holds and however the samples fall into chunks.
+ *   - mean_out: NULL, or per map NULL or [3 * N_m]: the per-vertex mean (sum_s x_s) * (1/S) the map is centred on, i.e. the posterior
+ *     mean mesh, with the sum taken in sample order.
+ *   - Working memory does not grow with the number of sample meshes: they pass through one chunk buffer of 64 MiB (meshes and, in
+ *     mode 2, their vertex normals).  A map larger than the buffer is instanced twice, once for the sums and once for the centred
+ *     moments.  Besides the buffer the call holds 10 * N_m doubles per map and the samples' coefficients and poses
+ *     (rank + 18 doubles per sample).
+ *   - Launches: at most four per chunk, however many maps, contexts and models the chunk holds.
+ * ICP_ERR_INVALID_ARG (a null entry, n_maps < 0 or > 65535, fewer than two samples, an unknown mode, mode 1 without a reference,
+ * contexts on two devices, a non-finite theta): nothing has run, nothing is written.  ICP_ERR_BUSY: a context belongs to a batch
+ * in flight.  n_maps == 0 is accepted and does nothing. */
+ICP_API int icp_posterior_variability_many(int32_t n_maps, icp_ctx *const *ctxs, const int32_t *n_samples,
+                                           const double *const *thetas, const int32_t *modes, const double *const *theta_refs,
+                                           double *const *out, double *const *mean_out);
+
 /* ---------------------------------------------------------------- fused chain step (measurement harness)
  * One call = all device work one Metropolis–Hastings step needs for a NEW state theta_prop proposed from
  * theta_cur, submitted as one stream sequence with a single synchronisation: the likelihood of theta_prop and,
