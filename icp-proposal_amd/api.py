@@ -217,6 +217,15 @@ class IcpContext:
         nat.check(nat.lib().icp_transformed_mesh(self.h, _d(th), _d(out)), "icp_transformed_mesh")
         return out
 
+    def coefficients(self, mesh, pose=None) -> np.ndarray:
+        """Scalismo's model.coefficients(mesh) (σ² = 1e-5) of one mesh [N, 3]; `pose` ([s = 1 | t | angles | centre]): the rigid pose
+        taken off first.  One item of model_coefficients."""
+        return model_coefficients(self, meshes=[mesh], poses=[pose])[0]
+
+    def project(self, mesh, pose=None) -> np.ndarray:
+        """Scalismo's model.project(mesh): the instance of coefficients(mesh, pose), under `pose` where one was taken off -> [N, 3]."""
+        return model_coefficients(self, meshes=[mesh], poses=[pose], want_project=True)[1][0]
+
     def vertexNormals(self, theta) -> np.ndarray:
         th = _theta(theta)
         out = np.empty((self.N, 3))
@@ -788,3 +797,96 @@ def dice_coefficient(ctx: IcpContext, theta, samples: int = 10000, seed: int = 1
     nat.check(int(m["status"][0]), "icp_mesh_metrics_many")
     return float(m["dice"][0])
 
+
+
+def _per_item(contexts, n):
+    ctxs = list(contexts) if isinstance(contexts, (list, tuple)) else [contexts] * n
+    if n == 0 or len(ctxs) != n:
+        raise ValueError("one context per item (or one for all) and at least one item")
+    if n > 65535:
+        raise ValueError("at most 65,535 items a call")
+    return ctxs
+
+
+def transformed_meshes(contexts, thetas) -> np.ndarray:
+    """ModelFittingParameters.transformedMesh of many states in one call (icp_model_instances_many): row b is
+    contexts[b].transformedMesh(thetas[b]) bit for bit, pose and registered rotation matrices included.  `contexts`: one context or
+    one per item (they may repeat and differ in target, model and rank; the models of one call have one vertex count, so that the
+    result is one array [n, N, 3] — ReplayFittingFromLog's and RandomSamplesFromModel's loops over logged states); `thetas`:
+    [n, 10 + rank] or a list of states."""
+    th = [_f64(t).reshape(-1) for t in thetas]
+    ctxs = _per_item(contexts, len(th))
+    N = ctxs[0].N
+    for b, (c, t) in enumerate(zip(ctxs, th)):
+        if t.shape[0] != 10 + c.rank:
+            raise ValueError(f"item {b}: a state has 10 + rank values")
+        if c.N != N:
+            raise ValueError(f"item {b}: the contexts' models differ in their vertex count")
+        if not np.all(np.isfinite(t)):
+            raise ValueError(f"item {b}: theta contains a non-finite value")
+    n = len(th)
+    out = np.empty((n, N, 3))
+    c_ctx = (C.c_void_p * n)(*[c.h for c in ctxs])
+    c_th = (nat.c_double_p * n)(*[_d(t) for t in th])
+    c_out = (nat.c_double_p * n)(*[_d(out[b]) for b in range(n)])
+    nat.check(nat.lib().icp_model_instances_many(n, c_ctx, c_th, c_out), "icp_model_instances_many")
+    return out
+
+
+def model_coefficients(contexts, meshes=None, thetas=None, poses=None, want_project: bool = False):
+    """Scalismo's model.coefficients(mesh) — and model.project(mesh) — of many meshes in one call (icp_model_coefficients_many):
+    c = (QᵀQ + σ²I)⁻¹ Qᵀ(x − x̄ − μ), σ² = 1e-5, as NonRigidIcpProposal.scala:59 and IcpBasedSurfaceFitting.scala:84 use it.
+    `contexts`: one context or one per item, all of ONE model.  Item b's mesh is meshes[b] ([N, 3], the model's vertex order) or the
+    transformedMesh of thetas[b] (instanced on the device): give `meshes`, or `thetas`, or both as lists with None where the other
+    one holds the item.  `poses`: None, or per item None or [s | t | angles | centre] with s exactly 1 — the rigid pose taken off the
+    vertices first (a chain state's theta[:10]); without one the mesh is taken to be in model space.  Returns the coefficients
+    [n, rank]; with want_project also the projections [n, N, 3] (the instance of c, under the item's pose where one was taken off:
+    the bits of transformedMesh([pose or identity | c])).  An item with a non-finite vertex raises IcpNativeError (-3)."""
+    ms = list(meshes) if meshes is not None else None
+    ts = list(thetas) if thetas is not None else None
+    if ms is None and ts is None:
+        raise ValueError("give meshes, thetas, or both")
+    n = len(ms) if ms is not None else len(ts)
+    if ts is not None and len(ts) != n:
+        raise ValueError("meshes and thetas must have one entry per item")
+    ctxs = _per_item(contexts, n)
+    ps = list(poses) if poses is not None else [None] * n
+    if len(ps) != n:
+        raise ValueError("one pose per item (None where there is none)")
+    r, N = ctxs[0].rank, ctxs[0].N
+    pts, th, po = [], [], []
+    for b in range(n):
+        if ctxs[b].rank != r or ctxs[b].N != N:
+            raise ValueError(f"item {b}: the items of one call share a model")
+        m = ms[b] if ms is not None else None
+        t = ts[b] if ts is not None else None
+        if (m is None) == (t is None):
+            raise ValueError(f"item {b}: a mesh or a theta, one of the two")
+        if m is not None:
+            m = _f64(m)
+            if m.size != 3 * N:
+                raise ValueError(f"item {b}: a mesh has the model's {N} vertices")
+            m = m.reshape(N, 3)
+        else:
+            t = _f64(t).reshape(-1)
+            if t.shape[0] != 10 + r or not np.all(np.isfinite(t)):
+                raise ValueError(f"item {b}: theta must be 10 + rank finite values")
+        p = ps[b]
+        if p is not None:
+            p = _f64(p).reshape(-1)
+            if p.shape[0] != 10 or not np.all(np.isfinite(p)):
+                raise ValueError(f"item {b}: a pose is 10 finite values [s | t | angles | centre]")
+            if p[0] != 1.0:
+                raise ValueError(f"item {b}: the scale of a pose to take off must be exactly 1")
+        pts.append(m)
+        th.append(t)
+        po.append(p)
+    coeffs = np.zeros((n, r))
+    proj = np.zeros((n, N, 3)) if want_project else None
+    status = np.zeros(n, dtype=np.int32)
+    c_ctx = (C.c_void_p * n)(*[c.h for c in ctxs])
+    as_p = lambda arrs: (nat.c_double_p * n)(*[_d(a) if a is not None else None for a in arrs])  # noqa: E731
+    c_proj = (nat.c_double_p * n)(*[_d(proj[b]) for b in range(n)]) if want_project else None
+    rc = nat.lib().icp_model_coefficients_many(n, c_ctx, as_p(pts), as_p(th), as_p(po), _d(coeffs), c_proj, _i(status))
+    nat.check(rc, "icp_model_coefficients_many")
+    return (coeffs, proj) if want_project else coeffs

@@ -770,4 +770,24 @@ void launch_var_normals(hipStream_t st, int n_jobs, int Nmax, const VarNormalJob
 void launch_var_sum(hipStream_t st, int n_segs, int Nmax, const VarSeg* segs);
 void launch_var_centred(hipStream_t st, int n_segs, int Nmax, const VarSeg* segs);
 
+// ---- model projection of many meshes (kernels_projection.hip; icp_model_coefficients_many)
+constexpr int kProjGroup = 16;         // items side by side in one matrix instruction: the basis is read once per group
+constexpr int kProjMinSlabRows = 256;  // rows of the basis (3 per vertex) in a slab, at least …
+constexpr int kProjMaxSlabs = 128;     // … and slabs per mesh, at most
+struct ProjItem {       // one mesh of a chunk (device)
+  const double* x;      // [N*3] its vertices in the chunk buffer (uploaded, or the instance of the item's state)
+  Pose pose;            // has_pose != 0: the rigid pose taken off first
+  int has_pose;
+};
+int proj_slab_rows(int N);  // a function of the model alone: an item's sums do not depend on the batch
+int proj_slabs(int N);
+// D[group][3N][kProjGroup] = un-posed x − x̄ − μ of the chunk's n items (padding items of the last group: zeros); nonfinite[item] += 1
+// per non-finite vertex
+void launch_proj_residual(hipStream_t st, int n, int N, const double* ref, const double* mean, const ProjItem* items, double* D,
+                          int* nonfinite);
+// part[group][slab][rpad][kProjGroup] = Qᵀ·D per slab of rows (Q row-major [3N][r]; rpad = r rounded up to 16)
+void launch_proj_gemm(hipStream_t st, int n, int N, int r, const double* Q, const double* D, double* part);
+// coeffs[item][r] = P · Σ_slabs part
+void launch_proj_solve(hipStream_t st, int n, int N, int r, const double* part, const double* P, double* coeffs);
+
 }  // namespace icp

@@ -132,6 +132,16 @@ def variability_from_logs(contexts, logs, take_every_n: int = 50, total: int = 1
     return out
 
 
+def experiment_coefficients(contexts, thetas) -> np.ndarray:
+    """The study's model.coefficients(best mesh) (apps/femur/StdIcpVsChainICPrandomInitComparisonAll.scala:53-55) for a list of chain
+    states, in ONE batched device call (api.model_coefficients): row b is the regularised projection (sigma2 = 1e-5) of the mesh of
+    thetas[b] with its own pose taken off — what JSONExperimentLogger.append's coeff* fields hold in the reference.  `contexts`:
+    one context or one per state (one model); `thetas`: [n, 10 + rank] with scale 1.  Returns [n, rank]."""
+    from . import api as _api
+    th = [np.ascontiguousarray(t, dtype=np.float64).reshape(-1) for t in thetas]
+    return _api.model_coefficients(contexts, thetas=th, poses=[t[:10] for t in th])
+
+
 # jsonExperimentFormat (api/sampling/loggers/JSONExperimentLogger.scala:29-30), in its field order
 EXPERIMENT_FIELDS = ("index", "modelPath", "targetPath", "samplingEuclideanLoggerPath", "samplingHausdorffLoggerPath", "coeffInit",
                      "coeffSamplingEuclidean", "coeffSamplingHausdorff", "coeffIcp", "samplingEuclidean", "samplingHausdorff", "icp",
@@ -142,9 +152,10 @@ METRIC_KEYS = ("avg", "hausdorff", "dice")  # distMeasure of the study (StdIcpVs
 
 class JSONExperimentLogger:
     """api/sampling/loggers/JSONExperimentLogger.scala: the experiment summary (experiments.json) of the femur study.
-    The coeff* fields take the coefficient vectors they are given — the caller passes the thetas' own coefficients (theta[10:]),
-    where the reference logs model.coefficients(mesh), the regularised projection (sigma2 = 1e-5) of a mesh that is itself a model
-    instance (a stated deviation).  The metric maps are keyed avg / hausdorff / dice (registration_metrics gives all three)."""
+    The coeff* fields take the coefficient vectors they are given.  The reference logs model.coefficients(mesh), the regularised
+    projection (sigma2 = 1e-5) of the best meshes: experiment_coefficients gives those vectors for a list of states in one call
+    (theta[10:] itself differs from them by up to 5.8e-6 at rank 201).  The metric maps are keyed avg / hausdorff / dice
+    (registration_metrics gives all three)."""
 
     def __init__(self, file_path, model_path: str = ""):
         self.file_path = str(file_path)

@@ -324,6 +324,44 @@ ICP_API int icp_posterior_variability_many(int32_t n_maps, icp_ctx *const *ctxs,
                                            const double *const *thetas, const int32_t *modes, const double *const *theta_refs,
                                            double *const *out, double *const *mean_out);
 
+/* ---------------------------------------------------------------- model projection of many meshes
+ * Scalismo's model.instance / model.coefficients / model.project for many items in one call, one synchronisation
+ * (apps/femur/StdIcpVsChainICPrandomInitComparisonAll.scala:53-55 logs model.coefficients(best mesh) of 300 meshes per target;
+ * RunMHRandomInitComparison.scala:72 starts every chain from model.coefficients(initShape)).
+ *
+ * icp_model_instances_many: points_out[b] ([3 * N_b]) = the bits of icp_transformed_mesh(ctxs[b], thetas[b], .), pose and registered
+ * rotation matrices included.  Contexts may repeat and may differ in model and rank; all are on one device. */
+ICP_API int icp_model_instances_many(int32_t n_items, icp_ctx *const *ctxs, const double *const *thetas,
+                                     double *const *points_out /* [3*N] each */);
+
+/* icp_model_coefficients_many, per item b (all contexts share one device and ONE model; they may repeat):
+ *   - the mesh: exactly one of points[b] ([3 * N] vertices in the model's vertex order) and thetas[b] (the state whose
+ *     transformedMesh is meant, instanced on the device with its pose: only 10 + rank doubles go up) is non-NULL; either array
+ *     pointer may itself be NULL when no item uses it.
+ *   - poses (NULL, or per item NULL or 10 doubles [s | t | angles | centre], s exactly 1): the inverse rigid pose
+ *     R^T((p - t) - ctr) + ctr is applied to the vertices first, with the context's registered rotation matrix where the angles have
+ *     one.  Without a pose the mesh is taken to be in model space, as model.coefficients takes it.
+ *   - coeffs_out[b * rank ..] = c = P * Q^T (x - ref - mean) with Q = basis * sqrt(variance) and the context's resident
+ *     P = (Q^T Q + sigma2 I)^-1, sigma2 = 1e-5: DiscreteLowRankGaussianProcess.coefficients as NonRigidIcpProposal.scala:59 and
+ *     IcpBasedSurfaceFitting.scala:84 call it.  Of a model instance with coefficients c0 this is c0 - sigma2 * P * c0, not c0.
+ *   - project_out (NULL, or per item NULL or [3 * N]) = model.project(mesh): the instance of c, under the item's pose where one was
+ *     taken off; its bits equal icp_transformed_mesh of [pose or (1, 0, ..., 0) | c].
+ * The meshes pass through a chunk buffer of 32 MiB, with as much again (rounded up to 16 meshes) for the residuals and at most as much
+ * for partial sums: no mesh outlives its chunk.  Besides these the call holds rank doubles and a 144-byte record per item (and an
+ * instance record of 144 bytes per item given as a state or projected).
+ * An item's bits depend neither on the other items, nor on their order, nor on how the items fall into chunks.
+ * Limits: no scale in the pose to take off; one model per call; meshes need the model's vertex count and order (no correspondence
+ * is built here).
+ * ICP_ERR_INVALID_ARG (a null entry, n_items outside [1, 65535], both or neither of points / theta for an item, a non-finite theta
+ * or pose, s != 1 in a pose, mixed devices — or, for the coefficients, mixed models): nothing has run, nothing is written.
+ * ICP_ERR_BUSY: a context belongs to a batch in flight.  Otherwise status[b] = ICP_OK, or ICP_ERR_NOT_FINITE for an item whose mesh
+ * has a non-finite vertex (its coefficient row and projection are NaN; the other items are untouched), and the return value is
+ * ICP_OK or the first failing item's. */
+ICP_API int icp_model_coefficients_many(int32_t n_items, icp_ctx *const *ctxs, const double *const *points,
+                                        const double *const *thetas, const double *const *poses,
+                                        double *coeffs_out /* [n_items*rank] */, double *const *project_out,
+                                        int32_t *status /* [n_items] */);
+
 /* ---------------------------------------------------------------- fused chain step (measurement harness)
  * One call = all device work one Metropolis–Hastings step needs for a NEW state theta_prop proposed from
  * theta_cur, submitted as one stream sequence with a single synchronisation: the likelihood of theta_prop and,
