@@ -111,6 +111,9 @@ SIGNATURES = {
     "icp_model_instances_many": (C.c_int, [C.c_int32, C.POINTER(C.c_void_p), C.POINTER(c_double_p), C.POINTER(c_double_p)]),
     "icp_model_coefficients_many": (C.c_int, [C.c_int32, C.POINTER(C.c_void_p), C.POINTER(c_double_p), C.POINTER(c_double_p),
                                               C.POINTER(c_double_p), c_double_p, C.POINTER(c_double_p), c_int_p]),
+    "icp_posterior_models_many": (C.c_int, [C.c_int32, C.POINTER(C.c_void_p), c_int_p, C.POINTER(c_int_p), C.POINTER(c_double_p),
+                                            C.POINTER(c_double_p), C.POINTER(c_double_p), C.POINTER(c_double_p), C.POINTER(c_double_p),
+                                            C.POINTER(c_double_p), C.POINTER(c_double_p), C.POINTER(c_double_p), c_int_p]),
     "icp_chain_step": (C.c_int, [C.c_void_p, C.c_int32, C.POINTER(C.c_void_p), C.c_int32, c_double_p, c_double_p, c_double_p,
                                  c_double_p, c_double_p, c_double_p]),
     "icp_chain_step_batched_issue": (C.c_int, [C.c_int32, C.POINTER(C.c_void_p), C.c_int32, C.POINTER(C.c_void_p), C.POINTER(C.c_int32),

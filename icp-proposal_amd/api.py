@@ -226,6 +226,17 @@ class IcpContext:
         """Scalismo's model.project(mesh): the instance of coefficients(mesh, pose), under `pose` where one was taken off -> [N, 3]."""
         return model_coefficients(self, meshes=[mesh], poses=[pose], want_project=True)[1][0]
 
+    def posterior(self, vertex_ids, points, sigma2=None, covariances=None):
+        """Scalismo's model.posterior(correspondences, noise) as a model (IcpBasedSurfaceFitting.scala:81 with sigma2,
+        NonRigidIcpProposal.scala:152 with covariances [n, 3, 3]; NonRigidIcpProposal.scala:77): the model conditioned on the observed
+        positions `points` [n, 3] (model space) of the vertices `vertex_ids` -> data.StatisticalMeshModel over the same reference and
+        cells, which a new IcpContext accepts.  One item of posterior_models."""
+        res = posterior_models(self, [vertex_ids], [points], sigma2=None if sigma2 is None else [sigma2],
+                               covariances=None if covariances is None else [covariances], want=("mean", "basis", "variance"))[0]
+        nat.check(res["status"], "icp_posterior_models_many")
+        m = self.model
+        return _data.StatisticalMeshModel(m.ref_points, m.cells, res["mean"], res["basis"], res["variance"])
+
     def vertexNormals(self, theta) -> np.ndarray:
         th = _theta(theta)
         out = np.empty((self.N, 3))
@@ -890,3 +901,77 @@ def model_coefficients(contexts, meshes=None, thetas=None, poses=None, want_proj
     rc = nat.lib().icp_model_coefficients_many(n, c_ctx, as_p(pts), as_p(th), as_p(po), _d(coeffs), c_proj, _i(status))
     nat.check(rc, "icp_model_coefficients_many")
     return (coeffs, proj) if want_project else coeffs
+
+
+_POSTERIOR_WANT = ("alpha", "mean", "basis", "variance", "point_variance")
+
+
+def posterior_models(contexts, vertex_ids, points, sigma2=None, covariances=None, want=_POSTERIOR_WANT):
+    """Posterior shape models of many sets of correspondences in one call (icp_posterior_models_many): item b conditions
+    contexts[b]'s model on the observed positions points[b] ([n_b, 3], model space) of its vertices vertex_ids[b] ([n_b], repeats
+    allowed), with the noise in exactly one of two forms per item — sigma2[b] (one positive number, isotropic:
+    IcpBasedSurfaceFitting.scala:81) or covariances[b] ([n_b, 3, 3] symmetric positive definite: NonRigidIcpProposal.scala:152);
+    `sigma2` / `covariances` are None or lists with None where the other one holds the item.  `contexts`: one context or one per item
+    (they may repeat and differ in model and rank).  `want` names the outputs to fetch.  Returns one dict per item: "status" (0, or −3
+    for a covariance that is not positive definite — that item's arrays are NaN —, or −1 for a rank above 256 — its arrays are
+    absent) and the wanted ones of "alpha" [r], "mean" [N, 3] (the posterior model's mean deformation μ + Q·α), "basis" [3N, r]
+    (Φ·V, unscaled), "variance" [r] (descending), "point_variance" [N] (trace of every vertex's 3 × 3 posterior covariance)."""
+    ids = [np.ascontiguousarray(v, dtype=np.int32).reshape(-1) for v in vertex_ids]
+    n = len(ids)
+    ctxs = _per_item(contexts, n)
+    pts = list(points)
+    s2 = list(sigma2) if sigma2 is not None else [None] * n
+    cov = list(covariances) if covariances is not None else [None] * n
+    if len(pts) != n or len(s2) != n or len(cov) != n:
+        raise ValueError("vertex_ids, points and the noise have one entry per item")
+    want = tuple(want)
+    for w in want:
+        if w not in _POSTERIOR_WANT:
+            raise ValueError(f"unknown output {w!r}: one of {_POSTERIOR_WANT}")
+    p_arr, s_arr, c_arr = [], [], []
+    for b in range(n):
+        k = ids[b].shape[0]
+        if k < 1:
+            raise ValueError(f"item {b}: at least one observation")
+        if ids[b].min() < 0 or ids[b].max() >= ctxs[b].N:
+            raise ValueError(f"item {b}: vertex id out of range")
+        p = _f64(pts[b])
+        if p.size != 3 * k:
+            raise ValueError(f"item {b}: one observed position [3] per vertex id")
+        if not np.all(np.isfinite(p)):
+            raise ValueError(f"item {b}: points contain a non-finite value")
+        if (s2[b] is None) == (cov[b] is None):
+            raise ValueError(f"item {b}: the noise is sigma2 or covariances, one of the two")
+        if s2[b] is not None:
+            v = float(s2[b])
+            if not (math.isfinite(v) and v > 0.0):
+                raise ValueError(f"item {b}: sigma2 must be finite and positive")
+            s_arr.append(np.array([v]))
+            c_arr.append(None)
+        else:
+            c = _f64(cov[b])
+            if c.size != 9 * k:
+                raise ValueError(f"item {b}: one 3 x 3 covariance per observation")
+            if not np.all(np.isfinite(c)):
+                raise ValueError(f"item {b}: covariances contain a non-finite value")
+            s_arr.append(None)
+            c_arr.append(c.reshape(k, 3, 3))
+        p_arr.append(p.reshape(k, 3))
+    shapes = {"alpha": lambda c: (c.rank,), "mean": lambda c: (c.N, 3), "basis": lambda c: (3 * c.N, c.rank),
+              "variance": lambda c: (c.rank,), "point_variance": lambda c: (c.N,)}
+    out = [{w: np.zeros(shapes[w](c)) for w in want} for c in ctxs]
+    as_p = lambda arrs: (nat.c_double_p * n)(*[_d(a) if a is not None else None for a in arrs])  # noqa: E731
+    outs = [as_p([o[w] for o in out]) if w in want else None for w in _POSTERIOR_WANT]
+    status = np.zeros(n, dtype=np.int32)
+    n_obs = np.array([a.shape[0] for a in ids], dtype=np.int32)
+    c_ctx = (C.c_void_p * n)(*[c.h for c in ctxs])
+    c_ids = (nat.c_int_p * n)(*[_i(a) for a in ids])
+    rc = nat.lib().icp_posterior_models_many(n, c_ctx, _i(n_obs), c_ids, as_p(p_arr), as_p(s_arr), as_p(c_arr), *outs, _i(status))
+    if rc != 0 and not status.any():
+        nat.check(rc, "icp_posterior_models_many")  # a whole-call error: nothing has run
+    for b in range(n):
+        out[b]["status"] = int(status[b])
+        if status[b] == -1:
+            for w in want:
+                del out[b][w]
+    return out

@@ -790,4 +790,29 @@ void launch_proj_gemm(hipStream_t st, int n, int N, int r, const double* Q, cons
 // coeffs[item][r] = P · Σ_slabs part
 void launch_proj_solve(hipStream_t st, int n, int N, int r, const double* part, const double* P, double* coeffs);
 
+// ---- posterior shape models from given correspondences (kernels_posterior_model.hip; icp_posterior_models_many)
+struct PmItem {         // one item's r-space record (device): its observations, its model, its slot of r-space scratch
+  int K, splits, r, ldb;  // observations; regression_splits(K); rank; columns of Bm (r + 1 rounded up to 16)
+  const int* id;        // [K] model vertex of every observation
+  const double* pt;     // [K*3] observed positions (model space)
+  const double* W;      // [K*6] precisions Σ_i⁻¹: xx xy xz yy yz zz
+  const double* Q; const double* ref; const double* mean; const double* inv_sqrt_lambda;
+  double* Mpart;        // splits · (r+1)² partial sums, regression_tile's layout
+  const double* V;      // [r*r] eigenvectors of D M⁻¹ D (columns)
+  const double* alpha;  // [r]
+  double* Bm;           // [r rounded up to 16][ldb] = [D⁻¹V | α], zero padding
+};
+struct PmPiece {        // rows row0 .. row0+rows-1 of one item's Q·Bm, resident in the chunk buffer (device)
+  const double* Q; const double* Bm; const double* mu; const double* S;
+  int r, ldb, row0, rows;
+  int t0;               // first 16-column tile to compute (0: the basis and the mean; the tile of column r: the mean alone)
+  double* basis;        // [rows][r] (null: not kept)
+  double* mean;         // [rows] μ + Q·α (null: not asked for)
+  double* pvar;         // [rows/3] Σ_d Σ_j S_j·basis[3i+d][j]² (null: not asked for; needs `basis`)
+};
+void launch_pm_regression(hipStream_t st, int n, int splits_max, int rmax, const PmItem* items);
+void launch_pm_operand(hipStream_t st, int n, int rmax, const PmItem* items);
+void launch_pm_gemm(hipStream_t st, int n_pieces, int rows_max, int col_tiles_max, const PmPiece* pieces);
+void launch_pm_point_variance(hipStream_t st, int n_pieces, int rows_max, const PmPiece* pieces);
+
 }  // namespace icp

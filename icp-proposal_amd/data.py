@@ -116,6 +116,24 @@ def rigid_landmark_transform(src: np.ndarray, dst: np.ndarray):
     return rot, cd - rot @ cs
 
 
+def landmark_correspondences(model: "StatisticalMeshModel", model_landmarks, target_landmarks):
+    """Landmark pairs as correspondences of the model (IcpContext.posterior / posterior_models): every model landmark [L, 3] is
+    matched to the nearest reference vertex (the lowest index where several are equally near: a fixed rule on
+    the reference mesh) and observed at its target landmark.  -> (vertex_ids [L] int32, points [L, 3])."""
+    ml = np.ascontiguousarray(model_landmarks, dtype=np.float64).reshape(-1, 3)
+    tl = np.ascontiguousarray(target_landmarks, dtype=np.float64).reshape(-1, 3)
+    if ml.shape != tl.shape or ml.shape[0] < 1:
+        raise ValueError("one target landmark per model landmark, at least one pair")
+    if not (np.all(np.isfinite(ml)) and np.all(np.isfinite(tl))):
+        raise ValueError("landmarks contain a non-finite value")
+    ref = model.ref_points
+    ids = np.empty(ml.shape[0], dtype=np.int32)
+    for k in range(ml.shape[0]):
+        d = ref - ml[k]
+        ids[k] = int(np.argmin((d[:, 0] * d[:, 0] + d[:, 1] * d[:, 1]) + d[:, 2] * d[:, 2]))  # (argmin: the first of equal minima)
+    return ids, tl.copy()
+
+
 def load_femur_model_and_target(n_components: int = 50):
     """Counterpart of reference `apps/femur/LoadTestData.scala:32-50`: model + landmark-aligned target mesh."""
     model = load_femur_model(n_components)

@@ -431,6 +431,52 @@ ICP_API int icp_chain_step_batched_issue(int32_t n_chains, icp_evaluator *const 
 ICP_API int icp_chain_step_batched_collect(icp_step_ticket *ticket);
 ICP_API int icp_chain_step_batched_abandon(icp_step_ticket *ticket);
 
+/* ---------------------------------------------------------------- posterior shape models from given correspondences, many in one call
+ * Scalismo's model.posterior(correspondences, noise) and its discretisation as a model (api/other/IcpBasedSurfaceFitting.scala:81 with
+ * isotropic noise, NonRigidIcpProposal.scala:152 with a 3 x 3 covariance per point, NonRigidIcpProposal.scala:77 for the model), for
+ * correspondences the CALLER hands in: landmark pairs, a dense correspondence of an earlier fit.  SURVEY App. A.4, as the chain's own
+ * posterior implements it:  M = I + sum Q_i^T Sigma_i^-1 Q_i,  b = sum Q_i^T Sigma_i^-1 (y_i - xbar_i - mu_i),  alpha = M^-1 b,
+ * D M^-1 D = V S V^T  (Q = Phi D the scaled basis, D = diag(sqrt(variance))).  V has the canonical signs and the ordering of
+ * icp_posterior_view.V for the same M.
+ * Per item b (all contexts on ONE device; they may repeat, and they may differ in model and rank):
+ *   ctxs[b]; n_obs[b] >= 1; vertex_ids[b] [n_obs]: model vertices in [0, N), repeats allowed (as Scalismo's regression allows them);
+ *   points[b] [3 * n_obs]: the observed positions in MODEL space (the displacement is y_i - xbar_id - mu_id; take a pose off first);
+ *   the noise in exactly one of two forms: sigma2[b] -> ONE finite positive double (isotropic, sigma2 * I), or covariances[b]
+ *   [9 * n_obs]: a symmetric positive-definite 3 x 3 per observation, row-major (its symmetric part is used), inverted in closed form
+ *   in plain f64.  `sigma2` and `covariances` may each be NULL as a whole where no item uses that form.
+ * Outputs (each array may be NULL as a whole, and each entry of it may be NULL):
+ *   alpha_out[b] [r];  mean_out[b] [3N] = mu + Q alpha (the posterior model's mean_deformation);  basis_out[b] [3N * r] = Phi V,
+ *   row-major and unscaled like icp_model_desc.basis;  variance_out[b] [r] = S, descending;  point_variance_out[b] [N]: entry i =
+ *   sum_d sum_j S_j (Phi V)[3i+d][j]^2, the trace of vertex i's 3 x 3 block of Q M^-1 Q^T;  status[b].
+ * (ref_points, triangles, mean_out[b], basis_out[b], variance_out[b]) with the model's own reference and triangles IS a valid
+ * icp_model_desc: icp_ctx_create accepts it, and a context made from it registers with the conditioned model.
+ * One submission and one synchronisation per call: the regression sums of a group of items are ONE launch, their factorisations and
+ * decompositions run side by side rank by rank (the chain's own many-problem kernels), and Phi [V | D alpha] - the mean is the extra
+ * column - is a gfx950 kernel on the f64 matrix cores (v_mfma_f64_16x16x4_f64); point_variance is a pass over the rows that kernel has
+ * just written, in a fixed order, without floating-point atomics.  (Only an item whose spectrum the side-by-side decomposition cannot
+ * separate - equal eigenvalues - is decomposed again on its own behind a second synchronisation, as the chain does.)
+ * Fixed working memory, whatever n_items and N:
+ *   - ONE chunk buffer of ICP_POSTERIOR_MODELS_CHUNK_BYTES through which every output row streams back (a face-sized basis_out is
+ *     137 MB; no item's basis is resident as a whole beyond this buffer);
+ *   - r-space scratch for at most ICP_POSTERIOR_MODELS_GROUP items at a time, each at most ICP_POSTERIOR_MODELS_SLOT_BYTES(r, s) with
+ *     r the largest rank of the call and s = min(64, ceil(largest n_obs / 8)) the split count of its regression;
+ *   - the call's inputs (n_obs * (4 + 24 + 48) bytes per item) and 16 * r + 16 bytes of results per item.
+ * An item's bits depend neither on the other items of the call, nor on their order, nor on how its rows fall into the chunk buffer.
+ * Ranks: every rank the resident decompositions serve, i.e. r <= 256.  An item of a larger rank gets status[b] = ICP_ERR_INVALID_ARG
+ * and nothing is written for it; the other items are computed.
+ * Whole-call errors - nothing has run, nothing is written, status included: ICP_ERR_INVALID_ARG (a null entry, n_items outside
+ * [1, 65535], n_obs < 1, an id out of range, both noise forms given for an item or neither, a non-finite input, sigma2 <= 0, contexts
+ * on two devices); ICP_ERR_BUSY (a context belongs to a batch in flight).  Otherwise status[b] = ICP_OK, or ICP_ERR_NOT_FINITE for an
+ * item with a covariance that is not positive definite or whose M failed to factor: that item's outputs are NaN, the other items are
+ * untouched by it; the return value is ICP_OK or the first failing item's status. */
+#define ICP_POSTERIOR_MODELS_CHUNK_BYTES (32u << 20)
+#define ICP_POSTERIOR_MODELS_GROUP 16
+#define ICP_POSTERIOR_MODELS_SLOT_BYTES(r, s) (8ull * ((unsigned long long)(s) * ((r) + 1) * ((r) + 1) + 50ull * ((r) + 17) * ((r) + 17) + 4096))
+ICP_API int icp_posterior_models_many(int32_t n_items, icp_ctx *const *ctxs, const int32_t *n_obs, const int32_t *const *vertex_ids,
+                                      const double *const *points, const double *const *sigma2, const double *const *covariances,
+                                      double *const *alpha_out, double *const *mean_out, double *const *basis_out,
+                                      double *const *variance_out, double *const *point_variance_out, int32_t *status);
+
 /* ---------------------------------------------------------------- the per-method entry points as ONE submission per step (round 6)
  * The drop-in contract is "Scalismo's chain, unchanged": MetropolisHastings.next (constructed at
  * api/sampling/SamplingRegistration.scala:52-58) calls  logValue(current) [memoised] → propose(current) → logValue(proposal) →
