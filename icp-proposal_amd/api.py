@@ -593,6 +593,28 @@ def _direction_code(direction) -> int:
     raise ValueError(f"unknown projection direction {direction!r}")
 
 
+def _per_item(contexts, n, what="item", empty_ok=False):
+    """The contexts of a batched call: one per item, or one for all; at most 65,535 items."""
+    ctxs = list(contexts) if isinstance(contexts, (list, tuple)) else [contexts] * n
+    if empty_ok:
+        if len(ctxs) != n:
+            raise ValueError(f"one context per {what} (or one for all)")
+    elif n == 0 or len(ctxs) != n:
+        raise ValueError(f"one context per {what} (or one for all) and at least one {what}")
+    if n > 65535:
+        raise ValueError(f"at most 65,535 {what}s a call")
+    return ctxs
+
+
+def _ptr_array(arrays, ptype=nat.c_double_p, conv=_d):
+    """A ctypes array of one pointer per entry (None: a null pointer): `conv` makes a `ptype` of an entry."""
+    return (ptype * max(len(arrays), 1))(*[conv(a) if a is not None else None for a in arrays])
+
+
+def _ctx_array(ctxs):
+    return (C.c_void_p * len(ctxs))(*[c.h for c in ctxs])
+
+
 def icp_fits(contexts, theta_inits, numIterations: int, iterationSeq=(1.0, 0.1, 0.01), projectionDirection=ModelSampling,
              modelPointIds=None, targetPointSamples=None, stepLength: float = 1.0, directions=None, seed=None):
     """Many deterministic ICP fits (IcpBasedSurfaceFitting.runfitting, api/other/IcpBasedSurfaceFitting.scala:46-126) in one call
@@ -608,9 +630,7 @@ def icp_fits(contexts, theta_inits, numIterations: int, iterationSeq=(1.0, 0.1, 
     if th.ndim != 2:
         raise ValueError("theta_inits must be [n_fits, 10 + rank]")
     n = th.shape[0]
-    ctxs = list(contexts) if isinstance(contexts, (list, tuple)) else [contexts] * n
-    if n == 0 or len(ctxs) != n:
-        raise ValueError("one context per fit (or one for all) and at least one fit")
+    ctxs = _per_item(contexts, n, "fit")
     r = ctxs[0].rank
     if th.shape[1] != 10 + r or any(c.rank != r for c in ctxs):
         raise ValueError("theta_inits and the contexts' rank disagree")
@@ -639,12 +659,10 @@ def icp_fits(contexts, theta_inits, numIterations: int, iterationSeq=(1.0, 0.1, 
     fps = [nat.FitParams(code, ids.shape[0], _i(ids), tp.shape[0], _d(tp), float(stepLength)) for tp in tps]
     out = th.copy()
     status = np.zeros(n, dtype=np.int32)
-    c_ctx = (C.c_void_p * n)(*[c.h for c in ctxs])
-    c_fp = (C.POINTER(nat.FitParams) * n)(*[C.pointer(fp) for fp in fps])
-    c_in = (nat.c_double_p * n)(*[_d(th[b]) for b in range(n)])
-    c_out = (nat.c_double_p * n)(*[_d(out[b]) for b in range(n)])
+    c_fp = _ptr_array(fps, C.POINTER(nat.FitParams), C.pointer)
     c_dirs = dirs.ctypes.data_as(nat.c_ubyte_p) if dirs is not None else None
-    rc = nat.lib().icp_fit_deterministic_many(n, c_ctx, c_fp, c_in, c_dirs, int(numIterations), sig.shape[0], _d(sig), c_out, _i(status))
+    rc = nat.lib().icp_fit_deterministic_many(n, _ctx_array(ctxs), c_fp, _ptr_array(list(th)), c_dirs, int(numIterations), sig.shape[0],
+                                              _d(sig), _ptr_array(list(out)), _i(status))
     if rc not in (0, -3, -4) or (rc != 0 and not np.any(status != 0)):
         nat.check(rc, "icp_fit_deterministic_many")
     return out, status
@@ -701,17 +719,13 @@ def posterior_variability_maps(contexts, sample_sets, mode=0, theta_refs=None, w
     maps; with want_mean also the list of [N_m, 3] mean sample meshes."""
     sets = list(sample_sets)
     n = len(sets)
-    ctxs = list(contexts) if isinstance(contexts, (list, tuple)) else [contexts] * n
-    if len(ctxs) != n:
-        raise ValueError("one context per map (or one for all)")
+    ctxs = _per_item(contexts, n, "map", empty_ok=True)
     modes = [int(v) for v in mode] if isinstance(mode, (list, tuple, np.ndarray)) else [int(mode)] * n
     if len(modes) != n:
         raise ValueError("one mode per map (or one for all)")
     refs = list(theta_refs) if theta_refs is not None else [None] * n
     if len(refs) != n:
         raise ValueError("one theta_ref per map")
-    if n > 65535:
-        raise ValueError("at most 65,535 maps a call")
     th, rf = [], []
     for m in range(n):
         a = _f64(sets[m])
@@ -735,15 +749,11 @@ def posterior_variability_maps(contexts, sample_sets, mode=0, theta_refs=None, w
     outs = [np.zeros(c.N) for c in ctxs]
     means = [np.zeros((c.N, 3)) for c in ctxs] if want_mean else None
     if n > 0:
-        c_ctx = (C.c_void_p * n)(*[c.h for c in ctxs])
         c_n = np.array([a.shape[0] for a in th], dtype=np.int32)
         c_mode = np.array(modes, dtype=np.int32)
-        c_th = (nat.c_double_p * n)(*[_d(a) for a in th])
-        c_rf = (nat.c_double_p * n)(*[_d(a) if a is not None else None for a in rf])
-        c_out = (nat.c_double_p * n)(*[_d(a) for a in outs])
-        c_mean = (nat.c_double_p * n)(*[_d(a) for a in means]) if want_mean else None
-        nat.check(nat.lib().icp_posterior_variability_many(n, c_ctx, _i(c_n), c_th, _i(c_mode), c_rf, c_out, c_mean),
-                  "icp_posterior_variability_many")
+        c_mean = _ptr_array(means) if want_mean else None
+        nat.check(nat.lib().icp_posterior_variability_many(n, _ctx_array(ctxs), _i(c_n), _ptr_array(th), _i(c_mode), _ptr_array(rf),
+                                                           _ptr_array(outs), c_mean), "icp_posterior_variability_many")
     return (outs, means) if want_mean else outs
 
 
@@ -773,11 +783,7 @@ def registration_metrics(contexts, thetas, dice_samples: int = 10000, seed: int 
     if th.ndim != 2:
         raise ValueError("thetas must be [n_items, 10 + rank]")
     n = th.shape[0]
-    ctxs = list(contexts) if isinstance(contexts, (list, tuple)) else [contexts] * n
-    if n == 0 or len(ctxs) != n:
-        raise ValueError("one context per item (or one for all) and at least one item")
-    if n > 65535:
-        raise ValueError("at most 65,535 items a call")
+    ctxs = _per_item(contexts, n)
     r = ctxs[0].rank
     if th.shape[1] != 10 + r or any(c.rank != r for c in ctxs):
         raise ValueError("thetas and the contexts' rank disagree")
@@ -791,9 +797,7 @@ def registration_metrics(contexts, thetas, dice_samples: int = 10000, seed: int 
         raise ValueError("seed must be an unsigned 64-bit integer")
     out = np.zeros((n, 9))
     status = np.zeros(n, dtype=np.int32)
-    c_ctx = (C.c_void_p * n)(*[c.h for c in ctxs])
-    c_th = (nat.c_double_p * n)(*[_d(th[b]) for b in range(n)])
-    rc = nat.lib().icp_mesh_metrics_many(n, c_ctx, c_th, dice_samples, seed, _d(out), _i(status))
+    rc = nat.lib().icp_mesh_metrics_many(n, _ctx_array(ctxs), _ptr_array(list(th)), dice_samples, seed, _d(out), _i(status))
     if rc not in (0, -3) or (rc != 0 and not np.any(status != 0)):
         nat.check(rc, "icp_mesh_metrics_many")
     return {"avg": out[:, 0].copy(), "hausdorff": out[:, 1].copy(), "dice": out[:, 5].copy(),
@@ -808,15 +812,6 @@ def dice_coefficient(ctx: IcpContext, theta, samples: int = 10000, seed: int = 1
     nat.check(int(m["status"][0]), "icp_mesh_metrics_many")
     return float(m["dice"][0])
 
-
-
-def _per_item(contexts, n):
-    ctxs = list(contexts) if isinstance(contexts, (list, tuple)) else [contexts] * n
-    if n == 0 or len(ctxs) != n:
-        raise ValueError("one context per item (or one for all) and at least one item")
-    if n > 65535:
-        raise ValueError("at most 65,535 items a call")
-    return ctxs
 
 
 def transformed_meshes(contexts, thetas) -> np.ndarray:
@@ -837,10 +832,7 @@ def transformed_meshes(contexts, thetas) -> np.ndarray:
             raise ValueError(f"item {b}: theta contains a non-finite value")
     n = len(th)
     out = np.empty((n, N, 3))
-    c_ctx = (C.c_void_p * n)(*[c.h for c in ctxs])
-    c_th = (nat.c_double_p * n)(*[_d(t) for t in th])
-    c_out = (nat.c_double_p * n)(*[_d(out[b]) for b in range(n)])
-    nat.check(nat.lib().icp_model_instances_many(n, c_ctx, c_th, c_out), "icp_model_instances_many")
+    nat.check(nat.lib().icp_model_instances_many(n, _ctx_array(ctxs), _ptr_array(th), _ptr_array(list(out))), "icp_model_instances_many")
     return out
 
 
@@ -895,10 +887,9 @@ def model_coefficients(contexts, meshes=None, thetas=None, poses=None, want_proj
     coeffs = np.zeros((n, r))
     proj = np.zeros((n, N, 3)) if want_project else None
     status = np.zeros(n, dtype=np.int32)
-    c_ctx = (C.c_void_p * n)(*[c.h for c in ctxs])
-    as_p = lambda arrs: (nat.c_double_p * n)(*[_d(a) if a is not None else None for a in arrs])  # noqa: E731
-    c_proj = (nat.c_double_p * n)(*[_d(proj[b]) for b in range(n)]) if want_project else None
-    rc = nat.lib().icp_model_coefficients_many(n, c_ctx, as_p(pts), as_p(th), as_p(po), _d(coeffs), c_proj, _i(status))
+    c_proj = _ptr_array(list(proj)) if want_project else None
+    rc = nat.lib().icp_model_coefficients_many(n, _ctx_array(ctxs), _ptr_array(pts), _ptr_array(th), _ptr_array(po), _d(coeffs), c_proj,
+                                               _i(status))
     nat.check(rc, "icp_model_coefficients_many")
     return (coeffs, proj) if want_project else coeffs
 
@@ -960,13 +951,12 @@ def posterior_models(contexts, vertex_ids, points, sigma2=None, covariances=None
     shapes = {"alpha": lambda c: (c.rank,), "mean": lambda c: (c.N, 3), "basis": lambda c: (3 * c.N, c.rank),
               "variance": lambda c: (c.rank,), "point_variance": lambda c: (c.N,)}
     out = [{w: np.zeros(shapes[w](c)) for w in want} for c in ctxs]
-    as_p = lambda arrs: (nat.c_double_p * n)(*[_d(a) if a is not None else None for a in arrs])  # noqa: E731
-    outs = [as_p([o[w] for o in out]) if w in want else None for w in _POSTERIOR_WANT]
+    outs = [_ptr_array([o[w] for o in out]) if w in want else None for w in _POSTERIOR_WANT]
     status = np.zeros(n, dtype=np.int32)
     n_obs = np.array([a.shape[0] for a in ids], dtype=np.int32)
-    c_ctx = (C.c_void_p * n)(*[c.h for c in ctxs])
-    c_ids = (nat.c_int_p * n)(*[_i(a) for a in ids])
-    rc = nat.lib().icp_posterior_models_many(n, c_ctx, _i(n_obs), c_ids, as_p(p_arr), as_p(s_arr), as_p(c_arr), *outs, _i(status))
+    c_ids = _ptr_array(ids, nat.c_int_p, _i)
+    rc = nat.lib().icp_posterior_models_many(n, _ctx_array(ctxs), _i(n_obs), c_ids, _ptr_array(p_arr), _ptr_array(s_arr),
+                                             _ptr_array(c_arr), *outs, _i(status))
     if rc != 0 and not status.any():
         nat.check(rc, "icp_posterior_models_many")  # a whole-call error: nothing has run
     for b in range(n):

@@ -2,7 +2,8 @@
 //
 // Fit b is what icp_fit_deterministic gives when it is called once per recursion (n_iterations = 0, one sigma2, that recursion's
 // direction), each theta_out chained into the next theta_init — with every recursion of every fit enqueued up front on the first
-// context's stream and ONE synchronisation at the end.  Per recursion: instances (one pass over the basis per kFitInstGroup fits),
+// context's stream and ONE synchronisation at the end.  Per recursion: instances (launch_instance_many: one pass over the basis per
+// kInstGroup fits),
 // search initialisation, filter, resolve + correspondence rows, regression partial sums, factorisations (launch_posterior_factor, up
 // to posterior_factor_max() a launch), mean steps.  Every fit's work is split as the one-fit path splits it (search tasks made by the
 // same makers, regression_splits of the fit's own K), so a fit's bits do not depend on the other fits of the call or their order.
@@ -22,19 +23,9 @@ int icp_fit_deterministic_many(int32_t n_fits, icp_ctx* const* ctxs, const icp_f
     const size_t R = (size_t)n_sigma * ((size_t)n_iterations + 1);  // recursions per fit
     for (int b = 0; b < B; ++b) require(ctxs[b] && params[b] && theta_init[b] && theta_out[b], "null argument");
     icp_ctx& lead = *ctxs[0];
-    for (int b = 0; b < B; ++b) {
-      const icp_ctx& c = *ctxs[b];
-      require(c.device == lead.device && c.r == lead.r && c.N == lead.N && c.Qp.p == lead.Qp.p, "fits of one call share a device and a model");
-    }
-    // every distinct context locked, in address order (repeats are allowed: the inits of one target share its context)
-    std::vector<icp_ctx*> distinct(ctxs, ctxs + B);
-    std::sort(distinct.begin(), distinct.end(), std::less<icp_ctx*>());
-    distinct.erase(std::unique(distinct.begin(), distinct.end()), distinct.end());
+    require_one_model(B, ctxs, "fits of one call share a device and a model");
     std::vector<std::unique_lock<std::recursive_mutex>> locks;
-    for (icp_ctx* c : distinct) {
-      locks.emplace_back(c->mu);
-      if (c->batch_busy) fail(ICP_ERR_BUSY, "a context belongs to a batch in flight (icp_chain_step_batched_issue): collect or abandon it first");
-    }
+    lock_contexts(B, ctxs, locks);
     const int r = lead.r, N = lead.N;
     require(r <= 512, "ranks up to 512 (the mean step keeps alpha in LDS)");
     const size_t P = 10 + (size_t)r;
@@ -44,7 +35,7 @@ int icp_fit_deterministic_many(int32_t n_fits, icp_ctx* const* ctxs, const icp_f
     for (int b = 0; b < B; ++b) {
       const icp_fit_params& p = *params[b];
       const icp_ctx& c = *ctxs[b];
-      for (size_t i = 0; i < P; ++i) require(std::isfinite(theta_init[b][i]), "theta_init contains a non-finite value");
+      require_finite(theta_init[b], P, "theta_init contains a non-finite value");
       require(std::isfinite(p.step_length), "step_length must be finite");
       for (size_t s = 0; s < R; ++s) {
         const int d = directions ? directions[(size_t)b * R + s] : p.direction;
@@ -85,17 +76,19 @@ int icp_fit_deterministic_many(int32_t n_fits, icp_ctx* const* ctxs, const icp_f
     DBuf<int> ids, hint_m, hint_t, cnt, cands, cid, caux, fstatus, sticky;
     DBuf<uint8_t> keep, ddirs;
     DBuf<FitItem> items;
+    DBuf<InstanceItem> inst_items;
+    DBuf<InstanceGroup> inst_groups;
     {
-      std::vector<double> hc((size_t)B * r);
+      PackedCoeffs hc((size_t)B * r);
       std::vector<int> hi((size_t)B * km, 0);
       std::vector<double> ht((size_t)B * 3 * kt, 0.0);
       for (int b = 0; b < B; ++b) {
-        std::memcpy(&hc[(size_t)b * r], theta_init[b] + 10, sizeof(double) * r);
+        hc.add(theta_init[b], r);
         if (uses_m[b]) std::memcpy(&hi[(size_t)b * km], params[b]->model_ids, sizeof(int) * params[b]->n_model_ids);
         if (uses_t[b]) std::memcpy(&ht[(size_t)b * 3 * kt], params[b]->target_points, sizeof(double) * 3 * params[b]->n_target_points);
       }
       NullStreamBatch _nb;
-      coeffs.upload(hc.data(), hc.size());
+      hc.upload(coeffs);
       ids.upload(hi.data(), hi.size());
       tpts.upload(ht.data(), ht.size());
       ddirs.upload(dirs.data(), dirs.size());
@@ -115,8 +108,9 @@ int icp_fit_deterministic_many(int32_t n_fits, icp_ctx* const* ctxs, const icp_f
     Mpart.alloc((size_t)B * Smax * nn);
     M.alloc((size_t)B * r * r); alpha.alloc((size_t)B * r);
     fscratch.alloc((size_t)B * fsz);
-    // ---- the fits' records
+    // ---- the fits' records, and their instance records (the same for every recursion: the coefficient vector is the fit's in / out one)
     std::vector<FitItem> h_items(B);
+    InstancePlan inst;
     FitGrid g{kpad, kmax, 1, 1};
     search_chains_hint(B);
     for (int b = 0; b < B; ++b) {
@@ -125,8 +119,8 @@ int icp_fit_deterministic_many(int32_t n_fits, icp_ctx* const* ctxs, const icp_f
       f = FitItem{};
       f.dirs = ddirs.p + (size_t)b * R;
       f.coeffs = coeffs.p + (size_t)b * r;
-      f.pose = c.pose_of(theta_init[b]);
       f.x = x.p + (size_t)b * 3 * N;
+      inst.add(lead, f.coeffs, c.pose_of(theta_init[b]), f.x);
       f.ids = ids.p + (size_t)b * km;
       f.P = Pm.p + (size_t)b * 3 * km;
       f.tpts = tpts.p + (size_t)b * 3 * kt;
@@ -161,6 +155,7 @@ int icp_fit_deterministic_many(int32_t n_fits, icp_ctx* const* ctxs, const icp_f
     {
       NullStreamBatch _nb;
       items.upload(h_items.data(), h_items.size());
+      inst.upload(inst_items, inst_groups);
     }
     // ---- every recursion of every fit, enqueued up front
     const int fmax = posterior_factor_max();
@@ -169,7 +164,7 @@ int icp_fit_deterministic_many(int32_t n_fits, icp_ctx* const* ctxs, const icp_f
       const double wt = 1.0 / sigma2_seq[si];  // isotropic noise N(0, sigma2·I) (IcpBasedSurfaceFitting.scala:81)
       for (int it = 0; it <= n_iterations; ++it) {
         const int rec = si * (n_iterations + 1) + it;
-        launch_fit_instance(st, B, N, r, lead.Qp.p, lead.ref.p, lead.mean.p, items.p);
+        launch_instance_many(st, (int)inst.groups.size(), N, inst_groups.p, inst_items.p);
         launch_fit_searches(st, B, rec, g, N, lead.ref.p, lead.mean.p, items.p);
         launch_fit_regression(st, B, rec, g, r, lead.Q.p, wt, items.p);
         for (int b = 0; b < B; ++b) {
@@ -197,15 +192,9 @@ int icp_fit_deterministic_many(int32_t n_fits, icp_ctx* const* ctxs, const icp_f
     }
   });
   if (rc != ICP_OK) return rc;
-  int first_bad = ICP_OK;
-  for (int b = 0; b < n_fits; ++b) {
-    status[b] = fit_status[b];
-    if (fit_status[b] != ICP_OK && first_bad == ICP_OK) {
-      first_bad = fit_status[b];
-      g_err = fit_status[b] == ICP_ERR_NOT_SPD ? "regression normal equations are not positive definite" : "fitted coefficients are not finite";
-    }
-  }
-  return first_bad;
+  return report_item_status(n_fits, fit_status, status, [](int code) {
+    return code == ICP_ERR_NOT_SPD ? "regression normal equations are not positive definite" : "fitted coefficients are not finite";
+  });
 }
 
 }  // extern "C"

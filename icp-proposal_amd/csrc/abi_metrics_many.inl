@@ -46,23 +46,11 @@ int icp_mesh_metrics_many(int32_t n_items, icp_ctx* const* ctxs, const double* c
     const int B = n_items;
     for (int b = 0; b < B; ++b) require(ctxs[b] && thetas[b], "null argument");
     icp_ctx& lead = *ctxs[0];
-    for (int b = 0; b < B; ++b) {
-      const icp_ctx& c = *ctxs[b];
-      require(c.device == lead.device && c.r == lead.r && c.N == lead.N && c.Qp.p == lead.Qp.p, "items of one call share a device and a model");
-    }
+    require_one_model(B, ctxs, "items of one call share a device and a model");
     const int r = lead.r, N = lead.N, T = lead.T;
-    const size_t P = 10 + (size_t)r;
-    for (int b = 0; b < B; ++b)
-      for (size_t i = 0; i < P; ++i) require(std::isfinite(thetas[b][i]), "theta contains a non-finite value");
-    // every distinct context locked, in address order (repeats are allowed: the meshes scored against one target share its context)
-    std::vector<icp_ctx*> distinct(ctxs, ctxs + B);
-    std::sort(distinct.begin(), distinct.end(), std::less<icp_ctx*>());
-    distinct.erase(std::unique(distinct.begin(), distinct.end()), distinct.end());
+    for (int b = 0; b < B; ++b) require_finite(thetas[b], 10 + (size_t)r, "theta contains a non-finite value");
     std::vector<std::unique_lock<std::recursive_mutex>> locks;
-    for (icp_ctx* c : distinct) {
-      locks.emplace_back(c->mu);
-      if (c->batch_busy) fail(ICP_ERR_BUSY, "a context belongs to a batch in flight (icp_chain_step_batched_issue): collect or abandon it first");
-    }
+    const std::vector<icp_ctx*> distinct = lock_contexts(B, ctxs, locks);
     Bound _b(&lead);
     hipStream_t st = lead.stream;
     const int S = dice_samples;
@@ -95,10 +83,9 @@ int icp_mesh_metrics_many(int32_t n_items, icp_ctx* const* ctxs, const double* c
     DBuf<unsigned> counts;
     const size_t sf4 = sphere_floats4(T);
     {
-      std::vector<double> hc((size_t)B * r);
-      for (int b = 0; b < B; ++b) std::memcpy(&hc[(size_t)b * r], thetas[b] + 10, sizeof(double) * r);
-      NullStreamBatch _nb;
-      coeffs.upload(hc.data(), hc.size());
+      PackedCoeffs hc((size_t)B * r);
+      for (int b = 0; b < B; ++b) hc.add(thetas[b], r);
+      hc.upload(coeffs);
     }
     res.alloc((size_t)B * 12); boxes.alloc((size_t)B * 6); nonfinite.alloc(B); counts.alloc((size_t)B * 3);
     x.alloc((size_t)C * 3 * N); spheres.alloc((size_t)C * sf4);
@@ -113,20 +100,20 @@ int icp_mesh_metrics_many(int32_t n_items, icp_ctx* const* ctxs, const double* c
       for (icp_ctx* c : distinct)
         if (!c->tgt_geo_valid) { ensure_target_geometry(*c, st, tboxes); made.push_back(c); }
     // ---- records: instances, items, boxes, searches, stats, Dice ranges (slot j of a chunk = item chunk_at[i] + j)
-    std::vector<FitItem> h_fit(B);
+    InstancePlan inst;  // a chunk's instances: whole groups, inst_at[i] .. inst_at[i + 1] - 1
+    std::vector<size_t> inst_at(n_chunks + 1, 0);
     std::vector<MetItem> h_item(B);
     std::vector<MetBoxJob> h_box(B);
-    for (int b = 0; b < B; ++b) {
-      int i = 0;
-      while (chunk_at[i + 1] <= b) ++i;
-      const size_t j = (size_t)(b - chunk_at[i]);
-      FitItem& f = h_fit[b];
-      f = FitItem{};
-      f.coeffs = coeffs.p + (size_t)b * r;
-      f.pose = ctxs[b]->pose_of(thetas[b]);
-      f.x = x.p + j * 3 * N;
-      h_item[b] = MetItem{f.x, spheres.p + j * sf4, dice ? normals.p + j * 3 * N : nullptr};
-      h_box[b] = MetBoxJob{f.x, N, dice ? ctxs[b]->tgt_box.p : nullptr, boxes.p + (size_t)b * 6, nonfinite.p + b};
+    for (int i = 0; i < n_chunks; ++i) {
+      inst.boundary();
+      for (int b = chunk_at[i]; b < chunk_at[i + 1]; ++b) {
+        const size_t j = (size_t)(b - chunk_at[i]);
+        double* xb = x.p + j * 3 * N;
+        inst.add(lead, coeffs.p + (size_t)b * r, ctxs[b]->pose_of(thetas[b]), xb);
+        h_item[b] = MetItem{xb, spheres.p + j * sf4, dice ? normals.p + j * 3 * N : nullptr};
+        h_box[b] = MetBoxJob{xb, N, dice ? ctxs[b]->tgt_box.p : nullptr, boxes.p + (size_t)b * 6, nonfinite.p + b};
+      }
+      inst_at[i + 1] = inst.groups.size();
     }
     struct Round { size_t first, n; int kpad, filter, kmax; size_t cand, qslots; };
     std::vector<MetSearch> h_search;
@@ -270,7 +257,8 @@ int icp_mesh_metrics_many(int32_t n_items, icp_ctx* const* ctxs, const double* c
       search_chains_hint(1);
     }
     // (the target geometry above is complete before any record reads it: same stream; its pointers exist since ensure_target_geometry)
-    DBuf<FitItem> d_fit;
+    DBuf<InstanceItem> d_inst;
+    DBuf<InstanceGroup> d_grp;
     DBuf<MetItem> d_item;
     DBuf<MetBoxJob> d_box, d_tbox;
     DBuf<MetSearch> d_search;
@@ -278,7 +266,7 @@ int icp_mesh_metrics_many(int32_t n_items, icp_ctx* const* ctxs, const double* c
     DBuf<MetDice> d_dice;
     {
       NullStreamBatch _nb;
-      d_fit.upload(h_fit.data(), h_fit.size());
+      inst.upload(d_inst, d_grp);
       d_item.upload(h_item.data(), h_item.size());
       d_box.upload(h_box.data(), h_box.size());
       if (!tboxes.empty()) d_tbox.upload(tboxes.data(), tboxes.size());
@@ -293,7 +281,7 @@ int icp_mesh_metrics_many(int32_t n_items, icp_ctx* const* ctxs, const double* c
     for (int i = 0; i < n_chunks; ++i) {
       const ChunkPlan& cp = plan[i];
       const int b0 = chunk_at[i], nb = chunk_at[i + 1] - b0;
-      launch_fit_instance(st, nb, N, r, lead.Qp.p, lead.ref.p, lead.mean.p, d_fit.p + b0);  // ModelFittingParameters.scala:108-110
+      launch_instance_many(st, (int)(inst_at[i + 1] - inst_at[i]), N, d_grp.p + inst_at[i], d_inst.p);  // ModelFittingParameters.scala:108-110
       launch_met_items(st, nb, N, T, lead.tris.p, lead.tri_order.p, lead.adj_off.p, lead.adj.p, dice, d_item.p + b0);
       launch_met_box(st, nb, d_box.p + b0);
       run(cp.r1);
@@ -337,15 +325,7 @@ int icp_mesh_metrics_many(int32_t n_items, icp_ctx* const* ctxs, const double* c
   });
   if (rc != ICP_OK) return rc;
   std::memcpy(out, res_out.data(), sizeof(double) * res_out.size());
-  int first_bad = ICP_OK;
-  for (int b = 0; b < n_items; ++b) {
-    status[b] = item_status[b];
-    if (item_status[b] != ICP_OK && first_bad == ICP_OK) {
-      first_bad = item_status[b];
-      g_err = "an item's mesh is not finite";
-    }
-  }
-  return first_bad;
+  return report_item_status(n_items, item_status, status, [](int) { return "an item's mesh is not finite"; });
 }
 
 }  // extern "C"

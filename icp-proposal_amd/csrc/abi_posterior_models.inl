@@ -18,12 +18,6 @@ constexpr int kPmMaxRank = 256;                       // what the resident decom
 constexpr int kPmRowQuantum = 48;                     // rows of a piece: whole 16-row tiles and whole vertices
 constexpr int kPmMaxPieces = 32768;                   // pieces per round (k_pm_gemm's grid.z stays below 65,536)
 
-// (test-hooks build, ICP_TEST_POSTERIOR_MODELS_CHUNK_DOUBLES: a small chunk buffer, so that small models take several rounds)
-size_t pm_chunk_doubles() {
-  if (const char* e = dev_env("ICP_TEST_POSTERIOR_MODELS_CHUNK_DOUBLES")) return std::max<size_t>(1, (size_t)std::atoll(e));
-  return kPmChunkDoubles;
-}
-
 // Σ⁻¹ of a symmetric 3 × 3 covariance (its symmetric part) in closed form; false: not positive definite
 bool pm_precision(const double* c, double* w) {
   const double a = c[0], b = 0.5 * (c[1] + c[3]), d = 0.5 * (c[2] + c[6]), e = c[4], f = 0.5 * (c[5] + c[7]), g = c[8];
@@ -49,10 +43,8 @@ int icp_posterior_models_many(int32_t n_items, icp_ctx* const* ctxs, const int32
     require(n_items >= 1 && n_items <= 65535, "n_items must lie in [1, 65535]");
     require(ctxs && n_obs && vertex_ids && points && status, "null argument");
     const int B = n_items;
-    for (int b = 0; b < B; ++b) {
-      require(ctxs[b] && vertex_ids[b] && points[b], "null argument");
-      require(ctxs[b]->device == ctxs[0]->device, "items of one call share a device");
-    }
+    for (int b = 0; b < B; ++b) require(ctxs[b] && vertex_ids[b] && points[b], "null argument");
+    require_one_device(B, ctxs, "items of one call share a device");
     // ---- validation: nothing runs and nothing is written unless every item's arguments are good.  The precisions are made here.
     std::vector<size_t> off(B + 1, 0);
     for (int b = 0; b < B; ++b) {
@@ -67,7 +59,7 @@ int icp_posterior_models_many(int32_t n_items, icp_ctx* const* ctxs, const int32
       const bool iso = sigma2 && sigma2[b], full = covariances && covariances[b];
       require(iso != full, "an item's noise is given as sigma2 or as covariances, one of the two");
       for (int k = 0; k < K; ++k) require(vertex_ids[b][k] >= 0 && vertex_ids[b][k] < c.N, "vertex id out of range");
-      for (size_t i = 0; i < 3 * (size_t)K; ++i) require(std::isfinite(points[b][i]), "points contain a non-finite value");
+      require_finite(points[b], 3 * (size_t)K, "points contain a non-finite value");
       double* w = &h_w[6 * off[b]];
       if (iso) {
         const double s2 = sigma2[b][0];
@@ -75,14 +67,14 @@ int icp_posterior_models_many(int32_t n_items, icp_ctx* const* ctxs, const int32
         const double wi = 1.0 / s2;
         for (int k = 0; k < K; ++k) { double* wk = w + 6 * (size_t)k; wk[0] = wk[3] = wk[5] = wi; wk[1] = wk[2] = wk[4] = 0.0; }
       } else {
-        for (size_t i = 0; i < 9 * (size_t)K; ++i) require(std::isfinite(covariances[b][i]), "covariances contain a non-finite value");
+        require_finite(covariances[b], 9 * (size_t)K, "covariances contain a non-finite value");
         for (int k = 0; k < K; ++k)
           if (!pm_precision(covariances[b] + 9 * (size_t)k, w + 6 * (size_t)k)) { bad[b] = 2; break; }
       }
       if (c.r > kPmMaxRank) bad[b] = 1;
     }
     std::vector<std::unique_lock<std::recursive_mutex>> locks;
-    proj_lock(B, ctxs, locks);
+    lock_contexts(B, ctxs, locks);
     icp_ctx& lead = *ctxs[0];
     Bound _b(&lead);
     hipStream_t st = lead.stream;
@@ -118,7 +110,7 @@ int icp_posterior_models_many(int32_t n_items, icp_ctx* const* ctxs, const int32
     size_t work_max = 1;
     for (int b : live) work_max = std::max(work_max, eigen_work_doubles(ctxs[b]->r));
     const size_t fsz = (size_t)(rmax + 1) * rmax + 8;
-    size_t cap = pm_chunk_doubles();
+    size_t cap = test_chunk_doubles("ICP_TEST_POSTERIOR_MODELS_CHUNK_DOUBLES", kPmChunkDoubles);
     for (int b : live) cap = std::max(cap, (size_t)kPmRowQuantum * ((size_t)ctxs[b]->r + 2));  // (a piece always fits)
     DBuf<int> d_ids, d_status;
     DBuf<double> d_pts, d_w, d_alpha, d_S, Mpart, M, V, Vt, Bm, fscratch, work, chunk;
@@ -220,7 +212,7 @@ int icp_posterior_models_many(int32_t n_items, icp_ctx* const* ctxs, const int32
       flush();
     };
     auto issue_rounds = [&](const std::vector<Round>& rounds, size_t r0, size_t r1, const PmPiece* table) {
-      ProjCopies cp;
+      HostCopies cp;
       for (size_t i = r0; i < r1; ++i) {
         const Round& rd = rounds[i];
         launch_pm_gemm(st, (int)(rd.p1 - rd.p0), rd.rows_max, rd.tiles_max, table + rd.p0);
@@ -330,16 +322,10 @@ int icp_posterior_models_many(int32_t n_items, icp_ctx* const* ctxs, const int32
       if (item_status[b] == ICP_ERR_NOT_FINITE) fill_nan(b);
   });
   if (rc != ICP_OK) return rc;
-  int first_bad = ICP_OK;
-  for (int b = 0; b < n_items; ++b) {
-    status[b] = item_status[b];
-    if (item_status[b] != ICP_OK && first_bad == ICP_OK) {
-      first_bad = item_status[b];
-      g_err = item_status[b] == ICP_ERR_INVALID_ARG ? "an item's rank is above 256: no resident decomposition serves it"
-                                                    : "an item's covariance is not positive definite, or its M did not factor";
-    }
-  }
-  return first_bad;
+  return report_item_status(n_items, item_status, status, [](int code) {
+    return code == ICP_ERR_INVALID_ARG ? "an item's rank is above 256: no resident decomposition serves it"
+                                       : "an item's covariance is not positive definite, or its M did not factor";
+  });
 }
 
 }  // extern "C"

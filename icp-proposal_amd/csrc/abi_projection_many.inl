@@ -1,5 +1,5 @@
 // abi_projection_many.inl — C ABI: icp_model_instances_many and icp_model_coefficients_many, the model's instances, coefficients
-// and projections of many meshes (kernels_projection.hip; k_var_instance of kernels_variability.hip).
+// and projections of many meshes (kernels_projection.hip, launch_instance_many).
 //
 // Instances: points_out[b] is, bit for bit, icp_transformed_mesh(ctxs[b], thetas[b], ·).  Coefficients: item b's mesh — its uploaded
 // vertices, or the instance of its state — has the given pose taken off, and c = P·Qᵀ(x − x̄ − μ) with the model's resident
@@ -13,40 +13,6 @@ namespace {
 constexpr size_t kProjChunkDoubles = (size_t)4 << 20;  // the chunk buffer: 32 MiB of meshes
 constexpr int kProjMaxChunkItems = 32752;              // meshes per chunk (a multiple of 16; k_proj_residual's grid.y = items stays below 65,536)
 
-// (test-hooks build, ICP_TEST_PROJECTION_CHUNK_DOUBLES: a small chunk buffer, so that small meshes take the paths of large ones)
-size_t proj_chunk_doubles() {
-  if (const char* e = dev_env("ICP_TEST_PROJECTION_CHUNK_DOUBLES")) return std::max<size_t>(1, (size_t)std::atoll(e));
-  return kProjChunkDoubles;
-}
-
-// every distinct context of a batched call locked, in address order (repeats are allowed)
-void proj_lock(int B, icp_ctx* const* ctxs, std::vector<std::unique_lock<std::recursive_mutex>>& locks) {
-  std::vector<icp_ctx*> distinct(ctxs, ctxs + B);
-  std::sort(distinct.begin(), distinct.end(), std::less<icp_ctx*>());
-  distinct.erase(std::unique(distinct.begin(), distinct.end()), distinct.end());
-  for (icp_ctx* c : distinct) {
-    locks.emplace_back(c->mu);
-    if (c->batch_busy) fail(ICP_ERR_BUSY, "a context belongs to a batch in flight (icp_chain_step_batched_issue): collect or abandon it first");
-  }
-}
-
-// copies between the chunk buffer and the caller's arrays: neighbours on both sides (the rows of one array) go as ONE copy
-struct ProjCopies {
-  struct Run { double* dev; double* host; size_t n; };
-  std::vector<Run> runs;
-  void add(double* dev, const double* host, size_t n) {
-    if (!runs.empty() && runs.back().dev + runs.back().n == dev && runs.back().host + runs.back().n == host) runs.back().n += n;
-    else runs.push_back(Run{dev, const_cast<double*>(host), n});
-  }
-  void issue(hipStream_t st, bool to_device) {
-    for (const Run& c : runs) {
-      if (to_device) HIP_OK(hipMemcpyAsync(c.dev, c.host, sizeof(double) * c.n, hipMemcpyHostToDevice, st));
-      else HIP_OK(hipMemcpyAsync(c.host, c.dev, sizeof(double) * c.n, hipMemcpyDeviceToHost, st));
-    }
-    runs.clear();
-  }
-};
-
 const double kProjIdentityPose[10] = {1.0, 0.0, 0.0, 0.0, 0.0, 0.0, 0.0, 0.0, 0.0, 0.0};
 }  // namespace
 
@@ -57,23 +23,20 @@ int icp_model_instances_many(int32_t n_items, icp_ctx* const* ctxs, const double
     require(n_items >= 1 && n_items <= 65535, "n_items must lie in [1, 65535]");
     require(ctxs && thetas && points_out, "null argument");
     const int B = n_items;
-    for (int b = 0; b < B; ++b) {
-      require(ctxs[b] && thetas[b] && points_out[b], "null argument");
-      require(ctxs[b]->device == ctxs[0]->device, "items of one call share a device");
-    }
+    for (int b = 0; b < B; ++b) require(ctxs[b] && thetas[b] && points_out[b], "null argument");
+    require_one_device(B, ctxs, "items of one call share a device");
     size_t n_coeffs = 0;
     for (int b = 0; b < B; ++b) {
-      const size_t P = 10 + (size_t)ctxs[b]->r;
-      for (size_t i = 0; i < P; ++i) require(std::isfinite(thetas[b][i]), "theta contains a non-finite value");
+      require_finite(thetas[b], 10 + (size_t)ctxs[b]->r, "theta contains a non-finite value");
       n_coeffs += (size_t)ctxs[b]->r;
     }
     std::vector<std::unique_lock<std::recursive_mutex>> locks;
-    proj_lock(B, ctxs, locks);
+    lock_contexts(B, ctxs, locks);
     icp_ctx& lead = *ctxs[0];
     Bound _b(&lead);
     hipStream_t st = lead.stream;
 
-    size_t cap = proj_chunk_doubles();
+    size_t cap = test_chunk_doubles("ICP_TEST_PROJECTION_CHUNK_DOUBLES", kProjChunkDoubles);
     int Nmax = 1;
     for (int b = 0; b < B; ++b) {
       Nmax = std::max(Nmax, ctxs[b]->N);
@@ -84,16 +47,15 @@ int icp_model_instances_many(int32_t n_items, icp_ctx* const* ctxs, const double
     DBuf<double> chunk, coeffs;
     chunk.alloc(std::min(cap, total));
     {
-      std::vector<double> hc(n_coeffs);
-      size_t o = 0;
-      for (int b = 0; b < B; ++b) { std::memcpy(&hc[o], thetas[b] + 10, sizeof(double) * ctxs[b]->r); o += (size_t)ctxs[b]->r; }
-      NullStreamBatch _nb;
-      coeffs.upload(hc.data(), hc.size());
+      PackedCoeffs hc(n_coeffs);
+      for (int b = 0; b < B; ++b) hc.add(thetas[b], ctxs[b]->r);
+      hc.upload(coeffs);
     }
-    // ---- the plan: a record per mesh, groups of up to kVarInstGroup consecutive meshes of one model, rounds = ranges of groups
+    // ---- the plan: a record per mesh, groups of up to kInstGroup consecutive meshes of one model, rounds = ranges of groups
     struct Round { size_t g0, g1; int b0, b1; };
-    std::vector<VarSample> h_smp(B);
-    std::vector<VarGroup> h_grp;
+    InstancePlan inst;
+    const std::vector<InstanceItem>& h_smp = inst.items;
+    const std::vector<InstanceGroup>& h_grp = inst.groups;
     std::vector<Round> rounds;
     {
       size_t used = 0, co = 0;
@@ -106,27 +68,20 @@ int icp_model_instances_many(int32_t n_items, icp_ctx* const* ctxs, const double
           rounds.back().g1 = h_grp.size(); rounds.back().b1 = b;
           rounds.push_back(Round{h_grp.size(), 0, b, 0});
           used = 0; held = 0;
+          inst.boundary();
         }
-        const bool open = h_grp.size() > rounds.back().g0 && h_grp.back().Qp == c.Qp.p && h_grp.back().N == c.N && h_grp.back().r == c.r &&
-                          h_grp.back().n < kVarInstGroup;
-        if (open) ++h_grp.back().n;
-        else h_grp.push_back(VarGroup{c.Qp.p, c.ref.p, c.mean.p, c.N, c.r, b, 1});
-        h_smp[b] = VarSample{coeffs.p + co, c.pose_of(thetas[b]), chunk.p + used};
+        inst.add(c, coeffs.p + co, c.pose_of(thetas[b]), chunk.p + used);
         co += (size_t)c.r; used += n3; ++held;
       }
       rounds.back().g1 = h_grp.size(); rounds.back().b1 = B;
     }
-    DBuf<VarSample> d_smp;
-    DBuf<VarGroup> d_grp;
-    {
-      NullStreamBatch _nb;
-      d_smp.upload(h_smp.data(), h_smp.size());
-      d_grp.upload(h_grp.data(), h_grp.size());
-    }
+    DBuf<InstanceItem> d_smp;
+    DBuf<InstanceGroup> d_grp;
+    inst.upload(d_smp, d_grp);
     // ---- launches: one per round, and the round's meshes back to the caller
-    ProjCopies back;
+    HostCopies back;
     for (const Round& rd : rounds) {
-      launch_var_instance(st, (int)(rd.g1 - rd.g0), Nmax, d_grp.p + rd.g0, d_smp.p);  // ModelFittingParameters.scala:108-110
+      launch_instance_many(st, (int)(rd.g1 - rd.g0), Nmax, d_grp.p + rd.g0, d_smp.p);  // ModelFittingParameters.scala:108-110
       for (int b = rd.b0; b < rd.b1; ++b) back.add(h_smp[b].x, points_out[b], 3 * (size_t)ctxs[b]->N);
       back.issue(st, false);
     }
@@ -143,10 +98,7 @@ int icp_model_coefficients_many(int32_t n_items, icp_ctx* const* ctxs, const dou
     const int B = n_items;
     for (int b = 0; b < B; ++b) require(ctxs[b] != nullptr, "null argument");
     icp_ctx& lead = *ctxs[0];
-    for (int b = 0; b < B; ++b) {
-      const icp_ctx& c = *ctxs[b];
-      require(c.device == lead.device && c.r == lead.r && c.N == lead.N && c.Qp.p == lead.Qp.p, "items of one call share a device and a model");
-    }
+    require_one_model(B, ctxs, "items of one call share a device and a model");
     const int r = lead.r, N = lead.N;
     const size_t n3 = 3 * (size_t)N, P = 10 + (size_t)r;
     int n_theta = 0;
@@ -154,21 +106,22 @@ int icp_model_coefficients_many(int32_t n_items, icp_ctx* const* ctxs, const dou
       const bool has_pts = points && points[b], has_th = thetas && thetas[b];
       require(has_pts != has_th, "an item is given as points or as a theta, one of the two");
       if (has_th) {
-        for (size_t i = 0; i < P; ++i) require(std::isfinite(thetas[b][i]), "theta contains a non-finite value");
+        require_finite(thetas[b], P, "theta contains a non-finite value");
         ++n_theta;
       }
       if (poses && poses[b]) {
-        for (int i = 0; i < 10; ++i) require(std::isfinite(poses[b][i]), "pose contains a non-finite value");
+        require_finite(poses[b], 10, "pose contains a non-finite value");
         require(poses[b][0] == 1.0, "the scale of a pose to take off must be exactly 1");
       }
     }
     std::vector<std::unique_lock<std::recursive_mutex>> locks;
-    proj_lock(B, ctxs, locks);
+    lock_contexts(B, ctxs, locks);
     Bound _b(&lead);
     hipStream_t st = lead.stream;
 
     // ---- buffers: [meshes of a chunk | their residuals, 16 items side by side], the slabs' partial sums, the call's coefficient rows
-    const int per_chunk = (int)std::min<size_t>({(size_t)B, std::max<size_t>(1, proj_chunk_doubles() / n3), (size_t)kProjMaxChunkItems});
+    const size_t cap = test_chunk_doubles("ICP_TEST_PROJECTION_CHUNK_DOUBLES", kProjChunkDoubles);
+    const int per_chunk = (int)std::min<size_t>({(size_t)B, std::max<size_t>(1, cap / n3), (size_t)kProjMaxChunkItems});
     const int groups = (per_chunk + kProjGroup - 1) / kProjGroup, rpad = (r + 15) / 16 * 16;
     DBuf<double> xbuf, dbuf, part, coeffs, tcoeffs;
     DBuf<int> nonfinite;
@@ -177,66 +130,61 @@ int icp_model_coefficients_many(int32_t n_items, icp_ctx* const* ctxs, const dou
     part.alloc((size_t)groups * proj_slabs(N) * rpad * kProjGroup);
     coeffs.alloc((size_t)B * r);
     nonfinite.alloc(B);
-    {
-      std::vector<double> hc((size_t)n_theta * r);
-      size_t o = 0;
+    if (n_theta > 0) {
+      PackedCoeffs hc((size_t)n_theta * r);
       for (int b = 0; b < B; ++b)
-        if (thetas && thetas[b]) { std::memcpy(&hc[o], thetas[b] + 10, sizeof(double) * r); o += r; }
-      NullStreamBatch _nb;
-      if (n_theta > 0) tcoeffs.upload(hc.data(), hc.size());
+        if (thetas && thetas[b]) hc.add(thetas[b], r);
+      hc.upload(tcoeffs);
     }
     // ---- records: a ProjItem per mesh; instance records of the states' meshes (first) and of the projections (second), in groups
     std::vector<ProjItem> h_item(B);
-    std::vector<VarSample> h_smp;
-    std::vector<VarGroup> h_grp;
+    InstancePlan inst;
+    const std::vector<InstanceGroup>& h_grp = inst.groups;
     struct Chunk { int b0, b1; size_t tg0, tg1, pg0, pg1; };  // items; groups of the states' instances / of the projections
     std::vector<Chunk> chunks;
-    auto add_instance = [&](size_t g0, icp_ctx& c, const double* cf, const Pose& pose, double* x) {
-      if (h_grp.size() > g0 && h_grp.back().n < kVarInstGroup) ++h_grp.back().n;
-      else h_grp.push_back(VarGroup{c.Qp.p, c.ref.p, c.mean.p, N, r, (int)h_smp.size(), 1});
-      h_smp.push_back(VarSample{cf, pose, x});
-    };
     {
       size_t to = 0;
       for (int b0 = 0; b0 < B; b0 += per_chunk) {
         Chunk ch{b0, std::min(B, b0 + per_chunk), h_grp.size(), 0, 0, 0};
+        inst.boundary();
         for (int b = ch.b0; b < ch.b1; ++b) {
           double* x = xbuf.p + (size_t)(b - b0) * n3;
           ProjItem& it = h_item[b];
           it.x = x;
           it.has_pose = poses && poses[b] ? 1 : 0;
           it.pose = ctxs[b]->pose_of(it.has_pose ? poses[b] : kProjIdentityPose);
-          if (thetas && thetas[b]) { add_instance(ch.tg0, *ctxs[b], tcoeffs.p + to, ctxs[b]->pose_of(thetas[b]), x); to += r; }
+          if (thetas && thetas[b]) { inst.add(*ctxs[b], tcoeffs.p + to, ctxs[b]->pose_of(thetas[b]), x); to += r; }
         }
         ch.tg1 = ch.pg0 = h_grp.size();
+        inst.boundary();
         for (int b = ch.b0; b < ch.b1; ++b)
-          if (project_out && project_out[b]) add_instance(ch.pg0, *ctxs[b], coeffs.p + (size_t)b * r, h_item[b].pose, const_cast<double*>(h_item[b].x));
+          if (project_out && project_out[b]) inst.add(*ctxs[b], coeffs.p + (size_t)b * r, h_item[b].pose, const_cast<double*>(h_item[b].x));
         ch.pg1 = h_grp.size();
         chunks.push_back(ch);
       }
     }
     DBuf<ProjItem> d_item;
-    DBuf<VarSample> d_smp;
-    DBuf<VarGroup> d_grp;
+    DBuf<InstanceItem> d_smp;
+    DBuf<InstanceGroup> d_grp;
     {
       NullStreamBatch _nb;
       d_item.upload(h_item.data(), h_item.size());
-      if (!h_smp.empty()) { d_smp.upload(h_smp.data(), h_smp.size()); d_grp.upload(h_grp.data(), h_grp.size()); }
+      if (!inst.items.empty()) inst.upload(d_smp, d_grp);
     }
     // ---- launches
     HIP_OK(hipMemsetAsync(nonfinite.p, 0, sizeof(int) * (size_t)B, st));
-    ProjCopies up, back;
+    HostCopies up, back;
     for (const Chunk& ch : chunks) {
       const int n = ch.b1 - ch.b0;
       for (int b = ch.b0; b < ch.b1; ++b)
         if (points && points[b]) up.add(const_cast<double*>(h_item[b].x), points[b], n3);
       up.issue(st, true);
-      launch_var_instance(st, (int)(ch.tg1 - ch.tg0), N, d_grp.p + ch.tg0, d_smp.p);
+      launch_instance_many(st, (int)(ch.tg1 - ch.tg0), N, d_grp.p + ch.tg0, d_smp.p);
       launch_proj_residual(st, n, N, lead.ref.p, lead.mean.p, d_item.p + ch.b0, dbuf.p, nonfinite.p + ch.b0);
       launch_proj_gemm(st, n, N, r, lead.Q.p, dbuf.p, part.p);
       launch_proj_solve(st, n, N, r, part.p, lead.P.p, coeffs.p + (size_t)ch.b0 * r);
       if (ch.pg1 > ch.pg0) {
-        launch_var_instance(st, (int)(ch.pg1 - ch.pg0), N, d_grp.p + ch.pg0, d_smp.p);
+        launch_instance_many(st, (int)(ch.pg1 - ch.pg0), N, d_grp.p + ch.pg0, d_smp.p);
         for (int b = ch.b0; b < ch.b1; ++b)
           if (project_out && project_out[b]) back.add(const_cast<double*>(h_item[b].x), project_out[b], n3);
         back.issue(st, false);
@@ -257,15 +205,7 @@ int icp_model_coefficients_many(int32_t n_items, icp_ctx* const* ctxs, const dou
     std::memcpy(coeffs_out, hc.data(), sizeof(double) * hc.size());
   });
   if (rc != ICP_OK) return rc;
-  int first_bad = ICP_OK;
-  for (int b = 0; b < n_items; ++b) {
-    status[b] = item_status[b];
-    if (item_status[b] != ICP_OK && first_bad == ICP_OK) {
-      first_bad = item_status[b];
-      g_err = "an item's mesh is not finite";
-    }
-  }
-  return first_bad;
+  return report_item_status(n_items, item_status, status, [](int) { return "an item's mesh is not finite"; });
 }
 
 }  // extern "C"

@@ -1,5 +1,5 @@
 // abi_variability_many.inl — C ABI: icp_posterior_variability_many, the posterior variability maps of many chains' samples
-// (kernels_variability.hip; apps/util/PosteriorVariability.scala:30-73).
+// (kernels_variability.hip, launch_instance_many; apps/util/PosteriorVariability.scala:30-73).
 //
 // Map m's out is, bit for bit, what icp_posterior_variability(ctxs[m], n_samples[m], thetas[m], modes[m], theta_refs[m], ·) gives.
 // The sample meshes pass through ONE chunk buffer of kVarChunkDoubles doubles, round by round: a round holds the samples of as many
@@ -13,12 +13,6 @@
 namespace {
 constexpr size_t kVarChunkDoubles = (size_t)8 << 20;  // the chunk buffer: 64 MiB of sample meshes (and mode-2 sample normals)
 constexpr int kVarMaxRoundSamples = 32768;            // meshes per round (every launch's grid.y stays below 65,536)
-
-// (test-hooks build, ICP_TEST_VARIABILITY_CHUNK_DOUBLES: a small chunk buffer, so that small meshes take the paths of large ones)
-size_t var_chunk_doubles() {
-  if (const char* e = dev_env("ICP_TEST_VARIABILITY_CHUNK_DOUBLES")) return std::max<size_t>(1, (size_t)std::atoll(e));
-  return kVarChunkDoubles;
-}
 }  // namespace
 
 extern "C" {
@@ -36,28 +30,19 @@ int icp_posterior_variability_many(int32_t n_maps, icp_ctx* const* ctxs, const i
       require(n_samples[m] >= 2, "at least two samples are needed");
       require(modes[m] >= 0 && modes[m] <= 2, "unknown mode");
       require(modes[m] != 1 || (theta_refs && theta_refs[m]), "theta_ref is null");
-      require(ctxs[m]->device == ctxs[0]->device, "maps of one call share a device");
     }
+    require_one_device(B, ctxs, "maps of one call share a device");
     size_t n_inst = 0, n_coeffs = 0;  // meshes to instance (samples and mode-1 references) and their coefficients
     for (int m = 0; m < B; ++m) {
       const size_t P = 10 + (size_t)ctxs[m]->r;
-      const size_t n = (size_t)n_samples[m] * P;
-      for (size_t i = 0; i < n; ++i) require(std::isfinite(thetas[m][i]), "theta contains a non-finite value");
-      if (modes[m] == 1)
-        for (size_t i = 0; i < P; ++i) require(std::isfinite(theta_refs[m][i]), "theta contains a non-finite value");
+      require_finite(thetas[m], (size_t)n_samples[m] * P, "theta contains a non-finite value");
+      if (modes[m] == 1) require_finite(theta_refs[m], P, "theta contains a non-finite value");
       const size_t k = (size_t)n_samples[m] + (modes[m] == 1 ? 1 : 0);
       n_inst += k;
       n_coeffs += k * (size_t)ctxs[m]->r;
     }
-    // every distinct context locked, in address order (repeats are allowed: the chains of one target share its context)
-    std::vector<icp_ctx*> distinct(ctxs, ctxs + B);
-    std::sort(distinct.begin(), distinct.end(), std::less<icp_ctx*>());
-    distinct.erase(std::unique(distinct.begin(), distinct.end()), distinct.end());
     std::vector<std::unique_lock<std::recursive_mutex>> locks;
-    for (icp_ctx* c : distinct) {
-      locks.emplace_back(c->mu);
-      if (c->batch_busy) fail(ICP_ERR_BUSY, "a context belongs to a batch in flight (icp_chain_step_batched_issue): collect or abandon it first");
-    }
+    lock_contexts(B, ctxs, locks);
     icp_ctx& lead = *ctxs[0];
     Bound _b(&lead);
     hipStream_t st = lead.stream;
@@ -65,7 +50,7 @@ int icp_posterior_variability_many(int32_t n_maps, icp_ctx* const* ctxs, const i
     // ---- the maps' own buffers: [res of every map | mean of every map | nrm, acc per map]
     struct MapBuf { size_t res, mean, nrm, acc; };
     std::vector<MapBuf> mb(B);
-    size_t sumN = 0, cap = var_chunk_doubles();
+    size_t sumN = 0, cap = test_chunk_doubles("ICP_TEST_VARIABILITY_CHUNK_DOUBLES", kVarChunkDoubles);
     int Nmax = 1;
     for (int m = 0; m < B; ++m) sumN += (size_t)ctxs[m]->N;
     {
@@ -82,36 +67,31 @@ int icp_posterior_variability_many(int32_t n_maps, icp_ctx* const* ctxs, const i
     state.alloc(10 * sumN);
     chunk.alloc(cap);
     {
-      std::vector<double> hc(n_coeffs);
-      size_t o = 0;
+      PackedCoeffs hc(n_coeffs);  // per map: its mode-1 reference, then its samples
       for (int m = 0; m < B; ++m) {
-        const size_t r = (size_t)ctxs[m]->r, P = 10 + r;
-        if (modes[m] == 1) { std::memcpy(&hc[o], theta_refs[m] + 10, sizeof(double) * r); o += r; }
-        for (int s = 0; s < n_samples[m]; ++s, o += r) std::memcpy(&hc[o], thetas[m] + (size_t)s * P + 10, sizeof(double) * r);
+        const int r = ctxs[m]->r;
+        if (modes[m] == 1) hc.add(theta_refs[m], r);
+        for (int s = 0; s < n_samples[m]; ++s) hc.add(thetas[m] + (size_t)s * (10 + (size_t)r), r);
       }
-      NullStreamBatch _nb;
-      coeffs.upload(hc.data(), hc.size());
+      hc.upload(coeffs);
     }
 
     // ---- the plan: records of every mesh, group, normal job and segment; rounds = ranges of them
     struct Round { size_t g0, g1, j0, j1, s0, s1, c0, c1; };  // groups, normal jobs, sum segments, centred segments
-    std::vector<VarSample> h_smp;
-    std::vector<VarGroup> h_grp;
+    InstancePlan inst;
+    const std::vector<InstanceGroup>& h_grp = inst.groups;
     std::vector<VarNormalJob> h_job;
     std::vector<VarSeg> h_sum, h_cen;
     std::vector<Round> rounds;
-    h_smp.reserve(n_inst);
+    inst.items.reserve(n_inst);
     size_t used = 0, co = 0;  // the open round: doubles of the chunk buffer taken, coefficient cursor
     int held = 0;             // … and meshes
     auto open_round = [&] { rounds.push_back(Round{h_grp.size(), h_grp.size(), h_job.size(), h_job.size(), h_sum.size(), h_sum.size(), h_cen.size(), h_cen.size()}); used = 0; held = 0; };
     auto close_round = [&] { Round& rd = rounds.back(); rd.g1 = h_grp.size(); rd.j1 = h_job.size(); rd.s1 = h_sum.size(); rd.c1 = h_cen.size(); };
-    auto add_meshes = [&](icp_ctx& c, const double* th, const double* cf, int n, double* x) {  // n consecutive thetas -> x[n][3N], grouped
+    auto add_meshes = [&](icp_ctx& c, const double* th, const double* cf, int n, double* x) {  // n consecutive thetas -> x[n][3N], in groups of their own
       const size_t P = 10 + (size_t)c.r, n3 = 3 * (size_t)c.N;
-      for (int s = 0; s < n; ++s) {
-        if (s % kVarInstGroup == 0)
-          h_grp.push_back(VarGroup{c.Qp.p, c.ref.p, c.mean.p, c.N, c.r, (int)h_smp.size(), std::min(kVarInstGroup, n - s)});
-        h_smp.push_back(VarSample{cf + (size_t)s * c.r, c.pose_of(th + (size_t)s * P), x + (size_t)s * n3});
-      }
+      inst.boundary();
+      for (int s = 0; s < n; ++s) inst.add(c, cf + (size_t)s * c.r, c.pose_of(th + (size_t)s * P), x + (size_t)s * n3);
     };
     open_round();
     for (int m = 0; m < B; ++m) {
@@ -160,21 +140,20 @@ int icp_posterior_variability_many(int32_t n_maps, icp_ctx* const* ctxs, const i
     }
     close_round();
 
-    DBuf<VarSample> d_smp;
-    DBuf<VarGroup> d_grp;
+    DBuf<InstanceItem> d_smp;
+    DBuf<InstanceGroup> d_grp;
     DBuf<VarNormalJob> d_job;
     DBuf<VarSeg> d_sum, d_cen;
     {
       NullStreamBatch _nb;
-      d_smp.upload(h_smp.data(), h_smp.size());
-      d_grp.upload(h_grp.data(), h_grp.size());
+      inst.upload(d_smp, d_grp);
       if (!h_job.empty()) d_job.upload(h_job.data(), h_job.size());
       d_sum.upload(h_sum.data(), h_sum.size());
       d_cen.upload(h_cen.data(), h_cen.size());
     }
     // ---- launches
     for (const Round& rd : rounds) {
-      launch_var_instance(st, (int)(rd.g1 - rd.g0), Nmax, d_grp.p + rd.g0, d_smp.p);
+      launch_instance_many(st, (int)(rd.g1 - rd.g0), Nmax, d_grp.p + rd.g0, d_smp.p);
       launch_var_normals(st, (int)(rd.j1 - rd.j0), Nmax, d_job.p + rd.j0);
       launch_var_sum(st, (int)(rd.s1 - rd.s0), Nmax, d_sum.p + rd.s0);
       launch_var_centred(st, (int)(rd.c1 - rd.c0), Nmax, d_cen.p + rd.c0);

@@ -59,6 +59,19 @@ void launch_instance(hipStream_t st, int N, int r, const double* Qp, const doubl
 void launch_instance_keep(hipStream_t st, int N, int r, const double* Qp, const double* ref, const double* mean,
                           const Pose& pose, const double* coeffs, double* x, double* defo);
 void launch_instance_pose(hipStream_t st, int N, const double* ref, const Pose& pose, const double* defo_in, double* x, double* defo_out);
+// K1 of many items in one launch (the batched entry points): every item's points are the bits of its own launch_instance
+constexpr int kInstGroup = 8;  // items whose instances one pass over the basis forms
+struct InstanceItem {   // one mesh to instance (device)
+  const double* coeffs; // [r] shape coefficients
+  Pose pose;
+  double* x;            // [N*3] the instance
+};
+struct InstanceGroup {  // up to kInstGroup consecutive items of one model: one pass over that model's basis
+  const double* Qp; const double* ref; const double* mean;
+  int N, r;
+  int first, n;         // items[first .. first+n-1]
+};
+void launch_instance_many(hipStream_t st, int n_groups, int Nmax, const InstanceGroup* groups, const InstanceItem* items);
 
 // K2: all vertex normals (diagnostic entry point; the posterior kernels compute normals on demand)
 void launch_vertex_normals(hipStream_t st, int N, const double* x, const int* tris, const int* adj_off,
@@ -661,12 +674,10 @@ VertexTask make_vertex_task(int V, const double* verts, int K, const double* P, 
 int query_batch(int K, int n_elems, size_t cand_capacity);
 
 // ---- many deterministic ICP fits in lockstep (kernels_fit.hip; icp_fit_deterministic_many)
-constexpr int kFitInstGroup = 8;  // fits whose instances one pass over the basis forms
 struct FitItem {  // one fit's record in device memory, the same for every recursion of the call
   const uint8_t* dirs;  // [n_recursions] ICP_MODEL_SAMPLING (0) / ICP_TARGET_SAMPLING (1): the fit's schedule
-  double* coeffs;       // [r] shape coefficients (in / out)
-  Pose pose;
-  double* x;            // [N*3] instance
+  double* coeffs;       // [r] shape coefficients (in / out; the fit's InstanceItem reads them)
+  double* x;            // [N*3] instance (made by launch_instance_many)
   const int* ids;       // model side: sample ids (surf.K of them)
   double* P;            // model side: their points on the instance
   const double* tpts;   // target side: target samples (vert.K of them)
@@ -683,7 +694,6 @@ struct FitItem {  // one fit's record in device memory, the same for every recur
 };
 int query_kpad(int K);  // K rounded up as the search tasks round it (SurfaceTask / VertexTask::Kpad)
 struct FitGrid { int kpad, kmax, filter, splits; };  // the launches' grid extents over every fit of a recursion
-void launch_fit_instance(hipStream_t st, int B, int N, int r, const double* Qp, const double* ref, const double* mean, const FitItem* items);
 void launch_fit_searches(hipStream_t st, int B, int rec, const FitGrid& g, int N, const double* ref, const double* mean, const FitItem* items);
 void launch_fit_regression(hipStream_t st, int B, int rec, const FitGrid& g, int r, const double* Q, double wt, const FitItem* items);
 void launch_fit_mean_step(hipStream_t st, int B, int r, const double* P, double sigma2, const FitItem* items);
@@ -737,17 +747,6 @@ void launch_met_samples(hipStream_t st, int n, int nmax, uint64_t seed, const Me
 void launch_met_dice_count(hipStream_t st, int n, int nmax, const MetDice* jobs);
 
 // ---- posterior variability maps of many chains (kernels_variability.hip; icp_posterior_variability_many)
-constexpr int kVarInstGroup = 8;  // samples whose meshes one pass over the basis forms
-struct VarSample {      // one sample mesh to instance (device)
-  const double* coeffs; // [r] shape coefficients
-  Pose pose;
-  double* x;            // [N*3] its slot in the chunk buffer
-};
-struct VarGroup {       // up to kVarInstGroup consecutive samples of one map: one pass over that model's basis
-  const double* Qp; const double* ref; const double* mean;
-  int N, r;
-  int first, n;         // samples[first .. first+n-1]
-};
 struct VarNormalJob {   // vertex normals of one mesh
   const double* x;
   const int* tris; const int* adj_off; const int* adj;
@@ -765,7 +764,6 @@ struct VarSeg {         // n consecutive samples of one map, resident in the chu
   double* out;          // [N]
   double nscale;        // mode 2: 1/S as the host divides it (launch_accumulate's scale_after)
 };
-void launch_var_instance(hipStream_t st, int n_groups, int Nmax, const VarGroup* groups, const VarSample* samples);
 void launch_var_normals(hipStream_t st, int n_jobs, int Nmax, const VarNormalJob* jobs);
 void launch_var_sum(hipStream_t st, int n_segs, int Nmax, const VarSeg* segs);
 void launch_var_centred(hipStream_t st, int n_segs, int Nmax, const VarSeg* segs);

@@ -20,59 +20,7 @@ __host__ __device__ inline int cdiv(int a, int b) { return (a + b - 1) / b; }
 
 __device__ __forceinline__ bool fit_model_side(const FitItem& f, int rec) { return f.dirs[rec] == 0; }
 
-// F1: instances of up to kFitInstGroup fits from one pass over the basis (thread = model point).  The sums are instance_point's: the
-// mean, then the basis columns in order with separately rounded multiply and add, then instance_pose — every fit's points are the bits
-// of its own k_instance launch.  The coefficients are wave-uniform loads from the fit's device vector (no rank limit from LDS).
-constexpr int kFitInstBlock = 64;
-constexpr int kFitInstU = 8;  // basis columns (× 3 rows) in flight per batch of loads
-__global__ void __launch_bounds__(kFitInstBlock) k_fit_instance(int B, int N, int r, const double* __restrict__ Qp, const double* __restrict__ ref,
-                                                                const double* __restrict__ mean, const FitItem* __restrict__ items) {
-  constexpr int G = kFitInstGroup;
-  const int g0 = blockIdx.y * G, ng = min(G, B - g0);
-  const int i = blockIdx.x * kFitInstBlock + threadIdx.x;
-  if (i >= N) return;
-  const double* cf[G];
-#pragma unroll
-  for (int g = 0; g < G; ++g) cf[g] = items[g0 + (g < ng ? g : 0)].coeffs;
-  double a0[G], a1[G], a2[G];
-  const double m0 = mean[3 * i], m1 = mean[3 * i + 1], m2 = mean[3 * i + 2];
-#pragma unroll
-  for (int g = 0; g < G; ++g) { a0[g] = m0; a1[g] = m1; a2[g] = m2; }
-  const double* q = Qp + i;
-  int j = 0;
-  for (; j + kFitInstU <= r; j += kFitInstU) {
-    double v[3 * kFitInstU];
-#pragma unroll
-    for (int u = 0; u < 3 * kFitInstU; ++u) v[u] = q[(size_t)(3 * j + u) * N];
-    __builtin_amdgcn_sched_barrier(0);  // (all loads requested before the first multiply)
-#pragma unroll
-    for (int u = 0; u < kFitInstU; ++u)
-#pragma unroll
-      for (int g = 0; g < G; ++g) {
-        const double c = cf[g][j + u];
-        a0[g] = a0[g] + v[3 * u] * c;
-        a1[g] = a1[g] + v[3 * u + 1] * c;
-        a2[g] = a2[g] + v[3 * u + 2] * c;
-      }
-  }
-  for (; j < r; ++j) {
-    const double v0 = q[(size_t)(3 * j) * N], v1 = q[(size_t)(3 * j + 1) * N], v2 = q[(size_t)(3 * j + 2) * N];
-#pragma unroll
-    for (int g = 0; g < G; ++g) {
-      const double c = cf[g][j];
-      a0[g] = a0[g] + v0 * c;
-      a1[g] = a1[g] + v1 * c;
-      a2[g] = a2[g] + v2 * c;
-    }
-  }
-#pragma unroll
-  for (int g = 0; g < G; ++g) {
-    if (g >= ng) continue;
-    const FitItem& f = items[g0 + g];
-    const d3 p = instance_pose(i, ref, f.pose, a0[g], a1[g], a2[g]);  // ModelFittingParameters.scala:108-110
-    f.x[3 * i] = p.x; f.x[3 * i + 1] = p.y; f.x[3 * i + 2] = p.z;
-  }
-}
+// F1: the fits' instances are one launch_instance_many (kernels_geometry.hip) over the call's instance records.
 
 // F2: the searches' initialisation.  Model side: gather the sample ids' points of the new instance (:72) and take each query's bound
 // from its previous winner; target side: the nearest-vertex queries' bounds against the new instance.
@@ -172,11 +120,6 @@ __global__ void __launch_bounds__(256) k_fit_mean_step(const FitItem* __restrict
 }  // namespace
 
 int query_kpad(int K) { return (K + kQU - 1) / kQU * kQU; }
-
-void launch_fit_instance(hipStream_t st, int B, int N, int r, const double* Qp, const double* ref, const double* mean, const FitItem* items) {
-  ProfScope _ps(st, KID_INSTANCE);
-  hipLaunchKernelGGL(k_fit_instance, dim3(cdiv(N, kFitInstBlock), cdiv(B, kFitInstGroup)), dim3(kFitInstBlock), 0, st, B, N, r, Qp, ref, mean, items);
-}
 
 void launch_fit_searches(hipStream_t st, int B, int rec, const FitGrid& g, int N, const double* ref, const double* mean, const FitItem* items) {
   { ProfScope _ps(st, KID_SURFACE_INIT);

@@ -70,6 +70,65 @@ __global__ void __launch_bounds__(kBlock) k_instance_pose(int N, const double* _
   x[3 * i] = p.x; x[3 * i + 1] = p.y; x[3 * i + 2] = p.z;
 }
 
+// K1 of many items: thread = model point, blockIdx.y = group of up to kInstGroup items of one model.  The sums are instance_point's:
+// the mean, then the basis columns in order with separately rounded multiply and add, then instance_pose — every item's points are the
+// bits of its own k_instance launch.  The basis is read once per group instead of once per item (24·r bytes per point: 137 MB per
+// item at N = 28,561, r = 200).  The coefficients are wave-uniform loads from the items' device vectors (no rank limit from LDS).
+// The basis pointer comes out of a record: global_ptr keeps its loads counted (icp_device.hpp).
+constexpr int kInstManyBlock = 64;
+constexpr int kInstManyU = 8;  // basis columns (× 3 rows) in flight per batch of loads
+__global__ void __launch_bounds__(kInstManyBlock) k_instance_many(const InstanceGroup* __restrict__ groups, const InstanceItem* __restrict__ items) {
+  constexpr int G = kInstGroup;
+  const InstanceGroup& grp = groups[blockIdx.y];
+  const int N = grp.N, r = grp.r, ng = grp.n;
+  const int i = blockIdx.x * kInstManyBlock + threadIdx.x;
+  if (i >= N) return;
+  const InstanceItem* itm = items + grp.first;
+  global_ptr<const double> cf[G];
+#pragma unroll
+  for (int g = 0; g < G; ++g) cf[g] = as_global(itm[g < ng ? g : 0].coeffs);
+  const global_ptr<const double> mean = as_global(grp.mean);
+  double a0[G], a1[G], a2[G];
+  const double m0 = mean[3 * i], m1 = mean[3 * i + 1], m2 = mean[3 * i + 2];
+#pragma unroll
+  for (int g = 0; g < G; ++g) { a0[g] = m0; a1[g] = m1; a2[g] = m2; }
+  const global_ptr<const double> q = as_global(grp.Qp) + i;
+  int j = 0;
+  for (; j + kInstManyU <= r; j += kInstManyU) {
+    double v[3 * kInstManyU];
+#pragma unroll
+    for (int u = 0; u < 3 * kInstManyU; ++u) v[u] = q[(size_t)(3 * j + u) * N];
+    __builtin_amdgcn_sched_barrier(0);  // (all loads requested before the first multiply)
+#pragma unroll
+    for (int u = 0; u < kInstManyU; ++u)
+#pragma unroll
+      for (int g = 0; g < G; ++g) {
+        const double c = cf[g][j + u];
+        a0[g] = a0[g] + v[3 * u] * c;
+        a1[g] = a1[g] + v[3 * u + 1] * c;
+        a2[g] = a2[g] + v[3 * u + 2] * c;
+      }
+  }
+  for (; j < r; ++j) {
+    const double v0 = q[(size_t)(3 * j) * N], v1 = q[(size_t)(3 * j + 1) * N], v2 = q[(size_t)(3 * j + 2) * N];
+#pragma unroll
+    for (int g = 0; g < G; ++g) {
+      const double c = cf[g][j];
+      a0[g] = a0[g] + v0 * c;
+      a1[g] = a1[g] + v1 * c;
+      a2[g] = a2[g] + v2 * c;
+    }
+  }
+#pragma unroll
+  for (int g = 0; g < G; ++g) {
+    if (g >= ng) continue;
+    const InstanceItem& s = itm[g];
+    const d3 p = instance_pose(i, grp.ref, s.pose, a0[g], a1[g], a2[g]);  // ModelFittingParameters.scala:108-110
+    const global_ptr<double> x = as_global(s.x);
+    x[3 * i] = p.x; x[3 * i + 1] = p.y; x[3 * i + 2] = p.z;
+  }
+}
+
 __global__ void __launch_bounds__(kBlock) k_vertex_normals(int N, const double* __restrict__ x, const int* __restrict__ tris,
                                                             const int* __restrict__ adj_off, const int* __restrict__ adj,
                                                             double* __restrict__ normals) {
@@ -200,6 +259,12 @@ void launch_instance_keep(hipStream_t st, int N, int r, const double* Qp, const 
 void launch_instance_pose(hipStream_t st, int N, const double* ref, const Pose& pose, const double* defo_in, double* x, double* defo_out) {
   ProfScope _ps(st, KID_INSTANCE);
   hipLaunchKernelGGL(k_instance_pose, dim3(cdiv(N, kBlock)), dim3(kBlock), 0, st, N, ref, pose, defo_in, x, defo_out);
+}
+
+void launch_instance_many(hipStream_t st, int n_groups, int Nmax, const InstanceGroup* groups, const InstanceItem* items) {
+  if (n_groups <= 0) return;
+  ProfScope _ps(st, KID_INSTANCE);
+  hipLaunchKernelGGL(k_instance_many, dim3(cdiv(Nmax, kInstManyBlock), n_groups), dim3(kInstManyBlock), 0, st, groups, items);
 }
 
 void launch_vertex_normals(hipStream_t st, int N, const double* x, const int* tris, const int* adj_off,

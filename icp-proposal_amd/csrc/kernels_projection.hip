@@ -8,7 +8,7 @@
 //   P2 k_proj_gemm      b = Qᵀ·D on the f64 matrix cores: a wave owns up to kProjTiles 16 × 16 output tiles (basis columns × items of one
 //                       group) over one slab of rows, so the basis is read once per group of 16 items
 //   P3 k_proj_solve     one workgroup per item: the slabs' partial sums folded in slab order, then c = P·b in column order
-// The meshes of items given as states, and the projections asked for, are instanced by k_var_instance (kernels_variability.hip).
+// The meshes of items given as states, and the projections asked for, are instanced by k_instance_many (kernels_geometry.hip).
 //
 // An item's bits depend on nothing but the item: its residuals are its own; a column of the matrix instruction never sees another
 // column's data (D[i][j] = Σ_k A[i][k]·B[k][j]: item j's sums read item j's operands only) and the padding columns of a group are

@@ -3,7 +3,8 @@
 //
 // The samples of a call pass through one chunk buffer of fixed size, round by round.  Every launch of a round carries all its work
 // (sample group, normal job or map segment = blockIdx.y) and reads its record from a device table made once per call:
-//   V1 k_var_instance  the sample meshes of the round: up to kVarInstGroup samples of one model from ONE pass over its basis
+//   V1 k_instance_many the sample meshes of the round: up to kInstGroup samples of one model from ONE pass over its basis
+//                      (kernels_geometry.hip, shared by every batched entry point)
 //   V2 k_var_normals   vertex normals of the samples that need them (mode 2) and of the mode-1 reference meshes
 //   V3 k_var_sum       lane = vertex: Σ_s x_s in sample order (and Σ_s n_s in mode 2), carried from round to round in the map's own
 //                      buffers; the map's last segment applies the 1/S scale
@@ -20,66 +21,7 @@ namespace {
 
 inline int cdiv(int a, int b) { return (a + b - 1) / b; }
 
-constexpr int kVarInstBlock = 64;
-constexpr int kVarInstU = 8;  // basis columns (× 3 rows) in flight per batch of loads
 constexpr int kVarBlock = 128;
-
-// V1.  Thread = model point, blockIdx.y = group.  The sums are instance_point's: the mean, then the basis columns in order with
-// separately rounded multiply and add, then instance_pose — every sample's points are the bits of its own k_instance launch.  The
-// basis is read once per group instead of once per sample (24·r bytes per point: 137 MB per sample at N = 28,561, r = 200).  The
-// coefficients are wave-uniform loads from the samples' device vectors.  The basis pointer comes out of a record: global_ptr keeps
-// its loads counted (icp_device.hpp).
-__global__ void __launch_bounds__(kVarInstBlock) k_var_instance(const VarGroup* __restrict__ groups, const VarSample* __restrict__ samples) {
-  constexpr int G = kVarInstGroup;
-  const VarGroup& grp = groups[blockIdx.y];
-  const int N = grp.N, r = grp.r, ng = grp.n;
-  const int i = blockIdx.x * kVarInstBlock + threadIdx.x;
-  if (i >= N) return;
-  const VarSample* smp = samples + grp.first;
-  global_ptr<const double> cf[G];
-#pragma unroll
-  for (int g = 0; g < G; ++g) cf[g] = as_global(smp[g < ng ? g : 0].coeffs);
-  const global_ptr<const double> mean = as_global(grp.mean);
-  double a0[G], a1[G], a2[G];
-  const double m0 = mean[3 * i], m1 = mean[3 * i + 1], m2 = mean[3 * i + 2];
-#pragma unroll
-  for (int g = 0; g < G; ++g) { a0[g] = m0; a1[g] = m1; a2[g] = m2; }
-  const global_ptr<const double> q = as_global(grp.Qp) + i;
-  int j = 0;
-  for (; j + kVarInstU <= r; j += kVarInstU) {
-    double v[3 * kVarInstU];
-#pragma unroll
-    for (int u = 0; u < 3 * kVarInstU; ++u) v[u] = q[(size_t)(3 * j + u) * N];
-    __builtin_amdgcn_sched_barrier(0);  // (all loads requested before the first multiply)
-#pragma unroll
-    for (int u = 0; u < kVarInstU; ++u)
-#pragma unroll
-      for (int g = 0; g < G; ++g) {
-        const double c = cf[g][j + u];
-        a0[g] = a0[g] + v[3 * u] * c;
-        a1[g] = a1[g] + v[3 * u + 1] * c;
-        a2[g] = a2[g] + v[3 * u + 2] * c;
-      }
-  }
-  for (; j < r; ++j) {
-    const double v0 = q[(size_t)(3 * j) * N], v1 = q[(size_t)(3 * j + 1) * N], v2 = q[(size_t)(3 * j + 2) * N];
-#pragma unroll
-    for (int g = 0; g < G; ++g) {
-      const double c = cf[g][j];
-      a0[g] = a0[g] + v0 * c;
-      a1[g] = a1[g] + v1 * c;
-      a2[g] = a2[g] + v2 * c;
-    }
-  }
-#pragma unroll
-  for (int g = 0; g < G; ++g) {
-    if (g >= ng) continue;
-    const VarSample& s = smp[g];
-    const d3 p = instance_pose(i, grp.ref, s.pose, a0[g], a1[g], a2[g]);  // ModelFittingParameters.scala:108-110
-    const global_ptr<double> x = as_global(s.x);
-    x[3 * i] = p.x; x[3 * i + 1] = p.y; x[3 * i + 2] = p.z;
-  }
-}
 
 // V2: k_vertex_normals of one mesh per blockIdx.y
 __global__ void __launch_bounds__(kVarBlock) k_var_normals(const VarNormalJob* __restrict__ jobs) {
@@ -157,11 +99,6 @@ __global__ void __launch_bounds__(kVarBlock) k_var_centred(const VarSeg* __restr
 
 }  // namespace
 
-void launch_var_instance(hipStream_t st, int n_groups, int Nmax, const VarGroup* groups, const VarSample* samples) {
-  if (n_groups <= 0) return;
-  ProfScope _ps(st, KID_INSTANCE);
-  hipLaunchKernelGGL(k_var_instance, dim3(cdiv(Nmax, kVarInstBlock), n_groups), dim3(kVarInstBlock), 0, st, groups, samples);
-}
 void launch_var_normals(hipStream_t st, int n_jobs, int Nmax, const VarNormalJob* jobs) {
   if (n_jobs <= 0) return;
   hipLaunchKernelGGL(k_var_normals, dim3(cdiv(Nmax, kVarBlock), n_jobs), dim3(kVarBlock), 0, st, jobs);

@@ -19,8 +19,8 @@ CHUNK_DOUBLES = 4 << 20     # kProjChunkDoubles: meshes of a chunk; as many doub
 GROUP = 16                  # kProjGroup
 MIN_SLAB_ROWS, MAX_SLABS = 256, 128  # kProjMinSlabRows, kProjMaxSlabs
 ITEM_RECORD_BYTES = 144     # sizeof(ProjItem): mesh pointer, Pose (16 doubles), flag
-SAMPLE_RECORD_BYTES = 144   # sizeof(VarSample): an item given as a state, a projection
-GROUP_RECORD_BYTES = 48     # sizeof(VarGroup); 8 instances a group
+SAMPLE_RECORD_BYTES = 144   # sizeof(InstanceItem): an item given as a state, a projection
+GROUP_RECORD_BYTES = 48     # sizeof(InstanceGroup); 8 instances a group
 
 
 def bound_of(c):

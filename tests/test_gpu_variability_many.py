@@ -15,8 +15,8 @@ pytestmark = pytest.mark.gpu
 
 # icp-proposal_amd/csrc/abi_variability_many.inl: kVarChunkDoubles (the chunk buffer) and the per-sample records
 CHUNK_DOUBLES = 8 << 20
-SAMPLE_RECORD_BYTES = 144   # sizeof(VarSample): coefficient pointer, Pose (16 doubles), mesh pointer
-GROUP_RECORD_BYTES = 48     # sizeof(VarGroup); kVarInstGroup = 8 samples a group
+SAMPLE_RECORD_BYTES = 144   # sizeof(InstanceItem): coefficient pointer, Pose (16 doubles), mesh pointer
+GROUP_RECORD_BYTES = 48     # sizeof(InstanceGroup); kInstGroup = 8 samples a group
 SIZES = (2, 3, 25, 41, 12)  # samples per map of the mixed batches
 
 
