@@ -594,125 +594,22 @@ __device__ __forceinline__ void tridiag_kernel_body(const TridiagIO& a) {
   tridiagonalise<NW, SI, NT, TOFF>(a, A, col0, d0, lds);
   EIG_STAMP(1);
 }
-template <int NW, int SI, int NT, int TOFF>
-__global__ void __launch_bounds__(NW * 64) k_tridiag(TridiagIO a) { tridiag_kernel_body<NW, SI, NT, TOFF>(a); }
-// the same for up to kTriMany matrices side by side, one workgroup each (the chains of a wide step: kernels_wide.hip)
-constexpr int kTriMany = kTriManyMax;  // (32, icp_kernels.hpp: the largest of the records below, TriSolveMany, is 3.8 KB of the 4 KB argument segment)
-struct TridiagMany { TridiagIO p[kTriMany]; };
-template <int NW, int SI, int NT, int TOFF>
-__global__ void __launch_bounds__(NW * 64) k_tridiag_many(TridiagMany m, const int* __restrict__ skip_all) {
-  if (skip_all && skip_all[blockIdx.x] != 0) return;  // (the on-device loop: a chain that did not move)
-  const TridiagIO a = m.p[blockIdx.x];  // (a copy: scalar registers, as a by-value kernel argument)
+// The kernels of the route take their records by value, CAP of them in the kernel arguments (the pattern of EigenBatch in
+// kernels_posterior.hip), one workgroup — or one slice of the grid — per record; skip_all (optional, device): != 0 leaves a record
+// alone (the on-device loop: a chain that did not move).  Two capacities are instantiated: kTriOne for one decomposition,
+// kTriMany for decompositions side by side (the chains of a wide step: kernels_wide.hip).  The record is copied to a local before
+// the body runs: scalar registers, as a by-value kernel argument.
+constexpr int kTriOne = 1;
+constexpr int kTriMany = kTriManyMax;  // (32, icp_kernels.hpp)
+template <class IO, int CAP> struct TriBatch { IO p[CAP]; };
+template <int CAP> __device__ __forceinline__ int tri_record(int q) { return CAP == 1 ? 0 : q; }
+
+template <int CAP, int NW, int SI, int NT, int TOFF>
+__global__ void __launch_bounds__(NW * 64) k_tridiag(TriBatch<TridiagIO, CAP> m, const int* __restrict__ skip_all) {
+  const int q = tri_record<CAP>(blockIdx.x);
+  if (skip_all && skip_all[q] != 0) return;
+  const TridiagIO a = m.p[q];
   tridiag_kernel_body<NW, SI, NT, TOFF>(a);
-}
-
-// Ranks <= 64, up to two decompositions per launch (one workgroup each), with the front end of a decomposition that was
-// enqueued ahead of its input (EigenSpec, see k_posterior_eigen_rr): wait on the device for the regression launch's word, give up
-// on cancellation or after 5 ms, sum the split-K partials.
-struct TriSmallProblem {
-  const double* M;            // r×r matrix — or, splits > 0, the partials: splits × (r+1)² row-major, lower triangle, identity not added
-  int splits;
-  const int* ready;           // (optional) device word raised to ready_seq or beyond when the partials are complete
-  int ready_seq;
-  const int* cancel;          // (optional) pinned host word: give up once *cancel == seq
-  int seq;
-  const double* sqrt_lambda;
-  TridiagIO out;              // d, e, beta, Hv (M / sqrt_lambda unused here)
-  int* sync;                  // the solve launch's words: [2] = skip
-};
-struct TriSmallBatch { int r; TriSmallProblem p[2]; };
-
-__global__ void __launch_bounds__(256) k_tridiag_small(TriSmallBatch b) {
-  constexpr int NW = 4, SI = 1, NT = 16;
-  __shared__ double lds[TridiagLds<NW, SI>::doubles];
-  __shared__ int s_cancel;
-  const TriSmallProblem& pb = b.p[blockIdx.x];
-  const int n = b.r, off = 64 - n;
-  const int tid = threadIdx.x, l = tid & 63;
-  const int w = __builtin_amdgcn_readfirstlane(tid >> 6);
-  if (tid == 0) s_cancel = 0;
-  __syncthreads();
-  const bool is_poll = pb.cancel != nullptr && tid == 255;
-  if (tid == 255) {
-    if (pb.ready) {
-      const long long t0 = __builtin_amdgcn_s_memrealtime();  // 100 MHz
-      for (;;) {
-        if (__hip_atomic_load(pb.ready, __ATOMIC_ACQUIRE, __HIP_MEMORY_SCOPE_AGENT) - pb.ready_seq >= 0) break;
-        if (pb.cancel && __hip_atomic_load(pb.cancel, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_SYSTEM) == pb.seq) { s_cancel = 1; break; }
-        if (__builtin_amdgcn_s_memrealtime() - t0 > 500000) { s_cancel = 2; break; }
-        __builtin_amdgcn_s_sleep(32);
-      }
-    } else if (pb.cancel) {
-      if (__hip_atomic_load(pb.cancel, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_SYSTEM) == pb.seq) s_cancel = 1;
-    }
-  }
-  __syncthreads();
-  __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "agent");  // (acquire side for the plain loads of the partials below)
-  if (s_cancel) {
-    if (tid == 0) __hip_atomic_store(pb.sync + 2, s_cancel, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-    return;
-  }
-  // ---- the matrix into registers: lane l holds row l − off, wave w columns w + 4t − off
-  const double* __restrict__ sl = pb.sqrt_lambda;
-  double A[SI][NT], col0[SI];
-  const int i = l - off;
-  double d0;
-  if (pb.splits > 0) {
-    // Σ over the splits in split order from 0.0, like the factorisation; four splits × seventeen entries in flight
-    const size_t nn = (size_t)(n + 1) * (n + 1);
-    size_t offs[NT + 1];
-    bool live[NT + 1];
-#pragma unroll
-    for (int t = 0; t <= NT; ++t) {
-      const int j = t < NT ? w + NW * t - off : 0;  // (slot NT: column 0, for the first reflector)
-      live[t] = i >= 0 && j >= 0;
-      const int hi = max(i, j), lo = min(i, j);
-      offs[t] = live[t] ? (size_t)hi * (n + 1) + lo : 0;
-    }
-    double acc[NT + 1];
-#pragma unroll
-    for (int t = 0; t <= NT; ++t) acc[t] = 0.0;
-    for (int sp = 0; sp < pb.splits; sp += 4) {
-      double q[4][NT + 1];
-#pragma unroll
-      for (int u = 0; u < 4; ++u) {
-        const double* src = pb.M + (size_t)min(sp + u, pb.splits - 1) * nn;
-#pragma unroll
-        for (int t = 0; t <= NT; ++t) q[u][t] = src[offs[t]];
-      }
-#pragma unroll
-      for (int u = 0; u < 4; ++u)
-        if (sp + u < pb.splits) {
-#pragma unroll
-          for (int t = 0; t <= NT; ++t) acc[t] += q[u][t];
-        }
-    }
-    const double sli = i >= 0 ? sl[i] : 1.0;
-#pragma unroll
-    for (int t = 0; t < NT; ++t) {
-      const int j = w + NW * t - off;
-      A[0][t] = live[t] ? (acc[t] + (i == j ? 1.0 : 0.0)) / (sli * sl[j]) : 0.0;
-    }
-    col0[0] = live[NT] ? (acc[NT] + (i == 0 ? 1.0 : 0.0)) / (sli * sl[0]) : 0.0;
-    d0 = readlane_f64(col0[0], off);  // (N_00: lane off of every wave holds row 0)
-  } else {
-    auto entry = [&](int ii, int jj) { return 0.5 * (pb.M[(size_t)jj * n + ii] + pb.M[(size_t)ii * n + jj]) / (sl[ii] * sl[jj]); };
-    col0[0] = i >= 0 ? entry(i, 0) : 0.0;
-#pragma unroll
-    for (int t = 0; t < NT; ++t) {
-      const int j = w + NW * t - off;
-      A[0][t] = i >= 0 && j >= 0 ? entry(i, j) : 0.0;
-    }
-    d0 = entry(0, 0);
-  }
-  TridiagIO a = pb.out;
-  a.n = n;
-  EIG_STAMP(0);
-  tridiagonalise<NW, SI, NT, 0>(a, A, col0, d0, lds);
-  EIG_STAMP(1);
-  // cancelled meanwhile? (the solve launch then only tidies up)
-  if (is_poll && __hip_atomic_load(pb.cancel, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_SYSTEM) == pb.seq)
-    __hip_atomic_store(pb.sync + 2, 1, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
 }
 
 // ---------------------------------------------------------------------------------------------------------------------
@@ -727,13 +624,9 @@ struct TriSolveIO {
   double* Vt;         // n×n: row `rank`
   double* S;          // [n] = 1/mu, descending
   double* mu;         // [n] scratch: the eigenvalues, ascending (the last wave checks the gaps)
-  const double* wy;   // [ceil((n−2)/8)][64] T factors of the reflector blocks (k_tri_wy), row-major 8×8, upper triangles
-  int* sync;          // [3] {waves finished, trouble flags, skip: 1 = cancelled, 2 = its input never came}: zero between launches
+  const double* wy;   // [ceil((n−2)/8)][64] T factors of the reflector blocks (tri_wy_body), row-major 8×8, upper triangles
+  int* sync;          // [5] {waves finished, trouble flags, skip: 1 = cancelled, 2 = its input never came, no refinement, no vectors}: [0..2] zero between launches
   int* status;        // status[0]: 0 ok, 2 = not trustworthy (gaps below resolution / non-finite); status[-1]: 0
-  // (ranks <= 64, where nothing follows this launch) published by the last wave:
-  int* host_status;   // pinned copy of the status (kEigenGaveUp for skip = 2)
-  int* done_word;     // set to done_value when the outputs are complete — or the decomposition was dropped
-  int done_value;
 };
 
 // Seven multisection passes and TWO twisted factorisations.  Round 3 had dropped the second factorisation (two chains of n − 1
@@ -801,8 +694,8 @@ __device__ __forceinline__ int sturm_count(const double* __restrict__ ds, const 
 
 // The reflectors in blocks of eight, compact WY (dlarft, forward / columnwise): H_k0 ··· H_k0+7 = I − V·T·Vᵀ with T upper triangular,
 // T_ii = β_i, T_{0:i,i} = −β_i · T_{0:i,0:i} · (V_{:,0:i}ᵀ v_i).  One wave per block (28 inner products, reduced seven at a time); the
-// eigenpair waves of the solve launch then apply EIGHT reflectors per round of reductions (tri_solve_body).  Runs between the
-// reduction and the solve.
+// back-transformation then applies EIGHT reflectors per round (tri_back_body).  Run by the solve launch's trailing workgroups
+// (tri_solve_or_wy).
 struct TriWyIO {
   int n;
   const double* beta;
@@ -854,21 +747,12 @@ __device__ __forceinline__ void tri_wy_body(const TriWyIO& a, const int blk) {  
       for (int i = 0; i < kWyBlock; ++i) out[jj * kWyBlock + i] = i >= jj ? T[jj][i] : 0.0;
   }
 }
-template <int SI>
-__global__ void __launch_bounds__(64) k_tri_wy(TriWyIO a0, TriWyIO a1) { tri_wy_body<SI>(blockIdx.y ? a1 : a0, blockIdx.x); }
-struct TriWyMany { TriWyIO p[kTriMany]; };
-template <int SI>
-__global__ void __launch_bounds__(64) k_tri_wy_many(TriWyMany m, const int* __restrict__ skip_all) {
-  if (skip_all && skip_all[blockIdx.y] != 0) return;
-  const TriWyIO a = m.p[blockIdx.y];
-  tri_wy_body<SI>(a, blockIdx.x);
-}
 
 struct TriSolveLds {  // the solve launch's dynamic LDS (doubles): offsets for an n x n problem
   int oDs, oE2, oDsr, oE2r, oEs, oRed, oWy, oScr, scr_stride, oCarry, carry_stride, total;
   __host__ __device__ explicit TriSolveLds(int n) {
     const int np = n + 8, nblk = (n - 2 + kWyBlock - 1) / kWyBlock;
-    oDs = 0; oE2 = np; oDsr = 2 * np; oE2r = 3 * np; oEs = 4 * np; oRed = oEs + n; oWy = oRed + 8;
+    oDs = 0; oE2 = np; oDsr = 2 * np; oE2r = 3 * np; oEs = 4 * np; oRed = oEs + n; oWy = oRed + 8;  // (oWy: unused since the back-transformation is a launch of its own; the layout behind it is kept)
     oScr = oWy + (nblk > 0 ? nblk : 0) * kWyBlock * kWyBlock;
     scr_stride = 2 * n + 2 * np;       // per wave: D⁺ | D⁻ by row, then the two chains' values (a group of eight filed whole)
     oCarry = oScr + 4 * scr_stride;
@@ -878,13 +762,10 @@ struct TriSolveLds {  // the solve launch's dynamic LDS (doubles): offsets for a
 };
 inline size_t tri_solve_lds_bytes(int n) { return sizeof(double) * (size_t)TriSolveLds(n).total; }
 
-// kBack: the back-transformation inside this launch, eigenvector by eigenvector (one row slot per lane: ranks <= 64, where the launch's
-// last wave also publishes the completion words).  Otherwise the wave hands the tridiagonal matrix's eigenvector on as row j of Vt, and
-// k_tri_back — sixteen vectors per wave on the matrix cores — takes it from there.
-template <int SI, bool kBack>
+// The wave hands the tridiagonal matrix's eigenvector on as row j of Vt; k_tri_back — sixteen vectors per wave on the matrix cores —
+// takes it from there.
+template <int SI>
 __device__ __forceinline__ void tri_solve_body(const TriSolveIO& a) {
-  constexpr int LD = 64 * SI;
-  const int off = LD - a.n;  // position of index 0 (see tridiagonalise)
   // LDS sized by n, not by the largest rank (round 5: 64 KB of static arrays let two workgroups share a compute unit; at rank 200 the
   // arrays below take 49 KB and three do — the launch of 16 posteriors side by side, 800 workgroups of four f64-issue-bound waves,
   // is a throughput kernel): tri_solve_lds_bytes(n) of dynamic shared memory
@@ -897,7 +778,6 @@ __device__ __forceinline__ void tri_solve_body(const TriSolveIO& a) {
   double* e2r = tri_dyn + L.oE2r;
   double* es = tri_dyn + L.oEs;      // [n] off-diagonal
   double* red = tri_dyn + L.oRed;    // [8]
-  double* wy = tri_dyn + L.oWy;      // T factors of the reflector blocks
   const int tid = threadIdx.x, l = tid & 63;
   const int w = __builtin_amdgcn_readfirstlane(tid >> 6);
   const int j = blockIdx.x * 4 + w;  // this wave's eigenvalue (ascending), rank j of the output
@@ -912,11 +792,7 @@ __device__ __forceinline__ void tri_solve_body(const TriSolveIO& a) {
     if (last) {
       a.sync[0] = 0; a.sync[1] = 0; a.sync[2] = 0;
       a.sync[4] = 1;  // (no vectors: k_tri_back has nothing to do)
-      if (skip == 2) {  // timed out: tell the host, and mark the basis that was never written so that nothing starts from it
-        if (a.host_status) __hip_atomic_store(a.host_status, 3 /* kEigenGaveUp */, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_SYSTEM);
-        a.V[0] = __builtin_nan("");
-      }
-      if (a.done_word) __hip_atomic_store(a.done_word, a.done_value, __ATOMIC_RELEASE, __HIP_MEMORY_SCOPE_AGENT);
+      if (skip == 2) a.V[0] = __builtin_nan("");  // (timed out: mark the basis that was never written so that nothing starts from it)
     }
     return;
   }
@@ -943,10 +819,6 @@ __device__ __forceinline__ void tri_solve_body(const TriSolveIO& a) {
     if (i < n - 1) e2r[n - 2 - i] = fmax(ee * ee, 1e-280);
   }
   if (tid < 8) { ds[n + tid] = 0.0; e2[n + tid] = 0.0; dsr[n + tid] = 0.0; e2r[n - 1 + tid] = 0.0; }  // (read, never used, by the chains' last group)
-  const int nblk = (n - 2 + kWyBlock - 1) / kWyBlock;
-  if constexpr (kBack) {
-    for (int i = tid; i < nblk * kWyBlock * kWyBlock; i += 256) wy[i] = a.wy[i];
-  }
   __syncthreads();
   if (j >= n) return;  // (no barrier below)
   TRI_STAMP(9);
@@ -1089,103 +961,11 @@ __device__ __forceinline__ void tri_solve_body(const TriSolveIO& a) {
   }
   TRI_STAMP(11);
   const double muj = lam * anorm;
-  if constexpr (!kBack) {
-    // the vector of T, normalised, as row j of Vt (contiguous); back-transformation, sign and the transposed copy: k_tri_back
-    const double sc = 1.0 / sqrt(znorm2);
-    for (int i = l; i < n; i += 64) a.Vt[(size_t)j * n + i] = zb[i] * sc;
-    if (!(muj > 0.0)) trouble = true;
-    if (l == 0) { a.S[j] = 1.0 / muj; a.mu[j] = muj; }
-  } else {
-  // ---- back-transformation: z ← H_0 H_1 ··· H_{n−3} z, one row slot per lane, reflectors fetched eight ahead
-  double zs[SI];
-  {
-    const double sc = 1.0 / sqrt(znorm2);
-#pragma unroll
-    for (int s = 0; s < SI; ++s) zs[s] = l + 64 * s >= off ? zb[l + 64 * s - off] * sc : 0.0;
-  }
-  {
-    // in blocks of eight reflectors, z ← (I − V·T·Vᵀ) z with the T factors of k_tri_wy, last block first: eight inner products reduced
-    // together (wave_sum_many) instead of eight dependent (dot product → wave reduction → update) rounds; the next block's
-    // reflectors are requested a block ahead (L2: ≈ 500 cycles)
-    // (two register sets, one in use while the other is on its way: every load is unconditional — a clamped row, zeroed afterwards
-    // where the block runs past the last reflector — and issued before the block in hand is touched)
-    double va[kWyBlock][SI], vb2[kWyBlock][SI];
-    auto fetch = [&](double (&dst)[kWyBlock][SI], int blk) {
-      const int b = max(blk, 0);
-#pragma unroll
-      for (int q = 0; q < kWyBlock; ++q) {
-        const int k = min(b * kWyBlock + q, n - 3);
-#pragma unroll
-        for (int s = 0; s < SI; ++s) dst[q][s] = a.Hv[(size_t)k * LD + l + 64 * s];
-      }
-    };
-    auto apply = [&](double (&v)[kWyBlock][SI], int blk) {
-      const double* Tb = wy + blk * kWyBlock * kWyBlock;
-      double u[kWyBlock];
-#pragma unroll
-      for (int q = 0; q < kWyBlock; ++q) {
-        const bool live = blk * kWyBlock + q < n - 2;
-        u[q] = 0.0;
-#pragma unroll
-        for (int s = 0; s < SI; ++s) {
-          v[q][s] = live ? v[q][s] : 0.0;
-          u[q] = fma(v[q][s], zs[s], u[q]);
-        }
-      }
-      wave_sum_many<kWyBlock>(u);  // u = Vᵀz
-#pragma unroll
-      for (int jj = 0; jj < kWyBlock; ++jj) {  // t = T·u (upper triangle), then z −= V·t
-        double t = 0.0;
-#pragma unroll
-        for (int i = jj; i < kWyBlock; ++i) t = fma(Tb[jj * kWyBlock + i], u[i], t);
-#pragma unroll
-        for (int s = 0; s < SI; ++s) zs[s] = fma(-t, v[jj][s], zs[s]);
-      }
-    };
-    fetch(va, nblk - 1);
-    for (int blk = nblk - 1; blk >= 0; blk -= 2) {
-      fetch(vb2, blk - 1);
-      __builtin_amdgcn_sched_barrier(0);
-      apply(va, blk);
-      if (blk - 1 >= 0) {
-        fetch(va, blk - 2);
-        __builtin_amdgcn_sched_barrier(0);
-        apply(vb2, blk - 1);
-      }
-    }
-  }
-  TRI_STAMP(12);
-  // ---- canonical sign (largest-|.| component positive, the first among equals), output
-  double bv = -1.0;
-  int bi = 0x7fffffff;
-#pragma unroll
-  for (int s = 0; s < SI; ++s) {
-    const int i = l + 64 * s;
-    const double av = fabs(zs[s]);
-    if (i >= off && av > bv) { bv = av; bi = i; }
-  }
-  for (int o = 32; o > 0; o >>= 1) {
-    const double ov = __shfl_xor(bv, o, 64);
-    const int oi = __shfl_xor(bi, o, 64);
-    if (ov > bv || (ov == bv && oi < bi)) { bv = ov; bi = oi; }
-  }
-  double lead = zs[0];
-#pragma unroll
-  for (int s = 1; s < SI; ++s) lead = (bi >> 6) == s ? zs[s] : lead;
-  lead = readlane_f64(lead, bi & 63);
-  const double sgn = lead < 0.0 ? -1.0 : 1.0;
-  if (!(bv >= 0.0) || !(muj > 0.0)) trouble = true;
-#pragma unroll
-  for (int s = 0; s < SI; ++s) {
-    const int i = l + 64 * s - off;
-    if (i >= 0) {
-      const double v = zs[s] * sgn;
-      a.V[(size_t)i * n + j] = v;
-      a.Vt[(size_t)j * n + i] = v;
-    }
-  }
+  // the vector of T, normalised, as row j of Vt (contiguous); back-transformation, sign and the transposed copy: k_tri_back
+  const double sc = 1.0 / sqrt(znorm2);
+  for (int i = l; i < n; i += 64) a.Vt[(size_t)j * n + i] = zb[i] * sc;
+  if (!(muj > 0.0)) trouble = true;
   if (l == 0) { a.S[j] = 1.0 / muj; a.mu[j] = muj; }
-  }  // kBack
   TRI_STAMP(13);
   // ---- the last wave to finish checks that the eigenvalues are told apart and publishes the status
   __threadfence();
@@ -1217,36 +997,28 @@ __device__ __forceinline__ void tri_solve_body(const TriSolveIO& a) {
     // (hand X on as V), written anew by every solve launch
     a.sync[3] = (close || bad) ? 0 : 1;
     a.sync[4] = 0;
-    if (a.host_status) __hip_atomic_store(a.host_status, st, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_SYSTEM);
-    if (a.done_word) __hip_atomic_store(a.done_word, a.done_value, __ATOMIC_RELEASE, __HIP_MEMORY_SCOPE_AGENT);
   }
 }
-// Ranks above 64 (the back-transformation is k_tri_back's): the reflector blocks' T factors are nobody's input inside this launch, so the
-// workgroups behind the eigenpairs' — one wave each — are k_tri_wy's: one launch and its boundary less per decomposition.
+// The reflector blocks' T factors are nobody's input inside this launch (the back-transformation is k_tri_back's), so the workgroups
+// behind the eigenpairs' — one wave each — compute them: one launch and its boundary less per decomposition.
 template <int SI>
 __device__ __forceinline__ void tri_solve_or_wy(const TriSolveIO& a) {
   const int nwg = (a.n + 3) / 4;
-  if constexpr (SI > 1) {
-    if ((int)blockIdx.x >= nwg) {
-      if (threadIdx.x < 64) tri_wy_body<SI>(TriWyIO{a.n, a.beta, a.Hv, const_cast<double*>(a.wy), a.sync}, (int)blockIdx.x - nwg);
-      return;
-    }
+  if ((int)blockIdx.x >= nwg) {
+    if (threadIdx.x < 64) tri_wy_body<SI>(TriWyIO{a.n, a.beta, a.Hv, const_cast<double*>(a.wy), a.sync}, (int)blockIdx.x - nwg);
+    return;
   }
-  tri_solve_body<SI, SI == 1>(a);
+  tri_solve_body<SI>(a);
 }
-template <int SI>
-__global__ void __launch_bounds__(256) k_tri_solve(TriSolveIO a0, TriSolveIO a1) {
-  tri_solve_or_wy<SI>(blockIdx.y ? a1 : a0);  // (up to two decompositions side by side: the two ICP directions of a chain step)
-}
-struct TriSolveMany { TriSolveIO p[kTriMany]; };
-static_assert(sizeof(TriSolveMany) + 16 <= 4096, "the records of a launch must fit the kernel argument segment");
-template <int SI>
-__global__ void __launch_bounds__(256) k_tri_solve_many(TriSolveMany m, const int* __restrict__ skip_all) {
-  if (skip_all && skip_all[blockIdx.y] != 0) return;
+static_assert(sizeof(TriBatch<TriSolveIO, kTriMany>) + 16 <= 4096, "the records of a launch must fit the kernel argument segment");
+template <int CAP, int SI>
+__global__ void __launch_bounds__(256) k_tri_solve(TriBatch<TriSolveIO, CAP> m, const int* __restrict__ skip_all) {
+  const int q = tri_record<CAP>(blockIdx.y);
+  if (skip_all && skip_all[q] != 0) return;
 #ifdef ICP_TRI_SETPRIO
   __builtin_amdgcn_s_setprio(ICP_TRI_SETPRIO);
 #endif
-  const TriSolveIO a = m.p[blockIdx.y];
+  const TriSolveIO a = m.p[q];
   tri_solve_or_wy<SI>(a);
 }
 
@@ -1256,7 +1028,7 @@ __global__ void __launch_bounds__(256) k_tri_solve_many(TriSolveMany m, const in
 // index space of tridiagonalise, columns = eigenvectors; tile t, register g of lane l: row 16t + (l >> 4) + 4g, column l & 15) —
 // which is also the layout of the B operand of a product's k-step (B[k = l >> 4][j = l & 15]: register g IS k-step g).  Per block of
 // eight reflectors, last block first:  U = V_bᵀ Z (four instructions per tile, A = the reflectors' entries straight from Hv),
-// W = T_b U (two), Z −= V_b W (two per tile).  An eigenvector at a time (tri_solve_body<·, true>) a block is eight inner products, a
+// W = T_b U (two), Z −= V_b W (two per tile).  An eigenvector at a time (the form of rounds 3-4) a block is eight inner products, a
 // wave reduction and eight updates per vector — 2,700 cycles; here ≈ 80 matrix instructions for sixteen vectors.  With 30 decompositions
 // side by side the solve launch is the chip's throughput kernel (6,000 eigenpair waves, 510 µs); a third of that was this.
 // Then the canonical sign (largest-|.| component positive, the first among equals), X and its transpose.
@@ -1264,7 +1036,7 @@ typedef double tri_d4 __attribute__((ext_vector_type(4)));
 struct TriBackIO {
   int n;
   const double* Hv;   // [n][64·SI]
-  const double* wy;   // [ceil((n−2)/8)][64] T factors (k_tri_wy)
+  const double* wy;   // [ceil((n−2)/8)][64] T factors (tri_wy_body)
   double* X;          // [n][n] out: eigenvectors in columns
   double* Xt;         // [n][n] in: the tridiagonal matrix's eigenvectors in rows (the solve launch); out: the transpose of X
   int* status;        // status[0] = 2 if a vector is not finite
@@ -1441,16 +1213,14 @@ __device__ __forceinline__ void tri_back_body(const TriBackIO& a) {
       }
   }
 }
-template <int SI>
-__global__ void __launch_bounds__(256) k_tri_back(TriBackIO a0, TriBackIO a1) { tri_back_body<SI>(blockIdx.y ? a1 : a0); }
-struct TriBackMany { TriBackIO p[kTriMany]; };
-template <int SI>
-__global__ void __launch_bounds__(256) k_tri_back_many(TriBackMany m, const int* __restrict__ skip_all) {
-  if (skip_all && skip_all[blockIdx.y] != 0) return;
+template <int CAP, int SI>
+__global__ void __launch_bounds__(256) k_tri_back(TriBatch<TriBackIO, CAP> m, const int* __restrict__ skip_all) {
+  const int q = tri_record<CAP>(blockIdx.y);
+  if (skip_all && skip_all[q] != 0) return;
 #ifdef ICP_TRI_SETPRIO
   __builtin_amdgcn_s_setprio(ICP_TRI_SETPRIO);
 #endif
-  const TriBackIO a = m.p[blockIdx.y];
+  const TriBackIO a = m.p[q];
   tri_back_body<SI>(a);
 }
 
@@ -1513,41 +1283,18 @@ __device__ __forceinline__ void tri_gemm_body(int n, const TriGemm& g) {
     }
   }
 }
-__global__ void __launch_bounds__(64) k_tri_gemm(int n, TriGemm g0, TriGemm g1) {
-  const TriGemm g = blockIdx.z ? g1 : g0;
+// blockIdx.z = product: per_problem of them per decomposition (the first launch of the step carries two)
+static_assert(sizeof(TriBatch<TriGemm, 2 * kTriMany>) + 32 <= 4096, "the records of a launch must fit the kernel argument segment");
+template <int CAP>
+__global__ void __launch_bounds__(64) k_tri_gemm(int n, TriBatch<TriGemm, 2 * CAP> m, const int* __restrict__ skip_all, int per_problem) {
+  if (skip_all && skip_all[tri_record<CAP>(blockIdx.z / per_problem)] != 0) return;
+  const TriGemm g = m.p[blockIdx.z];
   tri_gemm_body(n, g);
 }
-struct TriGemmMany { TriGemm g[2 * kTriMany]; };  // blockIdx.z = product
-static_assert(sizeof(TriGemmMany) + 32 <= 4096, "the records of a launch must fit the kernel argument segment");
-__global__ void __launch_bounds__(64) k_tri_gemm_many(int n, TriGemmMany m, const int* __restrict__ skip_all, int per_problem) {
-  if (skip_all && skip_all[blockIdx.z / per_problem] != 0) return;
-  const TriGemm g = m.g[blockIdx.z];
-  tri_gemm_body(n, g);
-}
-__global__ void __launch_bounds__(256) k_tri_correction(int n, const double* __restrict__ S, const double* __restrict__ R, double* __restrict__ E,
-                                                        double* __restrict__ Sout, const int* __restrict__ skip) {
-  const int e = blockIdx.x * 256 + threadIdx.x;
-  if (e >= n * n) return;
-  if (skip && __hip_atomic_load(skip, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT) == 1) return;  // (S stays the solve launch's)
-  const int i = e / n, j = e - i * n;
-  const double rii = R[(size_t)i * n + i], rjj = R[(size_t)j * n + j];
-  const double mi = S[(size_t)i * n + i] / (1.0 - rii), mj = S[(size_t)j * n + j] / (1.0 - rjj);
-  double v;
-  if (i == j) {
-    v = 0.5 * rii;
-    Sout[i] = 1.0 / mi;
-  } else {
-    const double den = mj - mi;
-    v = fabs(den) > 1e-11 * (fabs(mi) + fabs(mj)) ? fma(mj, R[e], S[e]) / den : 0.5 * R[e];
-  }
-  E[e] = v;
-}
-struct TriCorrMany { const double* S[kTriMany]; const double* R[kTriMany]; double* E[kTriMany]; double* Sout[kTriMany]; const int* skip[kTriMany]; };
-__global__ void __launch_bounds__(256) k_tri_correction_many(int n, TriCorrMany m, const int* __restrict__ skip_all) {
-  const int e = blockIdx.x * 256 + threadIdx.x, q = blockIdx.y;
-  if (e >= n * n) return;
-  if (skip_all && skip_all[q] != 0) return;
-  if (m.skip[q] && __hip_atomic_load(m.skip[q], __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT) == 1) return;
+template <int CAP> struct TriCorrBatch { const double* S[CAP]; const double* R[CAP]; double* E[CAP]; double* Sout[CAP]; const int* skip[CAP]; };
+// entry e of record q's E (and, on the diagonal, the corrected 1/mu_i) from S = XᵀNX and R = I − XᵀX
+template <int CAP>
+__device__ __forceinline__ void tri_correction_body(int n, int e, const TriCorrBatch<CAP>& m, int q) {
   const double* __restrict__ S = m.S[q];
   const double* __restrict__ R = m.R[q];
   const int i = e / n, j = e - i * n;
@@ -1563,9 +1310,19 @@ __global__ void __launch_bounds__(256) k_tri_correction_many(int n, TriCorrMany 
   }
   m.E[q][e] = v;
 }
-struct TriDoneMany { const int* status[kTriMany]; int* host_status[kTriMany]; int* done_word[kTriMany]; int done_value[kTriMany]; };
-__global__ void k_tri_done_many(TriDoneMany m, const int* __restrict__ skip_all) {
-  const int q = blockIdx.x;
+template <int CAP>
+__global__ void __launch_bounds__(256) k_tri_correction(int n, TriCorrBatch<CAP> m, const int* __restrict__ skip_all) {
+  const int e = blockIdx.x * 256 + threadIdx.x, q = tri_record<CAP>(blockIdx.y);
+  if (e >= n * n) return;
+  if (skip_all && skip_all[q] != 0) return;
+  if (m.skip[q] && __hip_atomic_load(m.skip[q], __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT) == 1) return;  // (S stays the solve launch's)
+  tri_correction_body(n, e, m, q);
+}
+// the completion words of a sequence: the pinned copy of the status, then the word a consumer on another stream waits for
+template <int CAP> struct TriDoneBatch { const int* status[CAP]; int* host_status[CAP]; int* done_word[CAP]; int done_value[CAP]; };
+template <int CAP>
+__global__ void k_tri_done(TriDoneBatch<CAP> m, const int* __restrict__ skip_all) {
+  const int q = tri_record<CAP>(blockIdx.x);
   if (skip_all && skip_all[q] != 0) return;
   if (m.host_status[q]) __hip_atomic_store(m.host_status[q], m.status[q][0], __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_SYSTEM);
   if (m.done_word[q]) __hip_atomic_store(m.done_word[q], m.done_value[q], __ATOMIC_RELEASE, __HIP_MEMORY_SCOPE_AGENT);
@@ -1579,10 +1336,6 @@ __global__ void __launch_bounds__(256) k_assemble_many(int r, AssembleMany m, co
   const int i = e / r, j = e - i * r;
   const int hi = max(i, j), lo = min(i, j);
   m.M[q][e] = m.P[q][(size_t)hi * (r + 1) + lo] + (i == j ? 1.0 : 0.0);
-}
-__global__ void k_tri_done(const int* status, int* host_status, int* done_word, int done_value) {
-  if (host_status) __hip_atomic_store(host_status, status[0], __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_SYSTEM);
-  if (done_word) __hip_atomic_store(done_word, done_value, __ATOMIC_RELEASE, __HIP_MEMORY_SCOPE_AGENT);
 }
 
 }  // namespace tri

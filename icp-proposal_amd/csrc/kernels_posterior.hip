@@ -2247,145 +2247,127 @@ constexpr int kTriMaxRank = 256;  // = tri::kTriMaxN: four row slots of 64
 static size_t tri_work_doubles(int r) { return r <= kTriMaxRank ? 4 * (size_t)tri::kTriMaxN + 8 + (size_t)r * 256 : 0; }
 size_t eigen_work_doubles(int r) { return jacobi_work_doubles(r) + tri_work_doubles(r); }  // `work` of launch_posterior_eigen
 
-// Householder tridiagonalisation on one workgroup, then one wave per eigenpair (icp_tridiag.hpp)
+// Householder tridiagonalisation on one workgroup, then one wave per eigenpair (icp_tridiag.hpp): ranks 65..256
+// (developer switch ICP_EIGEN_TRIDIAG=0: the Jacobi kernels at these ranks, too)
 static bool tridiag_route(int r) {
   static const int forced = dev_env("ICP_EIGEN_TRIDIAG") ? std::atoi(dev_env("ICP_EIGEN_TRIDIAG")) : -1;
-  if (r < 3 || r > kTriMaxRank) return false;
-  return forced >= 0 ? forced != 0 : r > 64;
+  return r > 64 && r <= kTriMaxRank && forced != 0;
 }
-static void launch_eigen_big(hipStream_t st, int r, const double* M, const double* sqrt_lambda, const double* Vwarm, double* V, double* Vt,
-                             double* S, double* work, int* status, int* host_status, const int* gate);
-static void launch_eigen_tridiag(hipStream_t st, int r, const double* M, const double* sqrt_lambda, double* V, double* Vt, double* S, double* work,
-                                 int* status, int* host_status, int* done_word, int done_value, int part = 0) {
-  double* base = work + jacobi_work_doubles(r);
-  double *d = base, *e = base + tri::kTriMaxN, *beta = base + 2 * tri::kTriMaxN, *mu = base + 3 * tri::kTriMaxN;
-  int* sync = (int*)(base + 4 * tri::kTriMaxN);
-  double* Hv = base + 4 * tri::kTriMaxN + 8;
-  // the refinement step's matrices live where the Jacobi kernels' log would be (this route replaces them): N | X | Xt | T | S | R
-  const size_t rr = (size_t)r * r;
-  double *Nm = work, *X = work + rr, *Xt = work + 2 * rr, *T = work + 3 * rr, *Sm = work + 4 * rr, *R = work + 5 * rr;
-  tri::TridiagIO ti{r, M, sqrt_lambda, d, e, beta, Hv, Nm};
-  // (the reflector blocks' T factors live where the refinement's R will be: written behind the solve)
-  tri::TriSolveIO so{r, d, e, beta, Hv, X, Xt, S, mu, R, sync, status, nullptr, nullptr, 0};
-  const tri::TriWyIO wyio{r, beta, Hv, R, sync};
-  const int nwg = (r + 3) / 4, nwy = (r - 2 + tri::kWyBlock - 1) / tri::kWyBlock;
-  if (part != 2) {  // the reduction
-    if (r <= 64) hipLaunchKernelGGL((tri::k_tridiag<4, 1, 16, 0>), dim3(1), dim3(256), 0, st, ti);
-    else if (r <= 128) hipLaunchKernelGGL((tri::k_tridiag<4, 2, 32, 0>), dim3(1), dim3(256), 0, st, ti);
-    else if (r <= 192) hipLaunchKernelGGL((tri::k_tridiag<8, 3, 24, 0>), dim3(1), dim3(512), 0, st, ti);
-    else if (r <= 200) hipLaunchKernelGGL((tri::k_tridiag<8, 4, 25, 7>), dim3(1), dim3(512), 0, st, ti);
-    else if (r <= 208) hipLaunchKernelGGL((tri::k_tridiag<8, 4, 26, 6>), dim3(1), dim3(512), 0, st, ti);
-    else hipLaunchKernelGGL((tri::k_tridiag<8, 4, 32, 0>), dim3(1), dim3(512), 0, st, ti);
+bool eigen_tridiag_many_supported(int r) { return r > 64 && r <= kTriMaxRank; }
+
+// The route's areas of a decomposition's `work`.  Behind the Jacobi kernels' part: d | e | beta | mu | sync words | reflectors.  At its
+// head, where the Jacobi kernels' log would be (this route replaces them), the refinement step's matrices N | X | Xt | T | S | R — the
+// reflector blocks' T factors live where R will be: R is written behind the solve.
+struct TriWork {
+  double *d, *e, *beta, *mu;
+  int* sync;
+  double* Hv;
+  double *N, *X, *Xt, *T, *S, *R;
+  TriWork(double* work, int r) {
+    double* base = work + jacobi_work_doubles(r);
+    d = base; e = base + tri::kTriMaxN; beta = base + 2 * tri::kTriMaxN; mu = base + 3 * tri::kTriMaxN;
+    sync = (int*)(base + 4 * tri::kTriMaxN);
+    Hv = base + 4 * tri::kTriMaxN + 8;
+    const size_t rr = (size_t)r * r;
+    N = work; X = work + rr; Xt = work + 2 * rr; T = work + 3 * rr; S = work + 4 * rr; R = work + 5 * rr;
   }
-  if (part == 1) return;
-  // (ranks above 64: the T factors by the solve launch's own trailing workgroups — tri_solve_or_wy)
-  if (r <= 64) hipLaunchKernelGGL(tri::k_tri_wy<1>, dim3(nwy), dim3(64), 0, st, wyio, wyio);
-  if (r <= 64) hipLaunchKernelGGL(tri::k_tri_solve<1>, dim3(nwg), dim3(256), tri::tri_solve_lds_bytes(r), st, so, so);
-  else if (r <= 128) hipLaunchKernelGGL(tri::k_tri_solve<2>, dim3(nwg + nwy), dim3(256), tri::tri_solve_lds_bytes(r), st, so, so);
-  else if (r <= 192) hipLaunchKernelGGL(tri::k_tri_solve<3>, dim3(nwg + nwy), dim3(256), tri::tri_solve_lds_bytes(r), st, so, so);
-  else {
-    static bool lds_set = false;  // (above rank 201 the launch's dynamic LDS passes 48 KiB: 61 KiB at rank 256)
-    set_dyn_lds_once((const void*)tri::k_tri_solve<4>, tri::tri_solve_lds_bytes(tri::kTriMaxN), &lds_set);
-    hipLaunchKernelGGL(tri::k_tri_solve<4>, dim3(nwg + nwy), dim3(256), tri::tri_solve_lds_bytes(r), st, so, so);
-  }
-  if (r > 64) {  // (ranks above 64: the back-transformation is a launch of its own, sixteen eigenvectors per wave on the matrix cores)
-    const tri::TriBackIO bk{r, Hv, R, X, Xt, status, sync};
-    const int nb16 = (r + 15) / 16;
-    if (r <= 128) hipLaunchKernelGGL(tri::k_tri_back<2>, dim3(nb16), dim3(256), 0, st, bk, bk);
-    else if (r <= 192) hipLaunchKernelGGL(tri::k_tri_back<3>, dim3(nb16), dim3(256), 0, st, bk, bk);
-    else hipLaunchKernelGGL(tri::k_tri_back<4>, dim3(nb16), dim3(256), 0, st, bk, bk);
-  }
-  // one refinement step: T = N·X and R = I − XᵀX, S = XᵀT, E, then V = X + X·E (and Vt)
-  const int nt = (r + 15) / 16;
-  const int* skip = sync + 3;  // (written by the solve launch: 1 = every gap wide enough, the refinement's launches return at once)
-  const tri::TriGemm gT{Nm, X, T, 0, nullptr, nullptr, skip}, gR{X, X, R, 1, nullptr, nullptr, skip}, gS{X, T, Sm, 0, nullptr, nullptr, skip};
-  hipLaunchKernelGGL(tri::k_tri_gemm, dim3(nt, nt, 2), dim3(64), 0, st, r, gT, gR);
-  hipLaunchKernelGGL(tri::k_tri_gemm, dim3(nt, nt, 1), dim3(64), 0, st, r, gS, gS);
-  hipLaunchKernelGGL(tri::k_tri_correction, dim3((unsigned)((rr + 255) / 256)), dim3(256), 0, st, r, (const double*)Sm, (const double*)R, T, S, skip);
-  const tri::TriGemm gV{Xt, T, V, 2, X, Vt, skip};
-  hipLaunchKernelGGL(tri::k_tri_gemm, dim3(nt, nt, 1), dim3(64), 0, st, r, gV, gV);
-  // eigenvalues that multisection could not tell apart (status 2: a spectrum with (near-)multiple eigenvalues, e.g. a posterior without
-  // correspondences over a model with equal variances): the Jacobi iteration takes over, cold, in the same stream — its launches
-  // return at once otherwise
-  if (r > 64 && r <= kBigMaxRank) launch_eigen_big(st, r, M, sqrt_lambda, nullptr, V, Vt, S, work, status, nullptr, status);
-  else if (r > kBigMaxRank)  // (matrix behind L2: `work`'s head, whose refinement matrices a failed multisection has no use for)
-    hipLaunchKernelGGL(k_posterior_eigen, dim3(1), dim3(1024), 0, st, r, M, sqrt_lambda, (const double*)nullptr, V, Vt, S, work, status, 0, 0,
-                       (const int*)status);
-  if (host_status || done_word) hipLaunchKernelGGL(tri::k_tri_done, dim3(1), dim3(1), 0, st, (const int*)status, host_status, done_word, done_value);
+};
+
+// rank -> the reduction's shape <waves, row slots, column slots per wave, empty column slots>; rank -> row slots of solve and back
+template <int NW_, int SI_, int NT_, int TOFF_> struct TriShape { static constexpr int NW = NW_, SI = SI_, NT = NT_, TOFF = TOFF_; };
+template <class F> static void tri_reduction_shape(int r, F&& f) {
+  if (r <= 128) f(TriShape<4, 2, 32, 0>{});
+  else if (r <= 192) f(TriShape<8, 3, 24, 0>{});
+  else if (r <= 200) f(TriShape<8, 4, 25, 7>{});
+  else if (r <= 208) f(TriShape<8, 4, 26, 6>{});
+  else f(TriShape<8, 4, 32, 0>{});
+}
+template <class F> static void tri_row_slots(int r, F&& f) {
+  if (r <= 128) f(tri::Tag<2>{});
+  else if (r <= 192) f(tri::Tag<3>{});
+  else f(tri::Tag<4>{});
 }
 
-// The same route for n decompositions side by side (the chains of a wide step): every launch of the sequence takes all of them —
-// the one-workgroup reductions run on n CUs at once.  No gated Jacobi fall-back in the sequence (see icp_kernels.hpp).
-bool eigen_tridiag_many_supported(int r) { return r > 64 && r <= kTriMaxRank; }
+// the completion launch of a sequence: pinned status copies and completion words
+template <int CAP>
+static void launch_tri_done(hipStream_t st, int n, const EigenRequest* rq, const int* skip) {
+  tri::TriDoneBatch<CAP> dm{};
+  bool any_done = false;  // (nobody to tell — the on-device loop reads the status words on the device —: no launch)
+  for (int q = 0; q < n; ++q) {
+    dm.status[q] = rq[q].status; dm.host_status[q] = rq[q].host_status; dm.done_word[q] = rq[q].done_word; dm.done_value[q] = rq[q].done_value;
+    any_done = any_done || dm.host_status[q] || dm.done_word[q];
+  }
+  if (any_done) hipLaunchKernelGGL(tri::k_tri_done<CAP>, dim3(n), dim3(1), 0, st, dm, skip);
+}
+// The launch sequence for n <= CAP decompositions of rank 65..256 side by side: every launch takes all of them — the one-workgroup
+// reductions run on n CUs at once.  parts (optional): M = I + the summed partial first.  skip (optional, device): requests to leave
+// alone.  part: 0 = everything, 1 = assembly and reduction only, 2 = what follows.  completion = false leaves the completion launch
+// to the caller, who has launches of its own to put before it.
+template <int CAP>
+static void launch_tri_sequence(hipStream_t st, int r, int n, const EigenRequest* rq, const double* const* parts, const int* skip, int part,
+                                bool completion) {
+  // (test-hooks build, ICP_TEST_TRI_REFINE_ALWAYS=1: the refinement step whatever the gaps are — it is the rare path otherwise)
+  static const bool refine_always = dev_env("ICP_TEST_TRI_REFINE_ALWAYS") && std::atoi(dev_env("ICP_TEST_TRI_REFINE_ALWAYS")) != 0;
+  const size_t rr = (size_t)r * r;
+  const int nwg = (r + 3) / 4, nt = (r + 15) / 16, nwy = (r - 2 + tri::kWyBlock - 1) / tri::kWyBlock;
+  tri::TriBatch<tri::TridiagIO, CAP> tm{};
+  tri::TriBatch<tri::TriSolveIO, CAP> sm{};
+  tri::TriBatch<tri::TriBackIO, CAP> bm{};
+  tri::TriBatch<tri::TriGemm, 2 * CAP> g1{}, g2{}, g3{};
+  tri::TriCorrBatch<CAP> cm{};
+  tri::AssembleMany am{};
+  bool assemble = false;
+  for (int q = 0; q < n; ++q) {
+    const TriWork w(rq[q].work, r);
+    tm.p[q] = tri::TridiagIO{r, rq[q].M, rq[q].sqrt_lambda, w.d, w.e, w.beta, w.Hv, w.N};
+    sm.p[q] = tri::TriSolveIO{r, w.d, w.e, w.beta, w.Hv, w.X, w.Xt, rq[q].S, w.mu, w.R, w.sync, rq[q].status};
+    bm.p[q] = tri::TriBackIO{r, w.Hv, w.R, w.X, w.Xt, rq[q].status, w.sync};
+    // one refinement step: T = N·X and R = I − XᵀX, S = XᵀT, E, then V = X + X·E (and Vt).  sync[3], written by the solve launch:
+    // 1 = every gap wide enough, the step's launches return at once (the last one handing X on as V)
+    const int* wide = refine_always ? nullptr : w.sync + 3;
+    g1.p[2 * q] = tri::TriGemm{w.N, w.X, w.T, 0, nullptr, nullptr, wide};
+    g1.p[2 * q + 1] = tri::TriGemm{w.X, w.X, w.R, 1, nullptr, nullptr, wide};
+    g2.p[q] = tri::TriGemm{w.X, w.T, w.S, 0, nullptr, nullptr, wide};
+    cm.S[q] = w.S; cm.R[q] = w.R; cm.E[q] = w.T; cm.Sout[q] = rq[q].S; cm.skip[q] = wide;
+    g3.p[q] = tri::TriGemm{w.Xt, w.T, rq[q].V, 2, w.X, rq[q].Vt, wide};
+    am.P[q] = parts ? parts[q] : nullptr;
+    am.M[q] = const_cast<double*>(rq[q].M);
+    assemble = assemble || am.P[q] != nullptr;
+  }
+  if (part != 2) {  // the reduction (part 1 of a split sequence: the long one-workgroup launch, before anybody knows whom to skip)
+    if (assemble) hipLaunchKernelGGL(tri::k_assemble_many, dim3((unsigned)((rr + 255) / 256), n), dim3(256), 0, st, r, am, skip);
+    tri_reduction_shape(r, [&](auto shape) {
+      using S = decltype(shape);
+      hipLaunchKernelGGL((tri::k_tridiag<CAP, S::NW, S::SI, S::NT, S::TOFF>), dim3(n), dim3(S::NW * 64), 0, st, tm, skip);
+    });
+  }
+  if (part == 1) return;
+  tri_row_slots(r, [&](auto si) {
+    constexpr int SI = decltype(si)::value;
+    if constexpr (SI == 4) {  // (above rank 201 the solve launch's dynamic LDS passes 48 KiB: 61 KiB at rank 256)
+      static bool lds_set = false;
+      set_dyn_lds_once((const void*)tri::k_tri_solve<CAP, SI>, tri::tri_solve_lds_bytes(tri::kTriMaxN), &lds_set);
+    }
+    // (the reflector blocks' T factors: the solve launch's trailing workgroups — tri_solve_or_wy)
+    hipLaunchKernelGGL((tri::k_tri_solve<CAP, SI>), dim3(nwg + nwy, n), dim3(256), tri::tri_solve_lds_bytes(r), st, sm, skip);
+    hipLaunchKernelGGL((tri::k_tri_back<CAP, SI>), dim3(nt, n), dim3(256), 0, st, bm, skip);
+  });
+  hipLaunchKernelGGL(tri::k_tri_gemm<CAP>, dim3(nt, nt, 2 * n), dim3(64), 0, st, r, g1, skip, 2);
+  hipLaunchKernelGGL(tri::k_tri_gemm<CAP>, dim3(nt, nt, n), dim3(64), 0, st, r, g2, skip, 1);
+  hipLaunchKernelGGL(tri::k_tri_correction<CAP>, dim3((unsigned)((rr + 255) / 256), n), dim3(256), 0, st, r, cm, skip);
+  hipLaunchKernelGGL(tri::k_tri_gemm<CAP>, dim3(nt, nt, n), dim3(64), 0, st, r, g3, skip, 1);
+  if (completion) launch_tri_done<CAP>(st, n, rq, skip);
+}
+
+// Any number of decompositions (the chains of a wide step), kTriMany to a sequence.  No gated Jacobi fall-back behind them (see
+// icp_kernels.hpp).
 void launch_posterior_eigen_tridiag_many(hipStream_t st, int r, int n_all, const EigenRequest* rq_all, const double* const* parts_all,
                                          const int* skip_all, int part) {
-  const size_t rr = (size_t)r * r;
-  const int nwg = (r + 3) / 4, nt = (r + 15) / 16;
   for (int q0 = 0; q0 < n_all; q0 += tri::kTriMany) {
     const int n = std::min(tri::kTriMany, n_all - q0);
-    const EigenRequest* rq = rq_all + q0;
-    const int* skip = skip_all ? skip_all + q0 : nullptr;
-    tri::TridiagMany tm{};
-    tri::TriSolveMany sm{};
-    tri::TriBackMany bm{};
-    tri::TriGemmMany g1{}, g2{}, g3{};
-    tri::TriCorrMany cm{};
-    tri::TriDoneMany dm{};
-    tri::AssembleMany am{};
-    bool assemble = false;
-    for (int q = 0; q < n; ++q) {
-      double* work = rq[q].work;
-      double* base = work + jacobi_work_doubles(r);
-      double *d = base, *e = base + tri::kTriMaxN, *beta = base + 2 * tri::kTriMaxN, *mu = base + 3 * tri::kTriMaxN;
-      int* sync = (int*)(base + 4 * tri::kTriMaxN);
-      double* Hv = base + 4 * tri::kTriMaxN + 8;
-      double *Nm = work, *X = work + rr, *Xt = work + 2 * rr, *T = work + 3 * rr, *Sm = work + 4 * rr, *R = work + 5 * rr;
-      const double* sl = rq[q].sqrt_lambda;
-      tm.p[q] = tri::TridiagIO{r, rq[q].M, sl, d, e, beta, Hv, Nm};
-      sm.p[q] = tri::TriSolveIO{r, d, e, beta, Hv, X, Xt, rq[q].S, mu, R, sync, rq[q].status, nullptr, nullptr, 0};
-      bm.p[q] = tri::TriBackIO{r, Hv, R, X, Xt, rq[q].status, sync};
-      // (test-hooks build, ICP_TEST_TRI_REFINE_ALWAYS=1: the refinement step whatever the gaps are — it is the rare path otherwise)
-      static const bool refine_always = dev_env("ICP_TEST_TRI_REFINE_ALWAYS") && std::atoi(dev_env("ICP_TEST_TRI_REFINE_ALWAYS")) != 0;
-      const int* skip = refine_always ? nullptr : sync + 3;
-      g1.g[2 * q] = tri::TriGemm{Nm, X, T, 0, nullptr, nullptr, skip};
-      g1.g[2 * q + 1] = tri::TriGemm{X, X, R, 1, nullptr, nullptr, skip};
-      g2.g[q] = tri::TriGemm{X, T, Sm, 0, nullptr, nullptr, skip};
-      cm.S[q] = Sm; cm.R[q] = R; cm.E[q] = T; cm.Sout[q] = rq[q].S; cm.skip[q] = skip;
-      g3.g[q] = tri::TriGemm{Xt, T, rq[q].V, 2, X, rq[q].Vt, skip};
-      dm.status[q] = rq[q].status; dm.host_status[q] = rq[q].host_status; dm.done_word[q] = rq[q].done_word; dm.done_value[q] = rq[q].done_value;
-      am.P[q] = parts_all ? parts_all[q0 + q] : nullptr;
-      am.M[q] = const_cast<double*>(rq[q].M);
-      assemble = assemble || am.P[q] != nullptr;
-    }
     ProfScope _ps(st, KID_EIGEN);
-    if (part != 2) {  // the reduction (part 1 of a split sequence: the long one-workgroup launch, before anybody knows whom to skip)
-      if (assemble) hipLaunchKernelGGL(tri::k_assemble_many, dim3((unsigned)((rr + 255) / 256), n), dim3(256), 0, st, r, am, skip);
-      if (r <= 128) hipLaunchKernelGGL((tri::k_tridiag_many<4, 2, 32, 0>), dim3(n), dim3(256), 0, st, tm, skip);
-      else if (r <= 192) hipLaunchKernelGGL((tri::k_tridiag_many<8, 3, 24, 0>), dim3(n), dim3(512), 0, st, tm, skip);
-      else if (r <= 200) hipLaunchKernelGGL((tri::k_tridiag_many<8, 4, 25, 7>), dim3(n), dim3(512), 0, st, tm, skip);
-      else if (r <= 208) hipLaunchKernelGGL((tri::k_tridiag_many<8, 4, 26, 6>), dim3(n), dim3(512), 0, st, tm, skip);
-      else hipLaunchKernelGGL((tri::k_tridiag_many<8, 4, 32, 0>), dim3(n), dim3(512), 0, st, tm, skip);
-    }
-    if (part == 1) continue;
-    const int nwy = (r - 2 + tri::kWyBlock - 1) / tri::kWyBlock;
-    // (the reflector blocks' T factors: the solve launch's trailing workgroups — tri_solve_or_wy)
-    if (r <= 128) hipLaunchKernelGGL(tri::k_tri_solve_many<2>, dim3(nwg + nwy, n), dim3(256), tri::tri_solve_lds_bytes(r), st, sm, skip);
-    else if (r <= 192) hipLaunchKernelGGL(tri::k_tri_solve_many<3>, dim3(nwg + nwy, n), dim3(256), tri::tri_solve_lds_bytes(r), st, sm, skip);
-    else {
-      static bool lds_set = false;
-      set_dyn_lds_once((const void*)tri::k_tri_solve_many<4>, tri::tri_solve_lds_bytes(tri::kTriMaxN), &lds_set);
-      hipLaunchKernelGGL(tri::k_tri_solve_many<4>, dim3(nwg + nwy, n), dim3(256), tri::tri_solve_lds_bytes(r), st, sm, skip);
-    }
-    if (r <= 128) hipLaunchKernelGGL(tri::k_tri_back_many<2>, dim3(nt, n), dim3(256), 0, st, bm, skip);
-    else if (r <= 192) hipLaunchKernelGGL(tri::k_tri_back_many<3>, dim3(nt, n), dim3(256), 0, st, bm, skip);
-    else hipLaunchKernelGGL(tri::k_tri_back_many<4>, dim3(nt, n), dim3(256), 0, st, bm, skip);
-    hipLaunchKernelGGL(tri::k_tri_gemm_many, dim3(nt, nt, 2 * n), dim3(64), 0, st, r, g1, skip, 2);
-    hipLaunchKernelGGL(tri::k_tri_gemm_many, dim3(nt, nt, n), dim3(64), 0, st, r, g2, skip, 1);
-    hipLaunchKernelGGL(tri::k_tri_correction_many, dim3((unsigned)((rr + 255) / 256), n), dim3(256), 0, st, r, cm, skip);
-    hipLaunchKernelGGL(tri::k_tri_gemm_many, dim3(nt, nt, n), dim3(64), 0, st, r, g3, skip, 1);
-    bool any_done = false;  // (nobody to tell — the on-device loop reads the status words on the device —: no launch)
-    for (int q = 0; q < n; ++q) any_done = any_done || dm.host_status[q] || dm.done_word[q];
-    if (any_done) hipLaunchKernelGGL(tri::k_tri_done_many, dim3(n), dim3(1), 0, st, dm, skip);
+    if (n == 1) launch_tri_sequence<tri::kTriOne>(st, r, n, rq_all + q0, parts_all ? parts_all + q0 : nullptr, skip_all ? skip_all + q0 : nullptr, part, true);
+    else launch_tri_sequence<tri::kTriMany>(st, r, n, rq_all + q0, parts_all ? parts_all + q0 : nullptr, skip_all ? skip_all + q0 : nullptr, part, true);
   }
 }
 
@@ -2595,50 +2577,9 @@ void launch_root_batch(hipStream_t st, int r, int n, const Batch& batch) {
 }
 }  // namespace
 
-// ranks <= 64 by the tridiagonal route: one launch reduces (a workgroup per decomposition, with the front end of a decomposition
-// enqueued ahead of its input), one solves (a wave per eigenpair); no refinement step (gaps at these ranks leave the vectors
-// orthogonal to 1e-13), completion words from the solve launch's last wave
-static void launch_eigen_tridiag_small(hipStream_t st, int r, const double* sqrt_lambda, int n, const EigenRequest* rq) {
-  tri::TriSmallBatch b{};
-  b.r = r;
-  tri::TriSolveIO so[2] = {};
-  tri::TriWyIO wy[2] = {};
-  for (int i = 0; i < n; ++i) {
-    double* base = rq[i].work + jacobi_work_doubles(r);
-    double *d = base, *e = base + tri::kTriMaxN, *beta = base + 2 * tri::kTriMaxN, *mu = base + 3 * tri::kTriMaxN;
-    int* sync = (int*)(base + 4 * tri::kTriMaxN);
-    double* Hv = base + 4 * tri::kTriMaxN + 8;
-    const EigenSpec* sp = rq[i].spec;
-    tri::TriSmallProblem& p = b.p[i];
-    p.M = rq[i].M;
-    p.splits = sp ? sp->splits : 0;
-    p.ready = sp ? sp->ready : nullptr;
-    p.ready_seq = sp ? sp->ready_seq : 0;
-    p.cancel = sp ? sp->cancel : nullptr;
-    p.seq = sp ? sp->seq : 0;
-    p.sqrt_lambda = rq[i].sqrt_lambda ? rq[i].sqrt_lambda : sqrt_lambda;
-    p.out = tri::TridiagIO{r, nullptr, nullptr, d, e, beta, Hv, nullptr};
-    p.sync = sync;
-    // (the reflector blocks' T factors: at the head of `work`, the Jacobi kernels' area, which this route leaves alone)
-    so[i] = tri::TriSolveIO{r, d, e, beta, Hv, rq[i].V, rq[i].Vt, rq[i].S, mu, rq[i].work, sync, rq[i].status, rq[i].host_status, rq[i].done_word,
-                            rq[i].done_value};
-    wy[i] = tri::TriWyIO{r, beta, Hv, rq[i].work, sync};
-  }
-  if (n == 1) { b.p[1] = b.p[0]; so[1] = so[0]; wy[1] = wy[0]; }
-  ProfScope _ps(st, KID_EIGEN);
-  hipLaunchKernelGGL(tri::k_tridiag_small, dim3(n), dim3(256), 0, st, b);
-  hipLaunchKernelGGL(tri::k_tri_wy<1>, dim3((r - 2 + tri::kWyBlock - 1) / tri::kWyBlock, n), dim3(64), 0, st, wy[0], wy[1]);
-  hipLaunchKernelGGL(tri::k_tri_solve<1>, dim3((r + 3) / 4, n), dim3(256), tri::tri_solve_lds_bytes(r), st, so[0], so[1]);
-}
-
 bool launch_posterior_eigen_pair(hipStream_t st, int r, const double* sqrt_lambda, int n, const EigenRequest* rq) {
   static const bool force_generic = dev_env("ICP_EIGEN_GENERIC") != nullptr;
   if (!(r >= 3 && r <= 64 && !force_generic) || n < 1 || n > 2) return false;
-  // The direct route at these ranks is a measured alternative, not the default: from input to completion word its two
-  // launches take ≈ 110 µs whatever the state, the warm-started iteration ≈ 100 even at four sweeps (70 at two); and without the
-  // refinement step its eigenvectors of close eigenvalues are a little further from the oracle's than the iteration's (femur-50
-  // golden proposals: 1.4e-7 against a tolerance of 1.2e-7).  Requests ask for it (EigenRequest::direct) under developer switches only.
-  static const int forced = dev_env("ICP_EIGEN_TRIDIAG") ? std::atoi(dev_env("ICP_EIGEN_TRIDIAG")) : -1;
   if (rq[0].root) {  // the Cholesky-root sampler (icp_proposal_set_sampler): no decomposition at all
     RootBatch2 b{};
     b.n = n;
@@ -2646,11 +2587,7 @@ bool launch_posterior_eigen_pair(hipStream_t st, int r, const double* sqrt_lambd
     launch_root_batch(st, r, n, b);
     return true;
   }
-  bool direct = false;
-  for (int i = 0; i < n; ++i) direct = direct || rq[i].direct;
-  if (forced >= 0) direct = forced != 0;
-  if (direct) launch_eigen_tridiag_small(st, r, sqrt_lambda, n, rq);
-  else launch_eigen_rr<2>(st, r, sqrt_lambda, n, rq);
+  launch_eigen_rr<2>(st, r, sqrt_lambda, n, rq);  // (the warm-started iteration; a direct route at these ranks was measured and lost: DESIGN.md §11)
   return true;
 }
 
@@ -2689,20 +2626,29 @@ int launch_posterior_eigen_many(hipStream_t st, int r, int n, const EigenRequest
 
 void launch_posterior_eigen(hipStream_t st, int r, const double* M, const double* sqrt_lambda, const double* Vwarm, double* V,
                             double* Vt, double* S, double* work, int* status, const EigenSpec* spec, int* host_status, int part) {
-  if (tridiag_route(r) && spec == nullptr) {
+  if (tridiag_route(r)) {
+    if (spec != nullptr) {  // (the route takes no spec; such a call is not split either)
+      if (part == 2) return;
+      part = 0;
+    }
+    const EigenRequest rq{M, nullptr, V, Vt, S, work, status, nullptr, host_status, nullptr, 0, sqrt_lambda};
     ProfScope _ps(st, KID_EIGEN);
-    launch_eigen_tridiag(st, r, M, sqrt_lambda, V, Vt, S, work, status, host_status, nullptr, 0, part);
+    launch_tri_sequence<tri::kTriOne>(st, r, 1, &rq, nullptr, nullptr, part, false);
+    if (part == 1) return;
+    // eigenvalues that multisection could not tell apart (status 2: a spectrum with (near-)multiple eigenvalues, e.g. a posterior without
+    // correspondences over a model with equal variances): the Jacobi iteration takes over, cold, in the same stream — its launches
+    // return at once otherwise — on the matrix the reduction left at the head of `work`
+    if (r <= kBigMaxRank) launch_eigen_big(st, r, M, sqrt_lambda, nullptr, V, Vt, S, work, status, nullptr, status);
+    else  // (matrix behind L2: `work`'s head, whose refinement matrices a failed multisection has no use for)
+      hipLaunchKernelGGL(k_posterior_eigen, dim3(1), dim3(1024), 0, st, r, M, sqrt_lambda, (const double*)nullptr, V, Vt, S, work, status, 0, 0,
+                         (const int*)status);
+    launch_tri_done<tri::kTriOne>(st, 1, &rq, nullptr);
     return;
   }
   if (part == 2) return;  // (the other routes are not split: part 1 has issued all of them)
   {
     const EigenRequest rq{M, Vwarm, V, Vt, S, work, status, spec, host_status, nullptr, 0};
     if (launch_posterior_eigen_pair(st, r, sqrt_lambda, 1, &rq)) return;
-  }
-  if (tridiag_route(r)) {
-    ProfScope _ps(st, KID_EIGEN);
-    launch_eigen_tridiag(st, r, M, sqrt_lambda, V, Vt, S, work, status, host_status, nullptr, 0);
-    return;
   }
   if (r > 64 && r <= kBigMaxRank) {  // in-place parallel Jacobi, packed triangle in one CU's LDS + replay workgroups
     ProfScope _ps(st, KID_EIGEN);
