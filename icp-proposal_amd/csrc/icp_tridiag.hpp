@@ -854,6 +854,7 @@ __device__ __forceinline__ void tri_solve_body(const TriSolveIO& a) {
   double lam = 0.5 * (lo + hi);
   double znorm2 = 1.0;
   bool trouble = false;
+  int rt_prev = 0;
   for (int round = 0; round < kTriRounds; ++round) {
     if (l < 2) {
       const int dir = l;
@@ -913,7 +914,12 @@ __device__ __forceinline__ void tri_solve_body(const TriSolveIO& a) {
       const int oi = __shfl_xor(ibest, o, 64);
       if (og < gbest || (og == gbest && oi < ibest)) { gbest = og; ibest = oi; }
     }
+    // (a row the matrix does not couple to its neighbours — e = 0: a posterior without correspondences is diagonal — whose entry the
+    // first round's correction has made λ itself: its γ is all but zero, 1e-280-ish by the floor under e², and stays the twist; with
+    // its neighbours at equal distances on both sides the recurrence gives the next row an EXACT zero, which would win the search)
+    if (round > 0 && fabs((Dq[rt_prev] + Dq[n + rt_prev]) - (ds[rt_prev] - lam)) < 1e-200) ibest = rt_prev;
     const int rt = ibest;
+    rt_prev = rt;
     const double gamma = (Dq[rt] + Dq[n + rt]) - (ds[rt] - lam);
     TRI_STAMP(32);
     // z_rt = 1; above the twist z_i = −(e_i / D⁺_i)·z_{i+1}, below it z_i = −(e_{i−1} / D⁻_i)·z_{i−1}: lane l takes rows SI·l .. SI·l + SI − 1
@@ -1305,8 +1311,12 @@ __device__ __forceinline__ void tri_correction_body(int n, int e, const TriCorrB
     v = 0.5 * rii;
     m.Sout[q][i] = 1.0 / mi;
   } else {
+    // S as the product leaves it is symmetric only to rounding, eps·‖N‖, and E_ij + E_ji = R_ij + (S_ij − S_ji)/(mu_j − mu_i): across a
+    // gap of 3e-8·‖N‖ the difference cost the orthogonality the step is there for (2e-9 left, as without the step; on a spectrum graded
+    // over six decades 3e-10, thirty times what the step was handed).  Both entries take the mean of the two.
+    const double sij = 0.5 * (S[e] + S[(size_t)j * n + i]);
     const double den = mj - mi;
-    v = fabs(den) > 1e-11 * (fabs(mi) + fabs(mj)) ? fma(mj, R[e], S[e]) / den : 0.5 * R[e];
+    v = fabs(den) > 1e-11 * (fabs(mi) + fabs(mj)) ? fma(mj, R[e], sij) / den : 0.5 * R[e];
   }
   m.E[q][e] = v;
 }

@@ -142,8 +142,10 @@ def test_synthetic_ranks_above_201_on_the_wide_step(pkg, oracle, rank):
 
 def test_refinement_step_of_many_decompositions_a_launch(pkg):
     """The refinement launches behind the back-transformation (Ogita-Aishima, icp_tridiag.hpp) return at once unless two eigenvalues
-    of a posterior are closer than kTriRefineGap — never, for these models.  Test-hooks build, ICP_TEST_TRI_REFINE_ALWAYS=1: the
-    on-device loop of the femur-200 model with the step taken by every decomposition of every launch, against the oracle as above."""
+    of a posterior are closer than kTriRefineGap — which these models' posteriors are not: here the step runs on vectors it has
+    nothing to correct in (tests/test_gpu_eigen_spectra.py is where it runs on gaps that need it).  Test-hooks build,
+    ICP_TEST_TRI_REFINE_ALWAYS=1: the on-device loop of the femur-200 model with the step taken by every decomposition of every
+    launch, against the oracle as above."""
     hooks = os.path.join(ROOT, "icp-proposal_amd", "libicp_proposal_amd_testhooks.so")
     assert os.path.exists(hooks), "build the test-hooks library (python -c 'import __graft_entry__ as g; g.build()')"
     done = subprocess.run([sys.executable, "-m", "pytest", os.path.abspath(__file__) + "::test_femur200_on_device_loop_matches_oracle", "-x", "-q", "-m", "gpu"],
