@@ -813,6 +813,35 @@ def dice_coefficient(ctx: IcpContext, theta, samples: int = 10000, seed: int = 1
     return float(m["dice"][0])
 
 
+def log_values(evaluators, thetas, return_aux: bool = False) -> dict:
+    """The log values of many states under many evaluators in one call (icp_evaluator_log_values_many): item b is
+    evaluators[b].logValue(thetas[b], return_aux=True) of a fresh evaluator bit for bit — re-scoring a chain's log under another
+    likelihood, or under every named evaluator as the reference's logger does (JSONAcceptRejectLogger.scala:84-106).  `evaluators`:
+    one evaluator or one per item; they may repeat, differ in kind, mode and parameters and belong to contexts of different targets
+    (one device, one model).  `thetas`: [n_items, 10 + rank].  Returns {"value": [n], "aux": [n, 4] (None without return_aux),
+    "status": [n]}: status 0, or -5 for an item whose boundary-aware evaluator dropped every point (its value is NaN); any other
+    per-item failure raises.  The evaluators and their chains are left as they were."""
+    th = _f64(thetas)
+    if th.ndim == 1:
+        th = th[None, :]
+    if th.ndim != 2:
+        raise ValueError("thetas must be [n_items, 10 + rank]")
+    n = th.shape[0]
+    evs = _per_item(evaluators, n, what="evaluator")
+    r = evs[0].ctx.rank
+    if th.shape[1] != 10 + r or any(e.ctx.rank != r for e in evs):
+        raise ValueError("thetas and the evaluators' rank disagree")
+    if not np.all(np.isfinite(th)):
+        raise ValueError("thetas contain a non-finite value")
+    value = np.zeros(n)
+    aux = np.zeros((n, 4)) if return_aux else None
+    status = np.zeros(n, dtype=np.int32)
+    rc = nat.lib().icp_evaluator_log_values_many(n, _ctx_array(evs), _ptr_array(list(th)), _d(value), _d(aux) if return_aux else None,
+                                                 _i(status))
+    nat.check(rc, "icp_evaluator_log_values_many")
+    return {"value": value, "aux": aux, "status": status}
+
+
 
 def transformed_meshes(contexts, thetas) -> np.ndarray:
     """ModelFittingParameters.transformedMesh of many states in one call (icp_model_instances_many): row b is

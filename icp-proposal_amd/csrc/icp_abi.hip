@@ -19,6 +19,7 @@
 #include "abi_metrics_many.inl"  // C ABI: icp_mesh_metrics_many (registration metrics and Dice of many meshes, kernels_metrics.hip)
 #include "abi_variability_many.inl"  // C ABI: icp_posterior_variability_many (variability maps of many chains, kernels_variability.hip)
 #include "abi_projection_many.inl"  // C ABI: icp_model_instances_many / icp_model_coefficients_many (model projection of many meshes, kernels_projection.hip)
+#include "abi_log_values_many.inl"  // C ABI: icp_evaluator_log_values_many (log values of many states under many evaluators, kernels_evaluate.hip)
 #include "abi_posterior_models.inl"  // C ABI: icp_posterior_models_many (posterior shape models of given correspondences, kernels_posterior_model.hip)
 #include "abi_step.inl"  // the merged step (five launches): fronts, speculative decompositions, icp_chain_step / _prelaunch
 #include "abi_wide.inl"  // the wide step's host side (kernels_wide.hip)

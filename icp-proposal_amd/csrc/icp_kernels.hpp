@@ -744,6 +744,26 @@ void launch_met_stats(hipStream_t st, int n, bool big, const MetStats* jobs);
 void launch_met_samples(hipStream_t st, int n, int nmax, uint64_t seed, const MetDice* jobs);
 void launch_met_dice_count(hipStream_t st, int n, int nmax, const MetDice* jobs);
 
+// ---- log values of many states under many evaluators (kernels_evaluate.hip; icp_evaluator_log_values_many)
+struct EvalGather {     // the first K points of an instance, copied into a packed query list
+  const double* x;
+  double* P;
+  int K;
+};
+enum { kEvalGauss = 0, kEvalMax = 1, kEvalStats = 2 };
+struct EvalReduce {     // one reduction over K squared distances, as its one-item launcher makes it
+  int kind;             // kEvalGauss: out[0] = Σ log N(d; mean, sigma); kEvalMax: out[0] = max d; kEvalStats: out [Σ, max, count]
+  int K;
+  const double* d2;
+  double mean, sigma;
+  const unsigned char* flags;  // kEvalStats: MetStats' boundary test
+  const int* idx;
+  int n_flags;
+  double* out;
+};
+void launch_eval_gather(hipStream_t st, int n, int kmax, const EvalGather* jobs);
+void launch_eval_reduce(hipStream_t st, int n, const EvalReduce* jobs);
+
 // ---- posterior variability maps of many chains (kernels_variability.hip; icp_posterior_variability_many)
 struct VarNormalJob {   // vertex normals of one mesh
   const double* x;

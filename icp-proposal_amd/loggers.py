@@ -33,16 +33,22 @@ class JSONAcceptRejectLogger:
         self.log_status = []
 
     # ---- filling
-    def add_records(self, records: np.ndarray, leaf_names, evaluator_name: str = "product"):
-        """Append the records of icp_host_chain_run (one row per MH step)."""
+    def add_records(self, records: np.ndarray, leaf_names, evaluator_name: str = "product", logvalues=None):
+        """Append the records of icp_host_chain_run (one row per MH step).  `logvalues`: what log_values_of_records gives for these
+        records — every record's "logvalue" map then holds all the named evaluators, as the reference's logger writes them (:84-106);
+        without it the map holds the record's own value under `evaluator_name`."""
         stamp = _dt.datetime.now().strftime("%Y-%m-%d %H:%M:%S")
-        for rec in np.asarray(records, dtype=np.float64):
+        records = np.asarray(records, dtype=np.float64)
+        if logvalues is not None and any(len(v) != len(records) for v in logvalues.values()):
+            raise ValueError("logvalues: one entry per record under every name")
+        for k, rec in enumerate(records):
             accepted = bool(rec[1] != 0.0)
             theta = rec[4:]
             self.log_status.append({
                 "index": len(self.log_status),                      # totalSamples at the time of logging (:96,104)
                 "name": leaf_names[int(rec[2])],
-                "logvalue": {evaluator_name: float(rec[3])},
+                "logvalue": ({evaluator_name: float(rec[3])} if logvalues is None
+                             else {name: float(v[k]) for name, v in logvalues.items()}),
                 "status": accepted,
                 # theta = [s | t(3) | phi,theta,psi | centre(3) | c(r)]  ->  rigid = t, rotation, centre (:133-140)
                 "rigid": [float(v) for v in theta[1:10]] if accepted else [],
@@ -95,6 +101,45 @@ def samples_from_log(log, take_every_n: int = 50, total: int = 100, burn_in: int
         return i
     idx = [get_log_index(i) for i in range(burn_in, min(len(log), total), take_every_n)]
     return [(log[i], i) for i in idx][:min(total, len(idx))]
+
+
+EVALUATOR_NAMES = ("product", "prior", "distance")  # the map of ProductEvaluators.scala:50-54
+
+
+def log_values_of_records(records, evaluator, theta_init) -> dict:
+    """Every named evaluator on every record of a chain (JSONAcceptRejectLogger.scala:84-106 evaluates the whole map of
+    ProductEvaluators.scala:50-54 per logged sample; the step records carry the product alone).  An accepted record is scored at its
+    sample, a rejected one at the CURRENT state (:100-106): the last accepted record's state, or `theta_init` before the first
+    acceptance.  "distance" comes from ONE api.log_values call over the distinct states under `evaluator` (the chain's likelihood, or
+    another one: re-scoring a log), "prior" is the closed form of ModelPriorEvaluator (:24-31), "product" = prior + distance as the
+    chain forms it.  Returns {"product", "prior", "distance"}: arrays of one entry per record."""
+    from . import api as _api
+    records = np.asarray(records, dtype=np.float64)
+    if records.ndim != 2:
+        raise ValueError("records must be [n_steps, 14 + rank]")
+    current = np.ascontiguousarray(theta_init, dtype=np.float64).reshape(-1)
+    if records.shape[1] != 4 + current.shape[0]:
+        raise ValueError("records and theta_init disagree in the rank")
+    states, where, slot = [], {}, np.zeros(len(records), dtype=np.int64)
+    for k, rec in enumerate(records):
+        if rec[1] != 0.0:
+            current = rec[4:]
+        key = current.tobytes()
+        if key not in where:
+            where[key] = len(states)
+            states.append(current)
+        slot[k] = where[key]
+    if not states:
+        return {name: np.zeros(0) for name in EVALUATOR_NAMES}
+    states = np.stack(states)
+    rank = states.shape[1] - 10
+    distance = _api.log_values(evaluator, states)["value"]
+    # MultivariateNormalDistribution(0, I).logpdf(c), the sum in icp_prior_log_value's order
+    nn = np.zeros(len(states))
+    for j in range(rank):
+        nn += states[:, 10 + j] * states[:, 10 + j]
+    prior = -0.5 * nn - 0.5 * rank * np.log(2.0 * np.pi)
+    return {"product": (prior + distance)[slot], "prior": prior[slot], "distance": distance[slot]}
 
 
 def variability_from_logs(contexts, logs, take_every_n: int = 50, total: int = 10000, burn_in: int = 200, mode=(2, 0), theta_refs=None,

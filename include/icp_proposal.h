@@ -303,6 +303,21 @@ ICP_API int icp_mesh_metrics(icp_ctx *ctx, const double *theta, double *out /* [
 ICP_API int icp_mesh_metrics_many(int32_t n_items, icp_ctx *const *ctxs, const double *const *thetas, int32_t dice_samples,
                                   uint64_t dice_seed, double *out /* [n_items*9] */, int32_t *status /* [n_items] */);
 
+/* Log values of many states under many evaluators in one call, one synchronisation (the reference's logger scores every named
+ * evaluator on every logged sample: JSONAcceptRejectLogger.scala:84-106; re-scoring a chain's log under another likelihood).
+ * Item b delivers in values[b], aux[4b..4b+3] and status[b] the bits of icp_evaluator_log_value(evaluators[b], thetas[b], ...) on a
+ * fresh evaluator, for every kind and mode, closed or open targets, ICP_ERR_EMPTY included.  Evaluators may repeat, differ in kind,
+ * mode and parameters and belong to different contexts (targets); all contexts share one device and one model.  The call leaves the
+ * evaluators and their contexts as they were: no memo, bind state, state slot or hint is read or written, and a chain stepped
+ * around the call produces the records it would have produced without it.
+ * ICP_ERR_INVALID_ARG (null pointers or entries, n_items outside [1, 65535], a non-finite theta, mixed devices or models) and
+ * ICP_ERR_BUSY (a context belongs to a batch in flight): nothing has run, nothing is written.  Otherwise status[b] = ICP_OK,
+ * ICP_ERR_EMPTY or ICP_ERR_NOT_FINITE as the one-item call reports it, and the return value is ICP_OK or the first status that is
+ * neither ICP_OK nor ICP_ERR_EMPTY.  An item's bits depend neither on the other items nor on their order. */
+ICP_API int icp_evaluator_log_values_many(int32_t n_items, icp_evaluator *const *evaluators, const double *const *thetas,
+                                          double *values /* [n_items] */, double *aux /* [4 * n_items], may be NULL */,
+                                          int32_t *status /* [n_items] */);
+
 /* Posterior variability maps of many chains in one call, one synchronisation (PosteriorVariabilityToMeshColor's maps for every chain
  * of apps/femur/StdIcpVsChainICPrandomInitComparisonAll.scala).  Map m is computed from the n_samples[m] states thetas[m]
  * ([n_samples[m] * (10 + rank of ctxs[m])], poses included, registered rotation matrices honoured) in modes[m] (0, 1, 2 as in
