@@ -108,6 +108,11 @@ SIGNATURES = {
     "icp_mesh_metrics": (C.c_int, [C.c_void_p, c_double_p, c_double_p]),
     "icp_mesh_metrics_many": (C.c_int, [C.c_int32, C.POINTER(C.c_void_p), C.POINTER(c_double_p), C.c_int32, C.c_uint64, c_double_p,
                                         c_int_p]),
+    "icp_registration_maps_many": (C.c_int, [C.c_int32, C.POINTER(C.c_void_p), C.POINTER(c_double_p), C.POINTER(c_double_p),
+                                             C.POINTER(c_int_p), C.POINTER(c_double_p), C.POINTER(c_ubyte_p), C.POINTER(c_double_p),
+                                             C.POINTER(c_int_p), C.POINTER(c_double_p), c_int_p]),
+    "icp_distance_summaries_many": (C.c_int, [C.c_int32, C.POINTER(C.c_void_p), c_int_p, C.POINTER(c_double_p), C.POINTER(c_double_p),
+                                              C.POINTER(c_double_p), C.POINTER(c_double_p), C.POINTER(c_double_p), c_int_p]),
     "icp_evaluator_log_values_many": (C.c_int, [C.c_int32, C.POINTER(C.c_void_p), C.POINTER(c_double_p), c_double_p, c_double_p,
                                                 c_int_p]),
     "icp_model_instances_many": (C.c_int, [C.c_int32, C.POINTER(C.c_void_p), C.POINTER(c_double_p), C.POINTER(c_double_p)]),

@@ -271,6 +271,12 @@ class IcpContext:
         nat.check(nat.lib().icp_closest_point_on_model(self.h, _d(th), n, _d(q), _d(cp), _i(tri), _d(d2)), "icp_closest_point_on_model")
         return cp, tri, d2
 
+    def distanceMap(self, theta, want=None) -> dict:
+        """The per-vertex result of the registration theta against this context's target: one item of registration_maps."""
+        m = registration_maps(self, _theta(theta)[None, :], want=_MAPS_WANT if want is None else want)[0]
+        nat.check(int(m["status"]), "icp_registration_maps_many")
+        return m
+
 
 @dataclasses.dataclass
 class IcpPosterior:
@@ -811,6 +817,122 @@ def dice_coefficient(ctx: IcpContext, theta, samples: int = 10000, seed: int = 1
     m = registration_metrics(ctx, _theta(theta)[None, :], samples, seed)
     nat.check(int(m["status"][0]), "icp_mesh_metrics_many")
     return float(m["dice"][0])
+
+
+_MAPS_WANT = ("m2t_point", "m2t_triangle", "m2t_distance", "m2t_on_boundary", "t2m_point", "t2m_triangle", "t2m_distance")
+_SUMMARY_WANT = ("m2t_mean", "m2t_max", "t2m_mean", "t2m_max")
+
+
+def _ubyte_p(a):
+    return a.ctypes.data_as(nat.c_ubyte_p)
+
+
+def _want(want, known):
+    want = tuple(want)
+    if not want:
+        raise ValueError(f"ask for at least one output of {known}")
+    for w in want:
+        if w not in known:
+            raise ValueError(f"unknown output {w!r}: one of {known}")
+    return want
+
+
+def _rows_of(block, counts, width):
+    """Per-item views [count, width] (width 0: [count]) of one contiguous block: the items' rows lie side by side in memory."""
+    views, at = [], 0
+    for k in counts:
+        views.append(block[at:at + k * max(width, 1)].reshape((k, width) if width else (k,)))
+        at += k * max(width, 1)
+    return views
+
+
+def registration_maps(contexts, thetas, want=_MAPS_WANT) -> list:
+    """The per-vertex result of many registrations in one call (icp_registration_maps_many): item b is the mesh of thetas[b] against
+    the target of contexts[b] (one context, or one per item; contexts may repeat, one model).  `want` names the outputs to fetch; a
+    direction none of whose outputs is wanted is not searched.  Returns one dict per item with "status" (0, or -3 for a mesh that is
+    not finite: NaN rows, triangles -1, flags 0) and the wanted ones of
+      "m2t_point" [N, 3], "m2t_triangle" [N], "m2t_distance" [N]: closestPointOnTarget(transformedMesh(theta)) and sqrt of its
+        squared distances — the colour-coded distance map of a fit, a dense correspondence set for posterior_models;
+      "m2t_on_boundary" [N] uint8: the nearest target vertex of that point is a boundary vertex of the target
+        (RegistrationComparison.scala:31-42; all 0 for a closed target);
+      "t2m_point" [M, 3], "t2m_triangle" [M], "t2m_distance" [M]: closestPointOnModel(theta, target vertices), likewise.
+    The arrays of one output are views of one block, item after item."""
+    th = _f64(thetas)
+    if th.ndim == 1:
+        th = th[None, :]
+    if th.ndim != 2:
+        raise ValueError("thetas must be [n_items, 10 + rank]")
+    n = th.shape[0]
+    ctxs = _per_item(contexts, n)
+    r = ctxs[0].rank
+    if th.shape[1] != 10 + r or any(c.rank != r for c in ctxs):
+        raise ValueError("thetas and the contexts' rank disagree")
+    if not np.all(np.isfinite(th)):
+        raise ValueError("thetas contain a non-finite value")
+    want = _want(want, _MAPS_WANT)
+    spec = {"m2t_point": (np.float64, 3, nat.c_double_p, _d), "m2t_triangle": (np.int32, 0, nat.c_int_p, _i),
+            "m2t_distance": (np.float64, 0, nat.c_double_p, _d), "m2t_on_boundary": (np.uint8, 0, nat.c_ubyte_p, _ubyte_p),
+            "t2m_point": (np.float64, 3, nat.c_double_p, _d), "t2m_triangle": (np.int32, 0, nat.c_int_p, _i),
+            "t2m_distance": (np.float64, 0, nat.c_double_p, _d)}
+    rows, args = {}, []
+    for w in _MAPS_WANT:
+        if w not in want:
+            args.append(None)
+            continue
+        dtype, width, ptype, conv = spec[w]
+        counts = [c.N if w.startswith("m2t") else c.target.n_points for c in ctxs]
+        rows[w] = _rows_of(np.zeros(sum(counts) * max(width, 1), dtype=dtype), counts, width)
+        args.append(_ptr_array(rows[w], ptype, conv))
+    status = np.zeros(n, dtype=np.int32)
+    rc = nat.lib().icp_registration_maps_many(n, _ctx_array(ctxs), _ptr_array(list(th)), *args, _i(status))
+    if rc not in (0, -3) or (rc != 0 and not np.any(status != 0)):
+        nat.check(rc, "icp_registration_maps_many")
+    out = []
+    for b in range(n):
+        item = {w: rows[w][b] for w in want}
+        item["status"] = int(status[b])
+        out.append(item)
+    return out
+
+
+def distance_summaries(contexts, sample_sets, want=_SUMMARY_WANT) -> list:
+    """The distance maps many chains' samples imply, in one call (icp_distance_summaries_many): set m holds the states sample_sets[m]
+    ([S_m, 10 + rank], S_m >= 1) on contexts[m] (one context, or one per set).  Per vertex, "m2t_mean" / "t2m_mean" are the
+    registration_maps distances of the set's states added left to right in sample order and divided once by S_m, "m2t_max" /
+    "t2m_max" their maximum: where the posterior stays off the target, beside posterior_variability_maps' where it is wide.  The
+    per-state maps never leave the device.  Returns one dict per set: the wanted arrays ([N] / [M]) and "status" (0, or -3 for a set
+    with a sample whose mesh is not finite: NaN rows)."""
+    sets = [_f64(a) for a in sample_sets]
+    n = len(sets)
+    ctxs = _per_item(contexts, n, "set")
+    r = ctxs[0].rank
+    for m, a in enumerate(sets):
+        if a.ndim != 2 or a.shape[1] != 10 + r or ctxs[m].rank != r:
+            raise ValueError(f"set {m}: samples must be [S, 10 + rank] of the contexts' one rank")
+        if a.shape[0] < 1:
+            raise ValueError(f"set {m}: at least one sample")
+        if not np.all(np.isfinite(a)):
+            raise ValueError(f"set {m}: samples contain a non-finite value")
+    want = _want(want, _SUMMARY_WANT)
+    rows, args = {}, []
+    for w in _SUMMARY_WANT:
+        if w not in want:
+            args.append(None)
+            continue
+        counts = [c.N if w.startswith("m2t") else c.target.n_points for c in ctxs]
+        rows[w] = _rows_of(np.zeros(sum(counts)), counts, 0)
+        args.append(_ptr_array(rows[w]))
+    status = np.zeros(n, dtype=np.int32)
+    c_n = np.array([a.shape[0] for a in sets], dtype=np.int32)
+    rc = nat.lib().icp_distance_summaries_many(n, _ctx_array(ctxs), _i(c_n), _ptr_array(sets), *args, _i(status))
+    if rc not in (0, -3) or (rc != 0 and not np.any(status != 0)):
+        nat.check(rc, "icp_distance_summaries_many")
+    out = []
+    for m in range(n):
+        item = {w: rows[w][m] for w in want}
+        item["status"] = int(status[m])
+        out.append(item)
+    return out
 
 
 def log_values(evaluators, thetas, return_aux: bool = False) -> dict:

@@ -207,6 +207,14 @@ Pose pose_from_theta(const double* th) {
   return p;
 }
 
+// which rows a call of abi_registration_maps.inl asks for: a direction nobody wants is not searched, a search keeps only what is read
+struct MapWant {
+  bool m2t = false, t2m = false;          // model vertices -> target surface / target vertices -> the instance's surface
+  bool m2t_cp = false, m2t_tri = false;   // the model -> target search's points / triangles go to the caller
+  bool boundary = false;                  // boundary flags are wanted and some target of the call has a boundary
+  bool t2m_cp = false, t2m_tri = false;
+};
+
 struct DeviceMesh {
   int V = 0, T = 0, n_boundary = 0;
   DBuf<double> verts;

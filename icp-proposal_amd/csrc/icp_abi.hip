@@ -20,6 +20,7 @@
 #include "abi_variability_many.inl"  // C ABI: icp_posterior_variability_many (variability maps of many chains, kernels_variability.hip)
 #include "abi_projection_many.inl"  // C ABI: icp_model_instances_many / icp_model_coefficients_many (model projection of many meshes, kernels_projection.hip)
 #include "abi_log_values_many.inl"  // C ABI: icp_evaluator_log_values_many (log values of many states under many evaluators, kernels_evaluate.hip)
+#include "abi_registration_maps.inl"  // C ABI: icp_registration_maps_many / icp_distance_summaries_many (per-vertex registration maps and chain summaries, kernels_maps.hip)
 #include "abi_posterior_models.inl"  // C ABI: icp_posterior_models_many (posterior shape models of given correspondences, kernels_posterior_model.hip)
 #include "abi_step.inl"  // the merged step (five launches): fronts, speculative decompositions, icp_chain_step / _prelaunch
 #include "abi_wide.inl"  // the wide step's host side (kernels_wide.hip)

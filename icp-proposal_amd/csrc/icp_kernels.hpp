@@ -764,6 +764,37 @@ struct EvalReduce {     // one reduction over K squared distances, as its one-it
 void launch_eval_gather(hipStream_t st, int n, int kmax, const EvalGather* jobs);
 void launch_eval_reduce(hipStream_t st, int n, const EvalReduce* jobs);
 
+// ---- per-vertex registration maps and their chain summaries (kernels_maps.hip; icp_registration_maps_many,
+// icp_distance_summaries_many).  The searches are the metrics' (launch_met_items / launch_met_box / launch_met_searches).
+struct MapSide {        // one direction of one item: what its search left, and the rows of the map
+  int K;                // queries (0: this direction is not searched)
+  const double* d2;     // [K] squared distances, as the search wrote them
+  double* cp;           // [K*3] the search's points (null: not kept)
+  int* tri;             // [K] the search's triangles (null: not kept)
+  double* dist;         // [K] sqrt(d2) (null: not wanted)
+};
+struct MapItem {        // one item's epilogue record (device)
+  const int* nonfinite; // the item's count of non-finite coordinates (k_met_box): != 0 makes every row NaN / -1 / 0
+  MapSide m2t, t2m;
+  unsigned char* flag;  // [m2t.K] 1 iff the nearest target vertex of the surface point lies on the target's boundary (null: not wanted)
+  const int* nnv;       // [m2t.K] that vertex (null: the target has no boundary, every flag is 0)
+  const unsigned char* boundary;  // [n_flags] the target's boundary flags
+  int n_flags;
+};
+struct MapSumSeg {      // n consecutive samples of one set and one direction, resident in the chunk (device)
+  int K, n, S;          // vertices; samples here; the set's sample count
+  int first, last;      // the set's first / last segment
+  const double* d2;     // [n][K] squared distances, sample after sample
+  const int* nonfinite; // [n] the samples' counts of non-finite coordinates
+  const double* acc_in; // [2K] Σ d and max d of the set's earlier segments (first: unused)
+  double* acc_out;      // [2K] … handed to its next segment (last: unused; never acc_in of a segment of the same launch)
+  int* bad;             // the set's word: != 0 once a sample's mesh was not finite (carried between segments)
+  double* mean;         // [K] written by the last segment (null: not wanted)
+  double* max;          // [K] likewise
+};
+void launch_map_rows(hipStream_t st, int n_items, int kmax, const MapItem* items);
+void launch_map_summaries(hipStream_t st, int n_segs, int kmax, const MapSumSeg* segs);
+
 // ---- posterior variability maps of many chains (kernels_variability.hip; icp_posterior_variability_many)
 struct VarNormalJob {   // vertex normals of one mesh
   const double* x;

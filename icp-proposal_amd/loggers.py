@@ -242,3 +242,24 @@ class JSONExperimentLogger:
         """:81-84"""
         with open(self.file_path) as f:
             return json.load(f)
+
+
+def distance_summaries_from_logs(contexts, logs, take_every_n: int = 50, total: int = 10000, burn_in: int = 200,
+                                 want=("m2t_mean", "m2t_max", "t2m_mean", "t2m_max")) -> dict:
+    """The distance maps many chains' logs imply: samples_from_log of every log (variability_from_logs' defaults), logSamples2shapes
+    and, in ONE batched device call (api.distance_summaries), per vertex the mean and the maximum over the picked states of the
+    distance to the target's surface — and of every target vertex's distance to the sample's surface.  `contexts`: one context or one
+    per log; `logs`: per chain the list loadLog gives.  Returns {"summaries": [per log api.distance_summaries' dict], "indices": [per
+    log the log indices samples_from_log picked]}."""
+    from . import api as _api
+    logs = list(logs)
+    ctxs = list(contexts) if isinstance(contexts, (list, tuple)) else [contexts] * len(logs)
+    if len(ctxs) != len(logs):
+        raise ValueError("one context per log (or one for all)")
+    picked = [samples_from_log(lg, take_every_n=take_every_n, total=total, burn_in=burn_in) for lg in logs]
+    sets = []
+    for k, sub in enumerate(picked):
+        if len(sub) < 1:
+            raise ValueError(f"log {k}: no sample behind the burn-in")
+        sets.append(np.stack([JSONAcceptRejectLogger.sample_to_model_parameters(s) for s, _ in sub]))
+    return {"summaries": _api.distance_summaries(ctxs, sets, want=want), "indices": [[i for _, i in sub] for sub in picked]}

@@ -303,6 +303,45 @@ ICP_API int icp_mesh_metrics(icp_ctx *ctx, const double *theta, double *out /* [
 ICP_API int icp_mesh_metrics_many(int32_t n_items, icp_ctx *const *ctxs, const double *const *thetas, int32_t dice_samples,
                                   uint64_t dice_seed, double *out /* [n_items*9] */, int32_t *status /* [n_items] */);
 
+/* Per-vertex registration maps of many meshes in one call, one synchronisation: what icp_mesh_metrics_many computes for every item
+ * and reduces to five numbers, handed out row by row (the colour-coded distance map of a fit; a dense correspondence set).  Item b
+ * is the mesh x = icp_transformed_mesh(ctxs[b], thetas[b]), N model vertices, against ctxs[b]'s target of M_b vertices.  Contexts
+ * may repeat; all share one device and one model, targets may differ.  Every output is an array of n_items pointers, one array per
+ * item, or NULL for "not wanted":
+ *   m2t_point[b]       [N*3]   the bits of icp_closest_point_on_target(ctxs[b], N, x, ...)'s points
+ *   m2t_triangle[b]    [N]     ... its triangle indices
+ *   m2t_distance[b]    [N]     sqrt of its squared distances, the expression icp_mesh_metrics reduces
+ *   m2t_on_boundary[b] [N]     1 iff the nearest target vertex of m2t_point (icp_closest_target_vertex) is a boundary vertex of the
+ *                              target — the filter of api/other/RegistrationComparison.scala:31-42; all 0 for a target without
+ *                              boundary, whose nearest vertices are then not searched
+ *   t2m_point[b]       [M_b*3] the bits of icp_closest_point_on_model(ctxs[b], thetas[b], M_b, target vertices, ...)'s points
+ *   t2m_triangle[b]    [M_b]   ... its triangle indices
+ *   t2m_distance[b]    [M_b]   sqrt of its squared distances
+ * A direction none of whose outputs is wanted is not searched.  Device memory does not grow with n_items: the rows stream to the
+ * caller through a fixed staging buffer.
+ * ICP_ERR_INVALID_ARG (null pointers or entries, n_items outside [1, 65535], every output NULL, a non-finite theta, mixed devices or
+ * models) and ICP_ERR_BUSY (a context belongs to a batch in flight): nothing has run, nothing is written.  Otherwise status[b] =
+ * ICP_OK, or ICP_ERR_NOT_FINITE for an item whose mesh is not finite (its rows are NaN, its triangles -1, its flags 0), and the
+ * return value is ICP_OK or the first failing item's.  An item's bits depend neither on the other items nor on their order. */
+ICP_API int icp_registration_maps_many(int32_t n_items, icp_ctx *const *ctxs, const double *const *thetas, double *const *m2t_point,
+                                       int32_t *const *m2t_triangle, double *const *m2t_distance, uint8_t *const *m2t_on_boundary,
+                                       double *const *t2m_point, int32_t *const *t2m_triangle, double *const *t2m_distance,
+                                       int32_t *status /* [n_items] */);
+
+/* The distance maps a chain's samples imply, for many chains in one call, one synchronisation.  Set m holds the n_samples[m] >= 1
+ * states theta_sets[m] ([n_samples[m] * (10 + rank)]) on ctxs[m]; with d_s the distances icp_registration_maps_many gives for state
+ * s, per vertex
+ *   mean = (((d_0 + d_1) + d_2) + ...) / n_samples[m]   (added left to right in sample order, then ONE division)
+ *   max  = the maximum of the same distances.
+ * m2t_mean[m], m2t_max[m] [N]; t2m_mean[m], t2m_max[m] [M_m].  An output array may be NULL; a direction neither of whose outputs
+ * is wanted is not searched.  The per-state maps never leave the device.  At most 2^24 samples a call.
+ * Errors as icp_registration_maps_many (n_sets outside [1, 65535], a set without samples: ICP_ERR_INVALID_ARG, nothing written);
+ * status[m] = ICP_ERR_NOT_FINITE for a set one of whose samples has a non-finite mesh (its rows are NaN).  A set's bits depend
+ * neither on the other sets nor on their order. */
+ICP_API int icp_distance_summaries_many(int32_t n_sets, icp_ctx *const *ctxs, const int32_t *n_samples, const double *const *theta_sets,
+                                        double *const *m2t_mean, double *const *m2t_max, double *const *t2m_mean,
+                                        double *const *t2m_max, int32_t *status /* [n_sets] */);
+
 /* Log values of many states under many evaluators in one call, one synchronisation (the reference's logger scores every named
  * evaluator on every logged sample: JSONAcceptRejectLogger.scala:84-106; re-scoring a chain's log under another likelihood).
  * Item b delivers in values[b], aux[4b..4b+3] and status[b] the bits of icp_evaluator_log_value(evaluators[b], thetas[b], ...) on a
