@@ -335,7 +335,6 @@ void icp_ctx_destroy(icp_ctx* ctx) {
     std::lock_guard<std::mutex> lk(g_eig_streams_mu);
     g_eig_streams.erase(s1);
     (void)hipStreamSynchronize(s1);
-    library_release_stream(s1);
     give_stream(s1);
   }
   if (ctx->ev_ready) (void)hipEventDestroy(ctx->ev_ready);
@@ -344,12 +343,10 @@ void icp_ctx_destroy(icp_ctx* ctx) {
   if (ctx->ev_asm) (void)hipEventDestroy(ctx->ev_asm);
   if (hipStream_t fs = ctx->front_stream.release()) {
     (void)hipStreamSynchronize(fs);
-    library_release_stream(fs);
     give_stream(fs);
   }
   if (ctx->stream) {
     (void)hipStreamSynchronize(ctx->stream);
-    library_release_stream(ctx->stream);
     give_stream(ctx->stream);
   }
   if (ctx->ev_join) (void)hipEventDestroy(ctx->ev_join);

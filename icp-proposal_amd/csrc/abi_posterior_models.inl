@@ -1,5 +1,5 @@
 // abi_posterior_models.inl — C ABI: icp_posterior_models_many, the posterior shape models of many sets of given correspondences
-// (kernels_posterior_model.hip; the resident factorisations and decompositions of kernels_posterior.hip).
+// (kernels_posterior_model.hip; the resident factorisations and decompositions of kernels_factor.hip and kernels_eigen.hip).
 //
 // Item b: M = I + Σ Q_iᵀ Σ_i⁻¹ Q_i and b = Σ Q_iᵀ Σ_i⁻¹ (y_i − x̄_i − μ_i) over its observations, α = M⁻¹ b, D M⁻¹ D = V S Vᵀ, and from
 // those the model (μ + Q·α, Φ·V, S).  The items go through kPmGroup slots of r-space scratch, a group at a time: one regression launch for

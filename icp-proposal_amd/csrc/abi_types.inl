@@ -109,7 +109,7 @@ constexpr int kStateSlots = 8;
 constexpr int kPosteriorMemo = 20;  // NonRigidIcpProposal.scala:49
 constexpr int kEvalMemo = 3;        // evaluators/EvaluationCaching.scala:32
 constexpr int kMaxRank = 500;
-constexpr int kCholMaxRankAbi = 256;  // (= kCholMaxRank of kernels_posterior.hip: ranks whose factorisation hands the factor out)
+constexpr int kCholMaxRankAbi = 256;  // (= kCholMaxRank of kernels_factor.hip: ranks whose factorisation hands the factor out)
 
 // ---- host-side mesh preprocessing (one-off, at context creation)
 

@@ -1,5 +1,6 @@
 // icp_dense.hpp — device-side bodies of the correspondence / regression / r-space kernels (math: kernels_posterior.hip).
-// Included by kernels_posterior.hip (one kernel per stage) and kernels_step.hip (merged per-step launches).
+// Included by kernels_posterior.hip, kernels_factor.hip, kernels_eigen.hip (one kernel per stage) and kernels_step.hip (merged per-step
+// launches), and by the batched entry points' units for the pieces they share with them.
 #pragma once
 #include "icp_kernels.hpp"
 
@@ -472,7 +473,7 @@ __device__ __forceinline__ void regression_xrows(int e, int K, int r, int xrs, c
 
 // ---------------------------------------------------------------- dense helpers (one workgroup, matrix behind a generic pointer)
 
-__device__ double block_sum(double v, double* s_red) {
+static inline __device__ double block_sum(double v, double* s_red) {
   const int tid = threadIdx.x;
   for (int o = 32; o > 0; o >>= 1) v += __shfl_down(v, o, 64);
   __syncthreads();
@@ -482,7 +483,7 @@ __device__ double block_sum(double v, double* s_red) {
   for (int w = 0; w < (int)((blockDim.x + 63) >> 6); ++w) t += s_red[w];
   return t;
 }
-__device__ double block_max(double v, double* s_red) {
+static inline __device__ double block_max(double v, double* s_red) {
   const int tid = threadIdx.x;
   for (int o = 32; o > 0; o >>= 1) v = fmax(v, __shfl_down(v, o, 64));
   __syncthreads();
@@ -513,7 +514,7 @@ __device__ __forceinline__ double fast_rsqrt(double x) {
 
 // y = A x for a row-major r×r matrix A (leading dimension lda; LDS or global), x and y in LDS.  2^tpr_log2 threads share
 // a row (their partial sums meet through wave shuffles), blockDim/2^tpr_log2 rows per pass.  Ends with a barrier.
-__device__ void block_matvec(int r, const double* A, int lda, const double* x, double* y, int tpr_log2) {
+static inline __device__ void block_matvec(int r, const double* A, int lda, const double* x, double* y, int tpr_log2) {
   const int tid = threadIdx.x, tpr = 1 << tpr_log2, sub = tid & (tpr - 1);
   const int rows_per_pass = blockDim.x >> tpr_log2;
   for (int row0 = 0; row0 < r; row0 += rows_per_pass) {  // uniform trip count: every lane reaches the shuffles
@@ -549,7 +550,7 @@ __device__ void block_matvec(int r, const double* A, int lda, const double* x, d
 // same with the matrix in the dynamic LDS segment at s_dyn[offA ...]: indexing s_dyn directly keeps the loads DS
 // instructions (a generic pointer to LDS would make them FLAT, several times slower)
 extern __shared__ __attribute__((aligned(16))) double s_dyn[];
-__device__ void block_matvec_lds(int r, int offA, int lda, const double* x, double* y, int tpr_log2) {
+static inline __device__ void block_matvec_lds(int r, int offA, int lda, const double* x, double* y, int tpr_log2) {
   const int tid = threadIdx.x, tpr = 1 << tpr_log2, sub = tid & (tpr - 1);
   const int rows_per_pass = blockDim.x >> tpr_log2;
   for (int row0 = 0; row0 < r; row0 += rows_per_pass) {
@@ -574,13 +575,13 @@ static inline int matvec_tpr_log2(int r, int block) {
 }
 
 // copy a row-major r×r matrix into LDS with leading dimension ld
-__device__ void stage_matrix(int r, const double* __restrict__ src, double* dst, int ld) {
+static inline __device__ void stage_matrix(int r, const double* __restrict__ src, double* dst, int ld) {
   for (int e = threadIdx.x; e < r * r; e += blockDim.x) {
     const int i = e / r, j = e - i * r;
     dst[(size_t)i * ld + j] = src[e];
   }
 }
-__device__ void stage_matrix_lds(int r, const double* __restrict__ src, int off, int ld) {
+static inline __device__ void stage_matrix_lds(int r, const double* __restrict__ src, int off, int ld) {
   for (int e = threadIdx.x; e < r * r; e += blockDim.x) {
     const int i = e / r, j = e - i * r;
     s_dyn[off + i * ld + j] = src[e];
@@ -591,7 +592,7 @@ __device__ void stage_matrix_lds(int r, const double* __restrict__ src, int off,
 // more rows below it through the same eliminations.  Column j is left UNSCALED (U[i][j] = L[i][j]·l_jj) and the
 // trailing update uses U[i][j]·U[k][j]/U[j][j], so each column costs ONE reciprocal and ONE barrier.
 // Afterwards L[i][j] = W[i][j]·dinv[j] with dinv[j] = 1/sqrt(W[j][j]).  2-D thread grid of tw×tw (tw² = blockDim).
-__device__ bool block_cholesky_rootfree(double* W, int n, int ld, int extra, int tw_log2) {
+static inline __device__ bool block_cholesky_rootfree(double* W, int n, int ld, int extra, int tw_log2) {
   const int tid = threadIdx.x, tw = 1 << tw_log2, ty = tid >> tw_log2, tx = tid & (tw - 1);
   const int rows = n + extra;
   for (int j = 0; j < n; ++j) {

@@ -21,6 +21,20 @@ inline const char* dev_env(const char* name) {
 #endif
 }
 
+// ---- small helpers of the launchers, shared by the kernels_*.hip
+constexpr int kBlock = 256;  // threads of the one-thread-per-element kernels
+__host__ __device__ static inline int cdiv(int a, int b) { return (a + b - 1) / b; }
+// dynamic LDS above the 48 KiB a kernel gets unasked
+static inline void set_dyn_lds(const void* fn, size_t bytes) {
+  if (bytes > 48 * 1024) (void)hipFuncSetAttribute(fn, hipFuncAttributeMaxDynamicSharedMemorySize, (int)bytes);
+}
+// the same for a kernel whose largest request is known up front: one runtime call per process instead of one per launch
+static inline void set_dyn_lds_once(const void* fn, size_t max_bytes, bool* done) {
+  if (*done) return;
+  (void)hipFuncSetAttribute(fn, hipFuncAttributeMaxDynamicSharedMemorySize, (int)max_bytes);
+  *done = true;
+}
+
 // ---- optional per-kernel timing with HIP events on the launch stream (bench.py's roofline leg).
 // Off by default: when `g_prof` is null the launch wrappers add nothing.
 enum KernelId {
@@ -160,7 +174,7 @@ void launch_surface_query(hipStream_t st, int T, const double* verts, const int*
 void launch_vertex_query(hipStream_t st, int V, const double* verts, int K, const double* P, int* hint,
                          const QueryBuffers& qb, double* d2, int* idx);
 
-// ---- posterior assembly + r-space algebra (kernels_posterior.hip)
+// ---- posterior assembly + r-space algebra (kernels_posterior.hip; the factorisation: kernels_factor.hip)
 
 struct CorrBuffers {   // per-correspondence data of one ICP posterior (device)
   int* id;             // [K] model vertex id
@@ -237,7 +251,8 @@ struct TransitionTailIO {
 void launch_transition_tails(hipStream_t st, int r, int n, const TransitionTailIO* io, const double* Ginv, double sigma2);
 void launch_transition_tail_direct(hipStream_t st, int r, const TransitionTailIO& io, const double* G, double sigma2, double* work /* r*r */);
 
-// eigen-decomposition of D M^-1 D (posterior KL basis): V columns (and its transpose Vt), S descending, canonical signs
+// ---- posterior KL basis (kernels_eigen.hip)
+// eigen-decomposition of D M^-1 D: V columns (and its transpose Vt), S descending, canonical signs
 // Vwarm (optional): eigenvectors of a nearby posterior, used as the starting basis of the Jacobi iteration
 size_t eigen_work_doubles(int r);  // size of `work`
 // EigenSpec (optional, ranks <= 64 only): a decomposition started before it is known to be needed.
@@ -259,7 +274,7 @@ struct EigenRequest { const double* M; const double* Vwarm; double* V; double* V
                       const EigenSpec* spec; int* host_status; int* done_word; int done_value;
                       const double* sqrt_lambda = nullptr; /* of the request's own model; launch_posterior_eigen_many needs it */
                       bool root = false; /* write V := D·L⁻ᵀ (M = L·Lᵀ), S := 1 instead of the eigen-decomposition: the opt-in
-                      Cholesky-root sampler (kernels_posterior.hip: k_posterior_root; ranks <= 64) */ };
+                      Cholesky-root sampler (kernels_eigen.hip: k_posterior_root; ranks <= 64) */ };
 bool launch_posterior_eigen_pair(hipStream_t st, int r, const double* sqrt_lambda, int n, const EigenRequest* rq);
 // one decomposition as the rank <= 64 kernels see it (EigenRequest resolved into the kernel's own pointers)
 struct EigenProblem {
@@ -279,7 +294,6 @@ void launch_posterior_eigen_resident(hipStream_t st, int r, int n, const EigenPr
 size_t eigen_many_record_bytes(int n);
 int launch_posterior_eigen_many(hipStream_t st, int r, int n, const EigenRequest* rq, void* pinned_records, int* arrive);
 void eigen_debug_dump(const double* work, int r);
-void library_release_stream(hipStream_t st);  // drops the library handle kept for `st` (ranks > 64), before the stream is destroyed
 void launch_posterior_eigen(hipStream_t st, int r, const double* M, const double* sqrt_lambda, const double* Vwarm, double* V,
                             double* Vt, double* S, double* work /* eigen_work_doubles(r) */, int* status,
                             const EigenSpec* spec = nullptr, int* host_status = nullptr /* pinned copy of *status; honoured
@@ -288,6 +302,7 @@ void launch_posterior_eigen(hipStream_t st, int r, const double* M, const double
                             one-workgroup launch at the head of the chain), 2: the launches behind it — a caller with other work
                             to issue puts it between the two (a launch costs the host 3-6 µs, the chain has eleven) */);
 
+// ---- proposal (kernels_posterior.hip)
 // a8: c' = c + step·((G+σ²I)^-1 G (α + D^-1 V √S z) − c), with P = (G+σ²I)^-1
 void launch_propose(hipStream_t st, int r, const double* alpha, const double* V, const double* S,
                     const double* inv_sqrt_lambda, const double* P, double sigma2, const double* c,
@@ -303,11 +318,11 @@ void launch_correspond_plain(hipStream_t st, int K, const int* ids, const double
 // c <- c + step·((G+σ²I)⁻¹ G α − c) with P = (G+σ²I)⁻¹ (:84-85)
 void launch_mean_step(hipStream_t st, int r, const double* alpha, const double* P, double sigma2, double step, double* c);
 
-// ---- posterior variability (apps/util/PosteriorVariability.scala:30-73): X = [S][N*3] sample meshes
+// ---- posterior variability (kernels_variability.hip; apps/util/PosteriorVariability.scala:30-73): X = [S][N*3] sample meshes
 void launch_accumulate(hipStream_t st, int n, const double* src, double scale_after /* 0 = none */, double* acc);
 void launch_variability(hipStream_t st, int N, int S, const double* X, int mode, const double* normals, double* out);
 
-// ---- evaluator reductions (kernels_posterior.hip)
+// ---- evaluator reductions (kernels_evaluate.hip)
 // out[0] = Σ log N(sqrt(d2_k); mean, sigma)
 void launch_sum_gauss_logpdf(hipStream_t st, int K, const double* d2, double mean, double sigma, double* out);
 // out[0] = Σ kept distances, out[1] = max kept distance, out[2] = number kept;  flag[k] != 0 drops the point
@@ -570,6 +585,8 @@ void launch_step_batch_resident(hipStream_t st, int B, const int grid[5], int r,
 //   W9  sum of the split-K partials -> [eigen stream: assemble, reduce to tridiagonal form, solve, refine]
 //   W10 factorisation    W11 transition tails    W12 results and completion flag into pinned host memory
 constexpr int kWideMaxChains = 16;  // chains per launch sequence (several kernels take their per-chain arguments by value)
+constexpr int kFactorMax = 2 * kWideMaxChains;  // posteriors per factor launch (posterior_factor_max) and per launch_sum_partials_many:
+                                              // both ICP directions of one or two states — or one per chain of a wide step
 
 struct WideProposeItem {   // W1
   int kind;                // 1: a8 from `in` (in.z: the step's standard normals); 0: the coefficients are given (`src`)

@@ -7,7 +7,7 @@
 // 7-9); the reduction to tridiagonal form is r−2 dependent steps ONCE, and everything behind it is parallel over the
 // eigenpairs.  No warm start, no state carried from one decomposition to the next.
 //
-// Included by kernels_posterior.hip only.
+// Included by kernels_eigen.hip only.
 #pragma once
 #include <hip/hip_runtime.h>
 
@@ -595,7 +595,7 @@ __device__ __forceinline__ void tridiag_kernel_body(const TridiagIO& a) {
   EIG_STAMP(1);
 }
 // The kernels of the route take their records by value, CAP of them in the kernel arguments (the pattern of EigenBatch in
-// kernels_posterior.hip), one workgroup — or one slice of the grid — per record; skip_all (optional, device): != 0 leaves a record
+// kernels_eigen.hip), one workgroup — or one slice of the grid — per record; skip_all (optional, device): != 0 leaves a record
 // alone (the on-device loop: a chain that did not move).  Two capacities are instantiated: kTriOne for one decomposition,
 // kTriMany for decompositions side by side (the chains of a wide step: kernels_wide.hip).  The record is copied to a local before
 // the body runs: scalar registers, as a by-value kernel argument.

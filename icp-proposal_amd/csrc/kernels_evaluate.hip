@@ -16,8 +16,6 @@ namespace icp {
 
 namespace {
 
-__host__ __device__ inline int cdiv(int a, int b) { return (a + b - 1) / b; }
-
 constexpr int kGatherBlock = 256;
 constexpr int kReduceBlock = 1024;
 
@@ -87,6 +85,46 @@ __global__ void __launch_bounds__(kReduceBlock) k_eval_reduce(const EvalReduce* 
   else eval_stats(j, j.K > 4096 ? 1024 : 256, s_red);
 }
 
+// ---- the one-item reductions
+
+__global__ void __launch_bounds__(kBlock) k_sum_gauss_logpdf(int K, const double* __restrict__ d2, double mean, double sigma,
+                                                              double* __restrict__ out) {
+  sum_gauss_logpdf_body(K, d2, mean, sigma, out);
+}
+
+__global__ void __launch_bounds__(1024) k_dist_stats(int K, const double* __restrict__ d2, const unsigned char* __restrict__ flags,
+                                                        const int* __restrict__ idx, int n_flags, double* __restrict__ out) {
+  __shared__ double s_red[16];
+  double sum = 0.0, mx = -__builtin_inf(), cnt = 0.0;
+  for (int k = threadIdx.x; k < K; k += blockDim.x) {
+    bool drop = false;
+    if (flags) {
+      int i = idx ? idx[k] : k;
+      drop = (i >= 0 && i < n_flags) ? flags[i] != 0 : false;
+    }
+    if (!drop) {
+      double d = sqrt(d2[k]);
+      sum += d;
+      mx = fmax(mx, d);
+      cnt += 1.0;
+    }
+  }
+  sum = block_sum(sum, s_red);
+  cnt = block_sum(cnt, s_red);
+  mx = block_max(mx, s_red);
+  if (threadIdx.x == 0) { out[0] = sum; out[1] = mx; out[2] = cnt; }
+}
+
+// the maximum alone (the Hausdorff evaluator needs nothing else of the list): any number of workgroups, the non-negative doubles'
+// bit patterns through a 64-bit atomic maximum — order-independent, so exact; `out_max` must be zero (or a distance) beforehand
+__global__ void __launch_bounds__(1024) k_dist_max(int K, const double* __restrict__ d2, double* __restrict__ out_max) {
+  __shared__ double s_red[16];
+  const int k = blockIdx.x * 1024 + threadIdx.x;
+  double mx = k < K ? d2[k] : 0.0;
+  mx = block_max(mx, s_red);
+  if (threadIdx.x == 0) atomicMax((unsigned long long*)out_max, d2bits(sqrt(mx)));
+}
+
 }  // namespace
 
 void launch_eval_gather(hipStream_t st, int n, int kmax, const EvalGather* jobs) {
@@ -98,6 +136,24 @@ void launch_eval_reduce(hipStream_t st, int n, const EvalReduce* jobs) {
   if (n <= 0) return;
   ProfScope _ps(st, KID_REDUCE);
   hipLaunchKernelGGL(k_eval_reduce, dim3(n), dim3(kReduceBlock), 0, st, jobs);
+}
+
+void launch_sum_gauss_logpdf(hipStream_t st, int K, const double* d2, double mean, double sigma, double* out) {
+  { ProfScope _ps(st, KID_REDUCE);
+    hipLaunchKernelGGL(k_sum_gauss_logpdf, dim3(1), dim3(kBlock), 0, st, K, d2, mean, sigma, out); }
+}
+
+void launch_dist_max(hipStream_t st, int K, const double* d2, double* out_max) {
+  if (K <= 0) return;  // (an empty list leaves the zero in place: distances are non-negative)
+  ProfScope _ps(st, KID_REDUCE);
+  hipLaunchKernelGGL(k_dist_max, dim3((K + 1023) / 1024), dim3(1024), 0, st, K, d2, out_max);
+}
+
+void launch_dist_stats(hipStream_t st, int K, const double* d2, const unsigned char* flags, const int* idx,
+                       int n_flags, double* out) {
+  { ProfScope _ps(st, KID_REDUCE);
+    // (one workgroup: the sum has one fixed order; four times the threads where the list is a whole mesh — 40 us per call at 28k points)
+    hipLaunchKernelGGL(k_dist_stats, dim3(1), dim3(K > 4096 ? 1024 : kBlock), 0, st, K, d2, flags, idx, n_flags, out); }
 }
 
 }  // namespace icp

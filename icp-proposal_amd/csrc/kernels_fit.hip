@@ -16,8 +16,6 @@ namespace icp {
 
 namespace {
 
-__host__ __device__ inline int cdiv(int a, int b) { return (a + b - 1) / b; }
-
 __device__ __forceinline__ bool fit_model_side(const FitItem& f, int rec) { return f.dirs[rec] == 0; }
 
 // F1: the fits' instances are one launch_instance_many (kernels_geometry.hip) over the call's instance records.

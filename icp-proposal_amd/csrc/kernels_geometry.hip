@@ -42,9 +42,7 @@ void Profiler::end(hipStream_t st) {
 
 namespace {
 
-constexpr int kBlock = kSearchBlock;
-
-inline int cdiv(int a, int b) { return (a + b - 1) / b; }
+static_assert(kBlock == kSearchBlock, "the search kernels below are launched with kBlock threads");
 
 __global__ void __launch_bounds__(kBlock) k_instance(int N, int r, const double* __restrict__ Qp,
                                                       const double* __restrict__ ref, const double* __restrict__ mean,

@@ -12,8 +12,6 @@ namespace {
 
 constexpr int kMapBlock = 256;
 
-__host__ __device__ inline int cdiv(int a, int b) { return (a + b - 1) / b; }
-
 // the rows of one direction at vertex i; bad: the item's mesh is not finite
 __device__ __forceinline__ void map_side_row(const MapSide& s, int i, bool bad) {
   if (i >= s.K) return;

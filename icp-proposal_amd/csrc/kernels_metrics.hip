@@ -15,8 +15,6 @@ namespace icp {
 
 namespace {
 
-__host__ __device__ inline int cdiv(int a, int b) { return (a + b - 1) / b; }
-
 // orc_rng_uniform (oracle/icp_oracle.c): splitmix64 over (seed, step, lane) -> (0, 1), exact in double
 __device__ __forceinline__ unsigned long long met_splitmix64(unsigned long long x) {
   x += 0x9E3779B97F4A7C15ull;

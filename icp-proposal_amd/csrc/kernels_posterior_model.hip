@@ -11,7 +11,7 @@
 //                           the context keeps, so Φ·V = Q·D⁻¹V and the mean's Q·α is one more column)
 //   PM3 k_pm_gemm           rows of Q·Bm on the f64 matrix cores into the chunk buffer: a wave owns 32 rows × 64 columns
 //   PM4 k_pm_point_variance one wave per vertex over the rows PM3 has just written: Σ_d Σ_j S_j·(ΦV)[3i+d][j]²
-// The factorisations and decompositions between PM1 and PM2 are the resident many-problem kernels (kernels_posterior.hip).
+// The factorisations and decompositions between PM1 and PM2 are the resident many-problem kernels (kernels_factor.hip, kernels_eigen.hip).
 //
 // An item's bits depend on nothing but the item.  PM1: an item's splits are regression_splits of its own observation count, a split's
 // sum runs over its observations in order, one matrix instruction each.  PM3: an output element reads its own row of Q and its own
@@ -27,8 +27,6 @@
 namespace icp {
 
 namespace {
-
-__host__ __device__ inline int cdiv(int a, int b) { return (a + b - 1) / b; }
 
 // PM1.  blockIdx = (split, tile, item).  Operand maps as regression_tile (icp_dense.hpp): lane l supplies A[i = l&15][k = l>>4] and
 // B[k = l>>4][j = l&15]; here k = coordinate (k = 3: nothing), A = X_i = [Q_i | e_i], B = W_i·X_i.

@@ -24,8 +24,6 @@ namespace icp {
 
 namespace {
 
-inline int cdiv(int a, int b) { return (a + b - 1) / b; }
-
 constexpr int kProjResBlock = 128;
 constexpr int kProjTiles = 4;     // 16-column tiles of the basis a wave owns (64 columns: 512 contiguous bytes of a basis row)
 constexpr int kProjSteps = 4;     // matrix instructions' worth of rows (4 each) whose loads are in flight together

@@ -36,8 +36,6 @@ namespace icp {
 namespace {
 
 constexpr int kStepBlock = 256;
-inline int cdiv(int a, int b) { return (a + b - 1) / b; }
-
 // ---------------------------------------------------------------- 1: coefficients -> instance -> query bounds
 
 __device__ __forceinline__ void step_begin_body(const StepBeginArgs& a, const int bx) {
@@ -456,10 +454,6 @@ __global__ void __launch_bounds__(NT) k_step_finish_batch(const StepFinishArgs* 
 }
 
 thread_local StepCapture* t_capture = nullptr;
-
-static void set_dyn_lds(const void* fn, size_t bytes) {
-  if (bytes > 48 * 1024) (void)hipFuncSetAttribute(fn, hipFuncAttributeMaxDynamicSharedMemorySize, (int)bytes);
-}
 
 struct FinishPlan { int E /* tiles per thread */, NT, n_lds, tail_base; size_t shmem; bool ok; };
 

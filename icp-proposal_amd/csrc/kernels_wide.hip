@@ -16,7 +16,6 @@ namespace icp {
 
 namespace {
 
-inline int cdiv(int a, int b) { return (a + b - 1) / b; }
 inline size_t up16(size_t x) { return (x + 15) & ~(size_t)15; }
 
 // ---------------------------------------------------------------- W1: proposal (NonRigidIcpProposal.scala:53-62), or given coefficients

@@ -2,7 +2,8 @@
 above kTriRefineGap, the vectors handed on unrefined), `close` and `graded` (gaps between 1e-10 and 1e-6 of the norm: the Ogita-Aishima
 step has vectors to correct), `multiple` (a pair 1e-13 apart: status 2, the Jacobi fall-back).  Over the rank ladder whose edges select
 the reduction, solve and back-transformation templates, through icp_posterior_models_many (the capacity-32 sequence, the capacity-1
-sequence, the rerun of an item on its own) and through the chain's own path (icp_proposal_posterior).
+sequence, the rerun of an item on its own) and through the chain's own path (icp_proposal_posterior).  The same models of rank r, at
+the edges of the Cholesky factor kernels' rank ladder (kernels_factor.hip): M and α against the numpy long form.
 
 The reference is numpy's eigh of N' = D⁻¹MD⁻¹ from a float64 M (the long form's, or the one the call returns).  Every check is
 invariant to the choice of basis inside a cluster of eigenvalues (a maximal run of reference gaps below 1e-5·μ_max).  Tolerances are
@@ -21,6 +22,37 @@ pytestmark = pytest.mark.gpu
 
 LADDER = (65, 128, 129, 192, 193, 200, 201, 208, 209, 256)  # both sides of every edge of tri_reduction_shape / tri_row_slots, kBigMaxRank
 ORDER = ("wide", "close", "graded", "multiple")
+
+# launch_posterior_factor's ladder (kernels_factor.hip), restated: rank -> the kernel that factors M.  A rank needs factor_tile_count(r)
+# 2 × 4 register tiles over the r + 1 rows of [M; bᵀ]; the factor stays in LDS while (r + 1)·(r | 1) doubles fit beside the kernel's
+# static arrays (w_fits), else it goes to global scratch.
+
+
+def factor_kernel(r):
+    tile_rows = (r + 2) >> 1
+    tiles = sum((t >> 1) + 1 for t in range(tile_rows))
+    w_fits = (r + 1) * (r | 1) <= 18432 - 2000
+    if w_fits and tiles <= 256:
+        return "k_posterior_factor_reg<1, 256>"
+    if w_fits and tiles <= 1024:
+        return "k_posterior_factor_reg<1, 1024>"
+    if w_fits:
+        return "k_posterior_factor_reg<2, 1024>"
+    if tiles <= 3072:
+        return "k_posterior_factor_tiles<3>"
+    if tiles <= 4096:
+        return "k_posterior_factor_tiles<4>"
+    return "k_posterior_factor_generic"
+
+
+# the last rank of every rung and the first of the next (from 128 on k_sum_partials runs ahead of the kernel: ranks 254..256 included)
+FACTOR_LADDER = {
+    61: "k_posterior_factor_reg<1, 256>", 62: "k_posterior_factor_reg<1, 1024>",
+    125: "k_posterior_factor_reg<1, 1024>", 126: "k_posterior_factor_reg<2, 1024>",
+    127: "k_posterior_factor_reg<2, 1024>", 128: "k_posterior_factor_tiles<3>",
+    217: "k_posterior_factor_tiles<3>", 218: "k_posterior_factor_tiles<4>",
+    253: "k_posterior_factor_tiles<4>", 254: "k_posterior_factor_generic",
+}
 
 
 def clusters(w):
@@ -182,4 +214,32 @@ def test_single_path_close_and_multiple_variances(pkg, r, kind):
         prop.close()
     assert not misses, misses
     assert all(v == 0 for v in pkg._native.runtime_stats(ctx.h).values())
+    ctx.close()
+
+
+def test_factor_ladder_edges_are_the_ones_listed():
+    edges = [r for r in range(1, 256) if factor_kernel(r) != factor_kernel(r + 1)]
+    assert sorted(FACTOR_LADDER) == sorted(edges + [r + 1 for r in edges])
+    assert all(factor_kernel(r) == name for r, name in FACTOR_LADDER.items())
+
+
+@pytest.mark.parametrize("r", sorted(FACTOR_LADDER))
+def test_factor_ladder_edges_match_numpy(pkg, r):
+    """Both sides of every edge of launch_posterior_factor's ladder (FACTOR_LADDER names the kernel of each rank): M and α of one
+    posterior through icp_proposal_posterior — the `wide` model of rank r, identity pose, every vertex sampled, equal noise along and
+    across the normal, so that Σ_i = σ²I — against the numpy long form over the correspondences the call reports, at the parity
+    tests' 1e-9 of the largest entry (test_gpu_parity.py: REL).  icpPosterior raises unless the call's status is 0."""
+    model = DS.designed_model(pkg, r, DS.wide(r), 1000 * r)[0]
+    ctx = pkg.IcpContext(model, model.reference_mesh, device=0)
+    prop = pkg.NonRigidIcpProposal(ctx, 0.1, 2.0, 2.0, model.n_points, "ModelSampling", False)
+    post = prop.icpPosterior(make_theta(model, r, pose=False))
+    keep = post.keep.astype(bool)
+    assert keep.sum() >= model.n_points // 2
+    lf = LF.long_form(model, post.corr_id[keep], post.corr_point[keep], sigma2=4.0)
+    err_M = float(np.abs(post.M - lf["M"]).max() / np.abs(lf["M"]).max())
+    err_alpha = float(np.abs(post.alpha - lf["alpha"]).max() / np.abs(lf["alpha"]).max())
+    print(f"rank {r} {FACTOR_LADDER[r]}: M {err_M:.2e} alpha {err_alpha:.2e} kept {int(keep.sum())}")
+    assert err_M < 1e-9 and err_alpha < 1e-9
+    assert all(v == 0 for v in pkg._native.runtime_stats(ctx.h).values())
+    prop.close()
     ctx.close()

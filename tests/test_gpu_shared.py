@@ -2,7 +2,7 @@
 
 The merged step orders its streams ON THE DEVICE: a step's first launch waits for the decomposition it draws from, a decomposition
 started ahead waits for the regression's word, a batched step's gate waits for its decompositions to become resident
-(kernels_step.hip, kernels_posterior.hip).  Those waits rely on the waited-for launch becoming resident while the waiting one spins —
+(kernels_step.hip, kernels_eigen.hip).  Those waits rely on the waited-for launch becoming resident while the waiting one spins —
 true on an idle device, not guaranteed when a second tenant's workgroups hold the compute units (the realistic case of "8 chains on 8
 GPUs" started by a JVM pool next to other jobs).  Every wait has a time-out that ends in a slower, equivalent schedule and a counter
 (icp_ctx_runtime_stats).  This test runs the metric chain (BASELINE.json configs[1], 58k-vertex target) and a 16-chain batch while
