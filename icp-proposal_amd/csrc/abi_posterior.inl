@@ -18,6 +18,8 @@ struct PosteriorEntry {
                                   // of ranks <= 64 record none: their consumers wait for the completion word on the device, and
                                   // an event record is 2-3 µs of host time on the accepted path)
   int done_value = 0;             // … and what the entry's word in icp_proposal::eig_words holds once it is complete (0: none)
+  bool planned = false, planned_cold = false;  // the place in the proposal's count of decompositions that a speculative launch would
+  int planned_seq = 0;                         // have taken, kept for the ordinary one (icp_proposal::plan_eigen)
   uint64_t stamp = 0;
   DBuf<int> id, aux;
   DBuf<double> pt, nhat, e;
@@ -99,6 +101,8 @@ struct icp_proposal {
   PosteriorEntry& fresh_entry();
   void alloc_entry(PosteriorEntry& e);
   void prepare_eigen(PosteriorEntry& e, EigenRequest* rq);
+  void plan_eigen(PosteriorEntry& e);
+  PosteriorEntry* plan_entry = nullptr;
   void ensure_eigen(PosteriorEntry& e);  // enqueue on the context's eigen stream (no-op if done or in flight)
   // … or on `es` (eig_stream / eig_stream2) with that stream's work buffer; the caller has made `es` wait for the entry's M
   // part: as launch_posterior_eigen's — 1 issues the chain's head, 2 what follows it and the event behind everything
@@ -256,6 +260,7 @@ PosteriorEntry& icp_proposal::fresh_entry() {
   e.valid = false;
   e.eig_valid = false;
   e.eig_checked = false;
+  e.planned = false;
   return e;
 }
 
@@ -395,10 +400,16 @@ void icp_proposal::prepare_eigen(PosteriorEntry& e, EigenRequest* rq) {
   if (!e.eig_done) HIP_OK(hipEventCreateWithFlags(&e.eig_done, hipEventDisableTiming));
   // the kernel reads all of Vwarm before it writes V, so the two may be the same buffer (a reused memo entry)
   h_eig[e.status_off / 3] = -1;  // in flight; the decomposition stores its status here when it ends
-  e.done_value = ++eig_seq;
   // Every decomposition inherits the (tiny) deviation from orthogonality of the basis it starts from and adds that of its own
   // first-order correction (<= 1e-11): every 128th starts cold, from the identity, which puts an end to the accumulation.
-  if (((eig_seq + 1) & 127) == 0) warm_valid = false;
+  if (e.planned) {  // (counted when its state was proposed: plan_eigen)
+    e.planned = false;
+    e.done_value = e.planned_seq;
+    if (e.planned_cold) warm_valid = false;
+  } else {
+    e.done_value = ++eig_seq;
+    if (((eig_seq + 1) & 127) == 0) warm_valid = false;
+  }
   *rq = EigenRequest{e.M.p, warm_valid ? warm_ptr : nullptr, e.V.p, e.Vt.p, e.S.p, work.p, status.p + e.status_off + 2, nullptr,
                      h_eig + e.status_off / 3, eig_words.p + e.status_off / 3, e.done_value, ctx->sqrt_lambda.p};
   rq->root = sampler == ICP_SAMPLER_CHOLESKY_ROOT;
@@ -510,6 +521,7 @@ void icp_proposal::await_eigen(PosteriorEntry& e) {
 void icp_proposal::speculate_eigen(PosteriorEntry& e, const PosteriorEntry& cur, int splits, int half, const int* ready, int ready_seq,
                                    EigenSpec* spec_out, EigenRequest* rq_out) {
   e.eig_event_valid = false;
+  e.planned = false;
   ++spec_seq;
   *spec_out = EigenSpec{splits, h_cancel + (spec_seq & 15), spec_seq, ready, ready_seq, ctx->profiling ? ctx->d_wait_ticks.p + 1 : nullptr};
   // warm start: the basis of the current state's posterior (complete, or ahead of this launch on the same stream)
@@ -525,8 +537,26 @@ void icp_proposal::speculate_eigen(PosteriorEntry& e, const PosteriorEntry& cur,
   spec_entry = &e;
 }
 
+// Speculation switched off (ICP_NO_SPECULATION, ICP_SPECULATION=0) in a step that would otherwise have started the decomposition of
+// the proposed state ahead: nothing is launched, but the entry takes the place in the proposal's count that the launch would have
+// had.  Every 128th decomposition starts cold; counted per launch alone, the cold starts would fall on other steps with the switch
+// than without it, and the two chains would differ in their last bits (a cold and a warm decomposition of one matrix agree to
+// ~1e-11).  An accepted state's ordinary decomposition (prepare_eigen, in the next step) starts as the speculative one would have;
+// a rejected state's place lapses, like a cancelled launch's (resolve_speculation).
+void icp_proposal::plan_eigen(PosteriorEntry& e) {
+  e.planned = true;
+  e.planned_cold = (eig_seq & 127) == 127;  // (see speculate_eigen)
+  e.planned_seq = ++eig_seq;
+  plan_entry = &e;
+}
+
 // the caller's next current state decides the fate of the decomposition started for the last proposed state
 void icp_proposal::resolve_speculation(const double* theta_cur) {
+  if (plan_entry) {
+    PosteriorEntry& pe = *plan_entry;
+    plan_entry = nullptr;
+    if (!(pe.valid && std::memcmp(pe.theta.data(), theta_cur, sizeof(double) * (10 + (size_t)ctx->r)) == 0)) pe.planned = false;
+  }
   if (!spec_entry) return;
   PosteriorEntry& e = *spec_entry;
   spec_entry = nullptr;

@@ -526,12 +526,18 @@ int icp_chain_step(icp_evaluator* e, int32_t n_props, icp_proposal* const* props
     for (int i = 0; i < 16; ++i) c.h_res[i] = 0.0;
     for (int i = 0; i < 16; ++i) c.h_status[i] = 0;
 
-    // Adaptive (speculation_mode): an accepted step finds its basis ≈ 50 µs earlier; a rejected one has paid one launch
-    // (≈ 3 µs of host time, a few CUs for at most one sweep) for nothing — worth it unless next to nothing is accepted
-    // (measured: 8.3k against 7.4k it/s over a chain's first 20 steps, 13.6k against 13.7k at one acceptance in three).
+    // Adaptive (speculation_mode): an accepted step finds its basis ≈ 50 µs earlier; a rejected one has paid one launch for
+    // nothing: ≈ 3 µs of host time, a few CUs — and the eigen stream, which the next decomposition shares, until the launch has
+    // seen its cancel word.  The kernel looks at the word before it starts and every eight rounds (≈ 3 µs) of the iteration:
+    // the launch behind a rejected step then starts 0-8 µs after its input (median; 13-25 µs when the word was looked at once
+    // per sweep: profiles/spec_cancel_lag.md).  Worth it unless next to nothing is accepted (measured then: 8.3k against 7.4k
+    // it/s over a chain's first 20 steps).
     const int spec_mode = speculation_mode();
-    const bool speculate = (spec_mode == 1 || (spec_mode == 2 && e->acc_ema >= 0.1)) && !c.speculation_off &&
-                           g_live_contexts.load(std::memory_order_relaxed) <= 2 && n_props > 0 && eigen_speculation_supported(r);
+    const bool spec_possible = !c.speculation_off && g_live_contexts.load(std::memory_order_relaxed) <= 2 && n_props > 0 &&
+                               eigen_speculation_supported(r);
+    const bool speculate = (spec_mode == 1 || (spec_mode == 2 && e->acc_ema >= 0.1)) && spec_possible;
+    // switched off where the default would speculate: the decompositions keep their places in the count (plan_eigen)
+    const bool plan_only = spec_mode == 0 && e->acc_ema >= 0.1 && spec_possible;
     // test hook: the speculative decompositions wait for a word that never comes, time out and are repeated
     static const int starve = dev_env("ICP_TEST_STARVE_SPECULATION") ? (1 << 24) : 0;
     const int step_seq = ++c.step_seq;
@@ -566,6 +572,8 @@ int icp_chain_step(icp_evaluator* e, int32_t n_props, icp_proposal* const* props
       for (int i = 0; i < n_props; ++i) props[i]->speculate_eigen(*ep[i], *ec[i], F.splits[i], F.mpart_half[i], c.d_done.p + 2, step_seq + starve, &specs[i], &rqs[i]);
       const hipStream_t es = eigen_stream_for(c, c.eig_stream.get());
       launch_posterior_eigen_pair(es, r, c.sqrt_lambda.p, n_props, rqs);  // (no event: completion words, see start_decompositions)
+    } else if (plan_only) {
+      for (int i = 0; i < n_props; ++i) props[i]->plan_eigen(*ep[i]);
     }
     // the caller's outcome-independent host work runs beside the device — first of all the pre-launch of the next step's
     // first half (under the rejection assumption), which the device can start as soon as the finish launch above has

@@ -259,8 +259,8 @@ size_t eigen_work_doubles(int r);  // size of `work`
 //   splits   > 0: `M` points at the split-K partials of the regression launch (splits × (r+1)² row-major; lower triangle
 //            used, identity not yet added) and the kernel sums them itself, in the order the factorisation does — the same
 //            values as the finished r×r M, available one launch earlier
-//   cancel   pinned host word, polled once per sweep: the decomposition gives up (writes nothing) once *cancel == seq
-//            (seq != 0)
+//   cancel   pinned host word, looked at before the start and every eight rounds of the iteration: the decomposition gives up
+//            (writes nothing) within about ten rounds of *cancel == seq (seq != 0)
 //   ready    device word raised (to ready_seq or beyond) by the regression launch when the partials are complete: the
 //            decomposition is enqueued without a stream dependency on that launch and waits for the word itself
 constexpr int kEigenGaveUp = 3;  // pinned status of a speculative decomposition whose input never arrived

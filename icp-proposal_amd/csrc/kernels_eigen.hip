@@ -353,12 +353,22 @@ constexpr int kEigMetaCorr = 7;          // meta word: the producer left a first
 constexpr int kEigMetaMu = 64;           // (double*)meta + this: the final diagonal, by position
 constexpr int kEigMetaXchg = 128;        // (double*)meta + this: [2 workgroups][64 values | 64 rows] sign candidates
 
+constexpr unsigned long long kEigenWaitTicks = 500000;  // 5 ms of s_memrealtime (100 MHz): the bound of every device-side wait here
+constexpr int kPwGaveUp = (int)0x80000000;     // never published: a replay workgroup's own mark on the word it acts on
+
 __device__ __forceinline__ void sc1_store(double* p, double v) { __hip_atomic_store(p, v, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT); }
 __device__ __forceinline__ double sc1_load(const double* p) { return __hip_atomic_load(p, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT); }
 
+// A replay workgroup that waited in vain: the host learns it from the pinned status and repeats the decomposition the ordinary way
+// (chain_step_record), and the basis that was never written is marked so that no later decomposition takes it for a warm start
+__device__ __forceinline__ void eigen_replay_gave_up(int* host_status, double* Vout) {
+  if (host_status) __hip_atomic_store(host_status, kEigenGaveUp, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_SYSTEM);
+  Vout[0] = __builtin_nan("");
+}
+
 __device__ void eigen_replay_consumer(int r, const double* Vwarm, const double* rotlog, int* meta, const double* xcorr /* [n2][n2] */,
                                       double* Vout, double* Vtout, double* Sout, int launch_id, int me, int nb, int* done_word,
-                                      int done_value) {
+                                      int done_value, int* host_status, bool awaits_input) {
   __shared__ int s_pw;
   const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
   const int n2 = (r + 1) & ~1, m = n2 >> 1;
@@ -375,10 +385,15 @@ __device__ void eigen_replay_consumer(int r, const double* Vwarm, const double* 
   bool aborted = false;
   for (;;) {
     if (tid == 0) {  // follow the producer (relaxed polls: an acquiring load would invalidate this CU's L1 every time round)
+      // No news for 5 ms (the producer publishes every few rounds, a few µs apart) — twice that before the first news of a launch
+      // whose producer may itself wait 5 ms for its input: the decomposition is dropped as if it had been aborted, and the
+      // pinned status says so (see eigen_replay_gave_up)
+      const unsigned long long t0 = __builtin_amdgcn_s_memrealtime(), limit = (awaits_input && done == 0) ? 2 * kEigenWaitTicks : kEigenWaitTicks;
       int pw;
       for (;;) {
         pw = __hip_atomic_load(meta, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
         if (((pw >> kPwIdShift) & kPwIdMask) == launch_id && ((pw & kPwRoundsMask) > done || (pw & (kPwAbort | kPwFinished)))) break;
+        if (__builtin_amdgcn_s_memrealtime() - t0 > limit) { pw = kPwAbort | kPwGaveUp; break; }
         __builtin_amdgcn_s_sleep(2);
       }
       s_pw = pw;
@@ -388,7 +403,11 @@ __device__ void eigen_replay_consumer(int r, const double* Vwarm, const double* 
     }
     __syncthreads();
     const int pw = s_pw;
-    if (pw & kPwAbort) { aborted = true; break; }  // cancelled decomposition: V stays untouched
+    if (pw & kPwAbort) {  // cancelled decomposition: V stays untouched
+      aborted = true;
+      if ((pw & kPwGaveUp) && tid == 0) eigen_replay_gave_up(host_status, Vout);
+      break;
+    }
     const int avail = pw & kPwRoundsMask;
     while (done < avail) {
       const int n = min(avail - done, kReplayStageRounds);
@@ -495,16 +514,23 @@ __device__ void eigen_replay_consumer(int r, const double* Vwarm, const double* 
       s_rank[tid] = rank;
       if (me == 0 && rank < r) sc1_store(Sout + rank, 1.0 / mi);
     }
+    bool lost = false;  // the other workgroup never came to the exchange (it gave up on the producer at the last moment)
     if (nb > 1) {  // exchange with the other workgroup: message out (write-through, drained), flag up; its flag, its message
       asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
       __syncthreads();
       const int o = 1 - me;
       if (tid == 0) {
         __hip_atomic_store(meta + 2 + me, launch_id, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-        while (__hip_atomic_load(meta + 2 + o, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT) != launch_id) __builtin_amdgcn_s_sleep(1);
+        const unsigned long long t0 = __builtin_amdgcn_s_memrealtime();
+        while (__hip_atomic_load(meta + 2 + o, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT) != launch_id) {
+          if (__builtin_amdgcn_s_memrealtime() - t0 > kEigenWaitTicks) { s_pw = kPwAbort | kPwGaveUp; break; }
+          __builtin_amdgcn_s_sleep(1);
+        }
       }
       __syncthreads();
-      if (tid < n2) {
+      lost = (s_pw & kPwGaveUp) != 0;
+      if (lost && tid == 0) eigen_replay_gave_up(host_status, Vout);
+      if (tid < n2 && !lost) {
         const double v = sc1_load(xchg + o * 128 + tid);
         const int kk = (int)sc1_load(xchg + o * 128 + 64 + tid);
         double bv = s_bv[tid];
@@ -515,7 +541,7 @@ __device__ void eigen_replay_consumer(int r, const double* Vwarm, const double* 
       if (tid == 0) __hip_atomic_store(meta + 2 + o, 0, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);  // read: back to idle (ids repeat after 2047 launches)
     }
     __syncthreads();
-    if (act) {  // (write-through stores: nothing to write back before the completion word)
+    if (act && !lost) {  // (write-through stores: nothing to write back before the completion word)
       const int p0 = 2 * q, p1 = 2 * q + 1, r0 = s_rank[p0], r1 = s_rank[p1];
       const bool n0 = s_bv[p0] < 0.0, n1 = s_bv[p1] < 0.0;
       if (ka < r) {
@@ -602,7 +628,8 @@ __global__ void __launch_bounds__(1024) k_posterior_eigen_rr(int r, const double
   int* host_status = pb.host_status;
   if (Vwarm && !(Vwarm[0] == Vwarm[0])) Vwarm = nullptr;  // the basis of a decomposition that gave up (see below): cold start
   if (local != 0) {
-    eigen_replay_consumer(r, Vwarm, rotlog, meta, vpos, Vout, Vtout, Sout, launch_id, local - 1, per - 1, pb.done_word, pb.done_value);
+    eigen_replay_consumer(r, Vwarm, rotlog, meta, vpos, Vout, Vtout, Sout, launch_id, local - 1, per - 1, pb.done_word, pb.done_value,
+                          host_status, spec.ready != nullptr);
     return;
   }
   __shared__ double s_red[16], s_red2[16];
@@ -623,6 +650,10 @@ __global__ void __launch_bounds__(1024) k_posterior_eigen_rr(int r, const double
   // idle wave fetches it while the others work, and the block looks at the copy at the next convenient barrier)
   const bool is_poll = spec.cancel != nullptr && tid == 64 * kRrPollWave + 63;
   if (tid == 0) s_cancel = 0;
+  // (the first look at the word is issued here and used behind the staging below: a launch that starts after it was cancelled —
+  // the eigen stream was busy — leaves without a wait)
+  int polled = 0x80000000;
+  if (is_poll) polled = __hip_atomic_load(spec.cancel, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_SYSTEM);
   // ---- N = D⁻¹ M D⁻¹ (symmetrised), padded; Vt = (warm start or identity)ᵀ, padded with zeros
   for (int e = tid; e < szV; e += nt) LDS_VT(e) = 0.0;
   __syncthreads();
@@ -658,24 +689,38 @@ __global__ void __launch_bounds__(1024) k_posterior_eigen_rr(int r, const double
     LDS_VT(j * ldk + i) = Vwarm ? Vwarm[e] : (i == j ? 1.0 : 0.0);
   }
   EIG_STAMP(50);
-  if (spec.ready) {  // enqueued ahead of its input: wait for the launch that announces it (or for the cancellation).
-    // Should that launch not come forward within 5 ms — kernels of different streams forced to run one at a time by a
-    // tool, say — give up and say so in the pinned status: the host then repeats the decomposition the ordinary way.
+  if (spec.ready || spec.cancel) {  // (uniform) a speculative launch: cancelled already?  Enqueued ahead of its input (`ready`):
+    // wait for the launch that announces it, or for the cancellation.  Should that launch not come forward within 5 ms — kernels
+    // of different streams forced to run one at a time by a tool, say — give up and say so in the pinned status: the host then
+    // repeats the decomposition the ordinary way.
     if (is_poll) {
-      const long long t0 = __builtin_amdgcn_s_memrealtime();  // 100 MHz
-      for (;;) {
-        if (__hip_atomic_load(spec.ready, __ATOMIC_ACQUIRE, __HIP_MEMORY_SCOPE_AGENT) - spec.ready_seq >= 0) break;
-        if (__hip_atomic_load(spec.cancel, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_SYSTEM) == spec.seq) { s_cancel = 1; break; }
-        if (__builtin_amdgcn_s_memrealtime() - t0 > 500000) { s_cancel = 2; break; }
-        __builtin_amdgcn_s_sleep(32);
+      if (polled == spec.seq) s_cancel = 1;  // the word first: an input that is there does not hide it
+      else if (spec.ready) {
+        const unsigned long long t0 = __builtin_amdgcn_s_memrealtime();  // 100 MHz
+        for (;;) {
+          if (__hip_atomic_load(spec.ready, __ATOMIC_ACQUIRE, __HIP_MEMORY_SCOPE_AGENT) - spec.ready_seq >= 0) break;
+          if (__hip_atomic_load(spec.cancel, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_SYSTEM) == spec.seq) { s_cancel = 1; break; }
+          if (__builtin_amdgcn_s_memrealtime() - t0 > kEigenWaitTicks) { s_cancel = 2; break; }
+          __builtin_amdgcn_s_sleep(32);
+        }
+        if (spec.wait_ticks) atomicAdd((unsigned long long*)spec.wait_ticks, (unsigned long long)(__builtin_amdgcn_s_memrealtime() - t0));
       }
-      if (spec.wait_ticks) atomicAdd((unsigned long long*)spec.wait_ticks, (unsigned long long)(__builtin_amdgcn_s_memrealtime() - t0));
     }
     __syncthreads();
-    __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "agent");  // (acquire side for the plain loads of the partials below)
+    if (spec.ready) __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "agent");  // (acquire side for the plain loads of the partials below)
+    if (s_cancel) {  // cancelled (or timed out) before it started: nothing is assembled, nothing is written
+      if (tid == 0) {
+        progress_publish(meta, launch_id, 0, kPwAbort);
+        if (s_cancel == 2) {  // timed out: tell the host, and mark the basis that was never written so that no later
+          // decomposition takes it for a warm start (a NaN in its first entry; a finished decomposition overwrites it)
+          if (host_status) __hip_atomic_store(host_status, kEigenGaveUp, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_SYSTEM);
+          Vout[0] = __builtin_nan("");
+        }
+      }
+      return;
+    }
   }
   EIG_STAMP(51);
-  if (is_poll && !spec.ready && __hip_atomic_load(spec.cancel, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_SYSTEM) == spec.seq) s_cancel = 1;
   if (spec.splits > 0) {
     // M = I + Σ_s partial_s from the split-K partials of the regression launch (lower triangle of (r+1)² matrices, summed in
     // split order from 0.0 like the factorisation does).  One 16-byte piece (row i, columns 2jp, 2jp+1) per thread and row
@@ -743,17 +788,6 @@ __global__ void __launch_bounds__(1024) k_posterior_eigen_rr(int r, const double
     }
   }
   __syncthreads();
-  if (s_cancel) {  // cancelled (or timed out) before it started: nothing is written
-    if (tid == 0) {
-      progress_publish(meta, launch_id, 0, kPwAbort);
-      if (s_cancel == 2) {  // timed out: tell the host, and mark the basis that was never written so that no later
-        // decomposition takes it for a warm start (a NaN in its first entry; a finished decomposition overwrites it)
-        if (host_status) __hip_atomic_store(host_status, kEigenGaveUp, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_SYSTEM);
-        Vout[0] = __builtin_nan("");
-      }
-    }
-    return;
-  }
   EIG_STAMP(1);
   if (Vwarm) {  // A <- Vᵀ A V (nearly diagonal when V diagonalised a nearby posterior) on the f64 matrix cores: one 16×16
     // output tile per wave, the contraction in steps of 4 (v_mfma_f64_16x16x4_f64: lane l supplies A[l&15][l>>4] and
@@ -895,7 +929,7 @@ __global__ void __launch_bounds__(1024) k_posterior_eigen_rr(int r, const double
     if (n_sweeps < first_test && n_sweeps + 1 < max_sweeps) {
       ++n_sweeps;
       EIG_STAMP(3 + 2 * n_sweeps);
-      return s_cancel != 0;
+      return false;
     }
     // this sweep's rotations are in the log (written through; the log wave's own progress stores have landed, too): the
     // replay workgroups may have all of them (published behind the barrier below)
@@ -944,22 +978,43 @@ __global__ void __launch_bounds__(1024) k_posterior_eigen_rr(int r, const double
     if (tid == 0 && n_sweeps < 8) ((double*)(meta + 80))[n_sweeps] = off / dg;  // diagnostic: off(A)²/Σdiag² after each sweep
     ++n_sweeps;
     EIG_STAMP(3 + 2 * n_sweeps);
-    return converged || n_sweeps >= max_sweeps || s_cancel;  // (s_cancel: stored by the poll thread rounds ago)
+    return converged || n_sweeps >= max_sweeps;
   };
-  int cur = 0, polled = 0x80000000;
-  const int poll_use = (n2 - 1) >> 2;
+  // The cancel word of a speculative decomposition, on a fixed schedule of the round counter (whatever the sweeps' length: a
+  // decomposition whose result nobody wants holds the eigen stream, and the next one waits behind it):
+  //   rounds ≡ 0 (mod 8)  the poll wave issues its read of the pinned word — never waited for on the spot, that would hold
+  //                       every wave at the round's barrier for a microsecond or two;
+  //   rounds ≡ 4          … and its last lane stores the outcome to s_cancel, ahead of that round's barrier;
+  //   rounds ≡ 6          every wave reads s_cancel behind the round's barrier and leaves the loop.
+  // Store and read are two barriers apart, and the next store is five rounds behind the read: every wave reads the same value
+  // in the same round (a wave that left a loop of barriers alone would hang the others).  Nothing else in the loop reads s_cancel.
+  const bool cancellable = spec.cancel != nullptr;                                           // (uniform)
+  const bool poll_wave = cancellable && __builtin_amdgcn_readfirstlane(wave) == kRrPollWave;  // (a scalar: real branches below)
+  bool cancelled = false;
+  int cur = 0, word = 0;
   if (max_sweeps > 0)
-    for (;;) {
-      // the poll of a sweep is issued at its start and looked at half a sweep later, when the word has long arrived
-      // (waiting for it on the spot would hold every wave at this round's barrier for a microsecond or two)
-      if (is_poll && (in_sweep >> 1) == 0) polled = __hip_atomic_load(spec.cancel, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_SYSTEM);
-      if (is_poll && (in_sweep >> 1) == poll_use && polled == spec.seq) s_cancel = 1;
+    for (;;) {  // (two rounds per pass: n_rounds is even here)
+      const int phase = n_rounds & 7;
+      if (poll_wave) {
+        if (phase == 0) word = __hip_atomic_load(spec.cancel, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_SYSTEM);
+        if (phase == 4) {
+          // (the wait for the word stays inside this branch — hoisted out of it, every wave would wait for its own memory
+          // operations here, the log wave for the stores it keeps in flight)
+          asm volatile("" : "+v"(word));
+          if (lane == 63 && word == spec.seq) s_cancel = 1;
+        }
+      }
       round(IntC<0>{}); cur = 1;
-      if (++in_sweep == n2 - 1 && sweep_end(cur)) break;
+      if (cancellable && phase == 6) cancelled = __builtin_amdgcn_readfirstlane(s_cancel) != 0;  // (one value: a uniform branch)
+      if (cancelled || (++in_sweep == n2 - 1 && sweep_end(cur))) break;
       round(IntC<1>{}); cur = 0;
       if (++in_sweep == n2 - 1 && sweep_end(cur)) break;
     }
-  if (s_cancel && !converged) {  // given up: no status, no eigenvalues; the replay workgroups drop what they have
+  if (cancelled) {  // given up: no status, no eigenvalues; the replay workgroups drop what they have.  The log wave's stores —
+    // those of the progress word among them — have landed before the barrier behind which the abort word is published: a late
+    // one on top of it would leave the replay workgroups waiting for rounds that never come
+    if (wave == kRrLogWave) asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
+    __syncthreads();
     if (tid == 0) progress_publish(meta, launch_id, n_rounds, kPwAbort);
     return;
   }
