@@ -64,6 +64,10 @@ class RuntimeStats(C.Structure):
                 ("step_redos", C.c_int64), ("gate_timeouts", C.c_int64), ("reserved", C.c_int64 * 3)]
 
 
+class KernelTerm(C.Structure):
+    _fields_ = [("scale", C.c_double), ("sigma", C.c_double), ("A", C.c_double * 9)]
+
+
 # every symbol include/icp_proposal.h declares: name -> (restype, argtypes)
 SIGNATURES = {
     "icp_ctx_create": (C.c_int, [C.POINTER(ModelDesc), C.POINTER(MeshDesc), C.c_int, C.POINTER(C.c_void_p)]),
@@ -121,6 +125,9 @@ SIGNATURES = {
     "icp_posterior_models_many": (C.c_int, [C.c_int32, C.POINTER(C.c_void_p), c_int_p, C.POINTER(c_int_p), C.POINTER(c_double_p),
                                             C.POINTER(c_double_p), C.POINTER(c_double_p), C.POINTER(c_double_p), C.POINTER(c_double_p),
                                             C.POINTER(c_double_p), C.POINTER(c_double_p), C.POINTER(c_double_p), c_int_p]),
+    "icp_gp_models_many": (C.c_int, [C.c_int32, C.c_int, c_int_p, C.POINTER(c_double_p), c_int_p, C.POINTER(C.POINTER(KernelTerm)), c_int_p,
+                                     c_int_p, c_double_p, C.POINTER(c_double_p), C.POINTER(c_double_p), C.POINTER(c_int_p),
+                                     C.POINTER(c_double_p), C.POINTER(c_double_p), c_int_p]),
     "icp_chain_step": (C.c_int, [C.c_void_p, C.c_int32, C.POINTER(C.c_void_p), C.c_int32, c_double_p, c_double_p, c_double_p,
                                  c_double_p, c_double_p, c_double_p]),
     "icp_chain_step_batched_issue": (C.c_int, [C.c_int32, C.POINTER(C.c_void_p), C.c_int32, C.POINTER(C.c_void_p), C.POINTER(C.c_int32),

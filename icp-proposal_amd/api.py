@@ -1116,3 +1116,118 @@ def posterior_models(contexts, vertex_ids, points, sigma2=None, covariances=None
             for w in want:
                 del out[b][w]
     return out
+
+
+_GP_WANT = ("variance", "basis", "pivots", "residual")
+GP_MAX_PIVOTS, GP_MAX_TERMS = 256, 8
+
+
+def _psd3(a):
+    """exactly symmetric, positive semi-definite (principal minors in closed form, a rounding's slack) and not zero — the library's test"""
+    if not np.all(np.isfinite(a)) or a[0, 1] != a[1, 0] or a[0, 2] != a[2, 0] or a[1, 2] != a[2, 1]:
+        return False
+    p, b, d, e, f, g = a[0, 0], a[0, 1], a[0, 2], a[1, 1], a[1, 2], a[2, 2]
+    eps = 2.0 ** -48
+    if p < 0 or e < 0 or g < 0 or not (p + e + g > 0):
+        return False
+    if p * e - b * b < -eps * (p * e + b * b) or p * g - d * d < -eps * (p * g + d * d) or e * g - f * f < -eps * (e * g + f * f):
+        return False
+    det = (p * (e * g - f * f) - b * (b * g - d * f)) + d * (b * f - d * e)
+    mag = (p * (e * g + f * f) + abs(b) * (abs(b) * g + abs(d * f))) + abs(d) * (abs(b * f) + abs(d) * e)
+    return bool(det >= -eps * mag)
+
+
+def gp_models(meshes, kernels, n_pivots, rank=None, rel_tolerance=0.0, device=0, want=_GP_WANT):
+    """Gaussian-process shape models of analytic kernels on many reference meshes in one call (icp_gp_models_many): what
+    apps/femur/CreateGPModel.scala makes, by Scalismo's pivoted Cholesky approximation instead of the Nyström one.  Item b: the model
+    of kernels[b] — a list of 1..8 data.GaussianKernelTerm, k(x, y) = Σ_t scale_t·exp(−‖x−y‖²/σ_t²)·A_t — on the points of meshes[b] (a
+    data.TriangleMesh), from at most n_pivots[b] <= min(256, 3N) pivots, keeping the leading rank[b] <= n_pivots[b] eigenpairs (None:
+    n_pivots); the pivot loop also stops when the residual trace is <= rel_tolerance[b] · trace(K) or the numerical rank is reached.
+    `kernels`: one list of terms for every mesh, or one list per mesh; n_pivots, rank, rel_tolerance: a number for all, or one per item.
+    `want` names the arrays to fetch.  Returns one (model, info) per item: a data.StatisticalMeshModel (zero mean deformation, columns of
+    squared norm N; None unless "variance" and "basis" are wanted) of the effective rank min(rank, effective pivots), and a dict with
+    "n_pivots" (effective), "rank" (effective), "total_variance" trace(K)/N, "approximated_variance" Σ variance, and the wanted ones of
+    "variance" [rank], "pivots" [effective] (rows 3·vertex + coordinate in the order chosen), "residual" [3N] (the residual diagonal
+    when the loop stopped)."""
+    ms = list(meshes)
+    n = len(ms)
+    if n == 0 or n > 65535:
+        raise ValueError("at least one mesh, at most 65,535 a call")
+    ks = list(kernels)
+    if ks and isinstance(ks[0], _data.GaussianKernelTerm):
+        ks = [ks] * n
+    if len(ks) != n:
+        raise ValueError("one kernel (a list of terms) per mesh, or one for all")
+
+    def per_item(v, name):
+        v = list(v) if isinstance(v, (list, tuple, np.ndarray)) else [v] * n
+        if len(v) != n:
+            raise ValueError(f"{name}: a number, or one per item")
+        return v
+    mp = [int(v) for v in per_item(n_pivots, "n_pivots")]
+    rk = [mp[b] if v is None else int(v) for b, v in enumerate(per_item(rank, "rank"))]
+    tol = [float(v) for v in per_item(rel_tolerance, "rel_tolerance")]
+    want = tuple(want)
+    for w in want:
+        if w not in _GP_WANT:
+            raise ValueError(f"unknown output {w!r}: one of {_GP_WANT}")
+    pts, terms = [], []
+    for b in range(n):
+        p = _f64(ms[b].points)
+        if p.ndim != 2 or p.shape[1] != 3 or p.shape[0] < 1:
+            raise ValueError(f"item {b}: a mesh has points [N, 3]")
+        if not np.all(np.isfinite(p)):
+            raise ValueError(f"item {b}: points contain a non-finite value")
+        if not (1 <= rk[b] <= mp[b] <= min(GP_MAX_PIVOTS, 3 * p.shape[0])):
+            raise ValueError(f"item {b}: 1 <= rank <= n_pivots <= min({GP_MAX_PIVOTS}, 3N)")
+        if not (0.0 <= tol[b] < 1.0):
+            raise ValueError(f"item {b}: rel_tolerance lies in [0, 1)")
+        kb = list(ks[b])
+        if not (1 <= len(kb) <= GP_MAX_TERMS):
+            raise ValueError(f"item {b}: a kernel has 1 to {GP_MAX_TERMS} terms")
+        arr = (nat.KernelTerm * len(kb))()
+        for t, k in enumerate(kb):
+            if not (math.isfinite(k.scale) and k.scale > 0.0 and math.isfinite(k.sigma) and k.sigma > 0.0 and math.isfinite(k.sigma * k.sigma)
+                    and k.sigma * k.sigma > 0.0):
+                raise ValueError(f"item {b}, term {t}: scale and sigma must be finite and positive")
+            a = _f64(k.A)
+            if a.shape != (3, 3) or not _psd3(a):
+                raise ValueError(f"item {b}, term {t}: A must be an exactly symmetric, positive semi-definite, non-zero 3 x 3 matrix")
+            arr[t].scale, arr[t].sigma = k.scale, k.sigma
+            arr[t].A[:] = a.reshape(-1).tolist()
+        pts.append(p)
+        terms.append(arr)
+    shapes = {"variance": lambda b: (rk[b],), "basis": lambda b: (3 * pts[b].shape[0], rk[b]), "pivots": lambda b: (mp[b],),
+              "residual": lambda b: (3 * pts[b].shape[0],)}
+    out = [{w: np.zeros(shapes[w](b), dtype=np.int32 if w == "pivots" else np.float64) for w in want} for b in range(n)]
+    info = np.zeros((n, 4))
+    status = np.zeros(n, dtype=np.int32)
+    outs = [None if w not in want else _ptr_array([o[w] for o in out], nat.c_int_p, _i) if w == "pivots"
+            else _ptr_array([o[w] for o in out]) for w in _GP_WANT]
+    c_terms = (C.POINTER(nat.KernelTerm) * n)(*[C.cast(a, C.POINTER(nat.KernelTerm)) for a in terms])
+    n_pts = np.array([p.shape[0] for p in pts], dtype=np.int32)
+    n_terms = np.array([len(a) for a in terms], dtype=np.int32)
+    a_mp, a_rk, a_tol = np.array(mp, dtype=np.int32), np.array(rk, dtype=np.int32), np.array(tol, dtype=np.float64)
+    rc = nat.lib().icp_gp_models_many(n, int(device), _i(n_pts), _ptr_array(pts), _i(n_terms), c_terms, _i(a_mp), _i(a_rk), _d(a_tol),
+                                      outs[0], outs[1], outs[2], outs[3], _ptr_array(list(info)), _i(status))
+    nat.check(rc, "icp_gp_models_many")
+    res = []
+    for b in range(n):
+        me, re = int(info[b, 0]), int(info[b, 1])
+        d = {"n_pivots": me, "rank": re, "total_variance": float(info[b, 2]), "approximated_variance": float(info[b, 3])}
+        if "variance" in want:
+            d["variance"] = out[b]["variance"][:re].copy()
+        if "pivots" in want:
+            d["pivots"] = out[b]["pivots"][:me].copy()
+        if "residual" in want:
+            d["residual"] = out[b]["residual"]
+        model = None
+        if "variance" in want and "basis" in want:
+            model = _data.StatisticalMeshModel(pts[b], ms[b].cells, np.zeros_like(pts[b]), out[b]["basis"][:, :re], d["variance"])
+        res.append((model, d))
+    return res
+
+
+def gp_model(mesh, kernel, n_pivots, rank=None, rel_tolerance=0.0, device=0, want=_GP_WANT):
+    """One item of gp_models: (model, info) of `kernel` (a list of data.GaussianKernelTerm) on `mesh`."""
+    return gp_models([mesh], [list(kernel)], n_pivots, rank, rel_tolerance, device, want)[0]

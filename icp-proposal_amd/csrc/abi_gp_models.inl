@@ -1,0 +1,361 @@
+// abi_gp_models.inl — C ABI: icp_gp_models_many, Gaussian-process shape models of analytic kernels on many reference meshes
+// (kernels_gp_model.hip; the resident decompositions of kernels_eigen.hip).
+//
+// Item b: the pivoted Cholesky factor L of its kernel matrix, up to n_pivots columns (one launch per pivot step carries every item
+// of the call), then LᵀL = W·Θ·Wᵀ and the model (Θ/N, √N·L·W·Θ^-1/2).  The host synchronises ONCE behind the pivot loop, to read how
+// many columns every item made: that is the rank of its decomposition.  The m-space work then goes through kGpmGroup slots of scratch,
+// a group at a time: the Gram matrices in one launch, the decompositions rank by rank (launch_posterior_eigen_many up to rank 64,
+// launch_posterior_eigen_tridiag_many up to 256, launch_posterior_eigen for ranks 1 and 2 and for a spectrum the side-by-side route
+// could not separate), one refinement step of the eigenvectors and the operands in a launch each, and the group's rows of L·Op through ONE chunk buffer, round by round, one
+// synchronisation per round.  The decompositions see sqrt_lambda ≡ 1 and a Gram matrix scaled by an exact power of two (trace(K) brought
+// into [1, 2)): magnitudes like a posterior's, and θ comes back exactly.  An item's bits depend neither on the other items, nor on
+// their order, nor on how its rows fall into rounds.
+
+namespace {
+constexpr size_t kGpmChunkDoubles = (size_t)ICP_GP_MODELS_CHUNK_BYTES / sizeof(double);
+constexpr int kGpmGroup = 16;       // items whose m-space work is in flight together
+constexpr int kGpmRowQuantum = 48;  // rows of a piece: whole 16-row tiles and whole vertices
+constexpr int kGpmMaxPieces = 32768;
+
+// exactly symmetric and positive semi-definite, by the principal minors of a 3 × 3 in closed form (a rounding's worth of slack:
+// a rank-one A = v·vᵀ has minors that are zero up to rounding); not zero
+bool gpm_psd(const double* A) {
+  for (int i = 0; i < 9; ++i)
+    if (!std::isfinite(A[i])) return false;
+  if (A[1] != A[3] || A[2] != A[6] || A[5] != A[7]) return false;
+  const double a = A[0], b = A[1], d = A[2], e = A[4], f = A[5], g = A[8];
+  const double eps = 0x1p-48;
+  if (a < 0.0 || e < 0.0 || g < 0.0 || !(a + e + g > 0.0)) return false;
+  if (a * e - b * b < -eps * (a * e + b * b) || a * g - d * d < -eps * (a * g + d * d) || e * g - f * f < -eps * (e * g + f * f)) return false;
+  const double det = (a * (e * g - f * f) - b * (b * g - d * f)) + d * (b * f - d * e);
+  const double mag = (a * (e * g + f * f) + std::fabs(b) * (std::fabs(b) * g + std::fabs(d * f))) + std::fabs(d) * (std::fabs(b * f) + std::fabs(d) * e);
+  return det >= -eps * mag;
+}
+
+struct DeviceScope {  // the calling thread's device, put back when the call ends
+  int prev = -1;
+  explicit DeviceScope(int device) {
+    (void)hipGetDevice(&prev);
+    HIP_OK(hipSetDevice(device));
+  }
+  ~DeviceScope() { if (prev >= 0) (void)hipSetDevice(prev); }
+};
+struct StreamScope {
+  hipStream_t st;
+  explicit StreamScope(int device) : st(take_stream(device, false, 0)) {}
+  ~StreamScope() { give_stream(st); }
+};
+}  // namespace
+
+extern "C" {
+
+int icp_gp_models_many(int32_t n_items, int device, const int32_t* n_points, const double* const* points, const int32_t* n_terms,
+                       const icp_kernel_term* const* terms, const int32_t* n_pivots, const int32_t* rank, const double* rel_tolerance,
+                       double* const* variance_out, double* const* basis_out, int32_t* const* pivots_out, double* const* residual_out,
+                       double* const* info_out, int32_t* status) {
+  std::vector<int> item_status;
+  int rc = guard([&] {
+    require(n_items >= 1 && n_items <= 65535, "n_items must lie in [1, 65535]");
+    require(n_points && points && n_terms && terms && n_pivots && rank && status, "null argument");
+    const int B = n_items;
+    // ---- validation, item by item, before the device is touched
+    item_status.assign(B, ICP_OK);
+    std::vector<int> live;
+    for (int b = 0; b < B; ++b) {
+      auto good = [&] {
+        if (!points[b] || !terms[b]) return false;
+        const long long N = n_points[b];
+        if (N < 1 || 3 * N > (long long)INT32_MAX) return false;
+        if (n_terms[b] < 1 || n_terms[b] > kGpmMaxTerms) return false;
+        if (!(rank[b] >= 1 && rank[b] <= n_pivots[b] && n_pivots[b] <= kGpmMaxPivots && (long long)n_pivots[b] <= 3 * N)) return false;
+        if (rel_tolerance && !(rel_tolerance[b] >= 0.0 && rel_tolerance[b] < 1.0)) return false;
+        for (int t = 0; t < n_terms[b]; ++t) {
+          const icp_kernel_term& k = terms[b][t];
+          if (!(std::isfinite(k.scale) && k.scale > 0.0 && std::isfinite(k.sigma) && k.sigma > 0.0 && std::isfinite(k.sigma * k.sigma))) return false;
+          if (!(k.sigma * k.sigma > 0.0) || !gpm_psd(k.A)) return false;
+        }
+        for (long long i = 0; i < 3 * N; ++i)
+          if (!std::isfinite(points[b][i])) return false;
+        return true;
+      };
+      if (good()) live.push_back(b);
+      else item_status[b] = ICP_ERR_INVALID_ARG;
+    }
+    const int n_live = (int)live.size();
+    if (n_live == 0) return;
+
+    int ndev = 0;
+    hipError_t e = hipGetDeviceCount(&ndev);
+    if (e != hipSuccess || ndev <= 0)
+      fail(ICP_ERR_DEVICE, std::string("no usable HIP device (this library has no CPU fallback): ") + hipGetErrorString(e));
+    if (device < 0) {
+      const char* lr = std::getenv("LOCAL_RANK");
+      device = lr ? std::atoi(lr) % ndev : 0;
+    }
+    require(device < ndev, "device ordinal out of range");
+    DeviceScope _dev(device);
+    StreamScope _st(device);
+    hipStream_t st = _st.st;
+
+    // ---- the pivot loop: every item's points, d, L and partials; one record per item
+    std::vector<GpmItem> h_items(n_live);
+    std::vector<size_t> off_pts(n_live + 1, 0), off_L(n_live + 1, 0), off_part(n_live + 1, 0), off_piv(n_live + 1, 0);
+    int nblk_max = 1, m_max = 1;
+    for (int q = 0; q < n_live; ++q) {
+      const int b = live[q], R = 3 * n_points[b], nblk = cdiv(R, kGpmBlockRows);
+      off_pts[q + 1] = off_pts[q] + (size_t)R;
+      off_L[q + 1] = off_L[q] + (size_t)R * n_pivots[b];
+      off_part[q + 1] = off_part[q] + 2 * (size_t)nblk;
+      off_piv[q + 1] = off_piv[q] + (size_t)n_pivots[b];
+      nblk_max = std::max(nblk_max, nblk);
+      m_max = std::max(m_max, (int)n_pivots[b]);
+    }
+    DBuf<double> d_pts, d_d, d_L, d_pmax, d_psum, d_start;
+    DBuf<int> d_pidx, d_meff, d_piv;
+    DBuf<GpmItem> d_items;
+    {
+      std::vector<double> h_pts(off_pts[n_live]);
+      for (int q = 0; q < n_live; ++q) std::memcpy(&h_pts[off_pts[q]], points[live[q]], sizeof(double) * (off_pts[q + 1] - off_pts[q]));
+      NullStreamBatch _nb;
+      d_pts.upload(h_pts.data(), h_pts.size());
+      d_d.alloc(off_pts[n_live]);
+      d_L.alloc(off_L[n_live]);
+      d_pmax.alloc(off_part[n_live]); d_psum.alloc(off_part[n_live]); d_pidx.alloc(off_part[n_live]);
+      d_start.alloc(2 * (size_t)n_live);
+      d_meff.alloc(n_live);
+      d_piv.alloc(off_piv[n_live]);
+      for (int q = 0; q < n_live; ++q) {
+        const int b = live[q];
+        GpmItem& it = h_items[q];
+        it.R = 3 * n_points[b]; it.m = n_pivots[b]; it.n_terms = n_terms[b]; it.nblk = cdiv(it.R, kGpmBlockRows);
+        it.rel_tol = rel_tolerance ? rel_tolerance[b] : 0.0;
+        for (int t = 0; t < kGpmMaxTerms; ++t) {
+          GpmTerm& tm = it.terms[t];
+          tm = GpmTerm{};
+          if (t >= it.n_terms) continue;
+          tm.scale = terms[b][t].scale; tm.sigma2 = terms[b][t].sigma * terms[b][t].sigma;
+          std::memcpy(tm.A, terms[b][t].A, sizeof(tm.A));
+        }
+        it.pts = d_pts.p + off_pts[q]; it.d = d_d.p + off_pts[q]; it.L = d_L.p + off_L[q];
+        it.pmax = d_pmax.p + off_part[q]; it.psum = d_psum.p + off_part[q]; it.pidx = d_pidx.p + off_part[q];
+        it.start = d_start.p + 2 * (size_t)q; it.m_eff = d_meff.p + q; it.pivots = d_piv.p + off_piv[q];
+      }
+      d_items.upload(h_items.data(), h_items.size());
+    }
+    launch_gpm_init(st, n_live, nblk_max, d_items.p);
+    for (int j = 0; j < m_max; ++j) launch_gpm_pivot_step(st, n_live, nblk_max, j, d_items.p);
+    std::vector<int> h_meff(n_live), h_piv(off_piv[n_live]);
+    std::vector<double> h_start(2 * (size_t)n_live);
+    HIP_OK(hipMemcpyAsync(h_meff.data(), d_meff.p, sizeof(int) * h_meff.size(), hipMemcpyDeviceToHost, st));
+    HIP_OK(hipMemcpyAsync(h_start.data(), d_start.p, sizeof(double) * h_start.size(), hipMemcpyDeviceToHost, st));
+    HIP_OK(hipMemcpyAsync(h_piv.data(), d_piv.p, sizeof(int) * h_piv.size(), hipMemcpyDeviceToHost, st));
+    for (int q = 0; q < n_live; ++q)
+      if (residual_out && residual_out[live[q]])
+        HIP_OK(hipMemcpyAsync(residual_out[live[q]], d_d.p + off_pts[q], sizeof(double) * (off_pts[q + 1] - off_pts[q]), hipMemcpyDeviceToHost, st));
+    HIP_OK(hipStreamSynchronize(st));  // the one synchronisation behind the loop: the effective pivot counts
+    for (int q = 0; q < n_live; ++q) {
+      if (h_meff[q] < 1 || h_meff[q] > n_pivots[live[q]]) fail(ICP_ERR_DEVICE, "the pivot loop left no column");  // (A ≠ 0, tolerance < 1: cannot be)
+      if (pivots_out && pivots_out[live[q]]) std::memcpy(pivots_out[live[q]], &h_piv[off_piv[q]], sizeof(int) * (size_t)n_pivots[live[q]]);
+    }
+
+    // ---- m-space: kGpmGroup slots of scratch sized for the call's largest decomposition; the chunk
+    int me_max = 1, rank_max = 1, slabs_max = 1;
+    std::vector<GpmSpace> h_sp(n_live);
+    for (int q = 0; q < n_live; ++q) {
+      const int b = live[q];
+      GpmSpace& s = h_sp[q];
+      s.R = 3 * n_points[b]; s.me = h_meff[q]; s.mp = (s.me + 15) / 16 * 16;
+      s.slab_rows = gpm_slab_rows(s.R); s.slabs = cdiv(s.R, s.slab_rows);
+      s.rank = rank[b]; s.re = std::min(s.rank, s.me); s.ldb = (s.rank + 15) / 16 * 16;
+      s.scale = std::ldexp(1.0, -std::ilogb(h_start[2 * (size_t)q + 1]));
+      s.n_points = (double)n_points[b];
+      s.L = d_L.p + off_L[q];
+      me_max = std::max(me_max, s.me); rank_max = std::max(rank_max, s.rank); slabs_max = std::max(slabs_max, s.slabs);
+    }
+    const int slots = std::min(kGpmGroup, n_live);
+    const int mp_max = (me_max + 15) / 16 * 16, ldb_max = (rank_max + 15) / 16 * 16;
+    const size_t mm = (size_t)me_max * me_max;
+    size_t work_max = 1;
+    for (int q = 0; q < n_live; ++q) work_max = std::max(work_max, eigen_work_doubles(h_sp[q].me));
+    size_t cap = test_chunk_doubles("ICP_TEST_GP_MODELS_CHUNK_DOUBLES", kGpmChunkDoubles);
+    cap = std::max(cap, (size_t)kGpmRowQuantum * rank_max);  // (a piece always fits)
+    DBuf<double> Gpart, G, V, Vt, S, T, Sm, Rm, E, lam, Op, work, ones, d_var, chunk;
+    DBuf<int> d_status, d_order;
+    DBuf<GpmSpace> d_sp;
+    {
+      NullStreamBatch _nb;
+      Gpart.alloc((size_t)slots * slabs_max * mp_max * mp_max);
+      G.alloc(slots * mm); V.alloc(slots * mm); Vt.alloc(slots * mm);
+      S.alloc((size_t)slots * me_max); lam.alloc((size_t)slots * me_max); d_order.alloc((size_t)slots * me_max);
+      T.alloc(slots * mm); Sm.alloc(slots * mm); Rm.alloc(slots * mm); E.alloc(slots * mm);
+      Op.alloc((size_t)slots * mp_max * ldb_max);
+      work.alloc(slots * work_max);
+      d_var.alloc((size_t)n_live * rank_max);
+      chunk.alloc(cap);
+      std::vector<double> h_ones(kGpmMaxPivots, 1.0);
+      ones.upload(h_ones.data(), h_ones.size());
+      d_status.alloc(4 * (size_t)n_live);  // per item {-, sweeps, decomposition, -}
+      d_status.fill_bytes(0);
+      for (int q = 0; q < n_live; ++q) {
+        const int s = q % slots;
+        GpmSpace& sp = h_sp[q];
+        sp.Gpart = Gpart.p + (size_t)s * slabs_max * mp_max * mp_max;
+        sp.G = G.p + s * mm; sp.V = V.p + s * mm;
+        sp.T = T.p + s * mm; sp.Sm = Sm.p + s * mm; sp.Rm = Rm.p + s * mm; sp.E = E.p + s * mm;
+        sp.lam = lam.p + (size_t)s * me_max; sp.order = d_order.p + (size_t)s * me_max;
+        sp.Op = Op.p + (size_t)s * mp_max * ldb_max;
+        sp.variance = d_var.p + (size_t)q * rank_max;
+      }
+      d_sp.upload(h_sp.data(), h_sp.size());
+    }
+    void* pinned_rec = nullptr;
+    pinned_alloc(&pinned_rec, eigen_many_record_bytes(n_live));
+    struct PinnedGuard { void* p; ~PinnedGuard() { pinned_free(p); } } _pg{pinned_rec};
+    size_t rec_used = 0;
+    EigenProblem* rec_base = (EigenProblem*)pinned_rec;
+
+    // the m-space work of items q0 .. q1-1 (one group).  alone: every decomposition by launch_posterior_eigen, which falls back to the
+    // Jacobi iteration on the device where the multisection gives up.
+    auto run_mspace = [&](int q0, int q1, bool alone) {
+      const int n = q1 - q0;
+      int gmp = 16, gldb = 16, gslabs = 1;
+      for (int q = q0; q < q1; ++q) {
+        gmp = std::max(gmp, h_sp[q].mp); gldb = std::max(gldb, h_sp[q].ldb); gslabs = std::max(gslabs, h_sp[q].slabs);
+      }
+      HIP_OK(hipMemsetAsync(work.p, 0, sizeof(double) * work_max * (size_t)std::min(n, slots), st));  // (the decompositions' progress words)
+      launch_gpm_gram(st, n, gmp, gslabs, d_sp.p + q0);
+      std::vector<int> order(n);  // decompositions, rank by rank
+      for (int i = 0; i < n; ++i) order[i] = q0 + i;
+      std::stable_sort(order.begin(), order.end(), [&](int x, int y) { return h_sp[x].me < h_sp[y].me; });
+      for (int i0 = 0; i0 < n;) {
+        int i1 = i0;
+        const int r = h_sp[order[i0]].me;
+        while (i1 < n && h_sp[order[i1]].me == r) ++i1;
+        std::vector<EigenRequest> rq;
+        for (int i = i0; i < i1; ++i) {
+          const int q = order[i], s = q % slots;
+          rq.push_back(EigenRequest{G.p + s * mm, nullptr, V.p + s * mm, Vt.p + s * mm, S.p + (size_t)s * me_max, work.p + s * work_max,
+                                    d_status.p + 4 * (size_t)q + 2, nullptr, nullptr, nullptr, 0, ones.p});
+        }
+        const int m = i1 - i0;
+        bool done = false;
+        if (!alone) {
+          if (eigen_tridiag_many_supported(r)) {
+            launch_posterior_eigen_tridiag_many(st, r, m, rq.data(), nullptr);
+            done = true;
+          } else if (launch_posterior_eigen_many(st, r, m, rq.data(), rec_base + rec_used, nullptr) >= 0) {
+            rec_used += (size_t)m;
+            done = true;
+          }
+        }
+        if (!done)
+          for (const EigenRequest& e : rq) launch_posterior_eigen(st, r, e.M, e.sqrt_lambda, nullptr, e.V, e.Vt, e.S, e.work, e.status);
+        i0 = i1;
+      }
+      launch_gpm_refine(st, n, gmp, d_sp.p + q0);
+      launch_gpm_operand(st, n, gmp, gldb, d_sp.p + q0);
+    };
+    // the rows of the group's bases through the chunk buffer: pieces that fill it are a round (product, copies back, synchronisation)
+    auto run_rounds = [&](int q0, int q1) {
+      struct Back { double* dev; double* host; size_t n; };
+      std::vector<GpmPiece> pcs;
+      std::vector<Back> back;
+      DBuf<GpmPiece> d_pcs;
+      size_t used = 0;
+      int rows_max = 0, tiles_max = 0;
+      auto flush = [&] {
+        if (pcs.empty()) return;
+        {
+          NullStreamBatch _nb;
+          d_pcs.upload(pcs.data(), pcs.size());
+        }
+        launch_gpm_gemm(st, (int)pcs.size(), rows_max, tiles_max, d_pcs.p);
+        HostCopies cp;
+        for (const Back& k : back) cp.add(k.dev, k.host, k.n);
+        cp.issue(st, false);
+        HIP_OK(hipStreamSynchronize(st));
+        pcs.clear(); back.clear();
+        used = 0; rows_max = 0; tiles_max = 0;
+      };
+      for (int q = q0; q < q1; ++q) {
+        const int b = live[q];
+        if (!(basis_out && basis_out[b])) continue;
+        const GpmSpace& sp = h_sp[q];
+        const size_t per_q = (size_t)kGpmRowQuantum * sp.rank;
+        for (int row0 = 0; row0 < sp.R;) {
+          if (cap - used < per_q || (int)pcs.size() == kGpmMaxPieces) flush();
+          const size_t fit = (cap - used) / per_q * kGpmRowQuantum;
+          const int rows = (int)std::min<size_t>(fit, (size_t)(sp.R - row0));
+          GpmPiece pc{};
+          pc.L = sp.L; pc.Op = sp.Op; pc.R = sp.R; pc.me = sp.me; pc.rank = sp.rank; pc.ldb = sp.ldb; pc.row0 = row0; pc.rows = rows;
+          pc.out = chunk.p + used;
+          used += (size_t)rows * sp.rank;
+          back.push_back(Back{pc.out, basis_out[b] + (size_t)row0 * sp.rank, (size_t)rows * sp.rank});
+          rows_max = std::max(rows_max, rows);
+          tiles_max = std::max(tiles_max, sp.ldb / 16);
+          pcs.push_back(pc);
+          row0 += rows;
+        }
+      }
+      flush();
+    };
+
+    std::vector<double> h_var((size_t)n_live * rank_max);
+    std::vector<int> h_st(4 * (size_t)n_live);
+    auto fetch_small = [&] {
+      HIP_OK(hipMemcpyAsync(h_var.data(), d_var.p, sizeof(double) * h_var.size(), hipMemcpyDeviceToHost, st));
+      HIP_OK(hipMemcpyAsync(h_st.data(), d_status.p, sizeof(int) * h_st.size(), hipMemcpyDeviceToHost, st));
+      HIP_OK(hipStreamSynchronize(st));
+    };
+    for (int q0 = 0; q0 < n_live; q0 += slots) {
+      const int q1 = std::min(n_live, q0 + slots);
+      run_mspace(q0, q1, false);
+      run_rounds(q0, q1);
+    }
+    fetch_small();
+    // a spectrum the side-by-side decomposition could not separate (equal eigenvalues: an isotropic kernel has them in threes): that
+    // item again, on its own
+    bool again = false;
+    for (int q = 0; q < n_live; ++q) {
+      if (h_st[4 * q + 2] == 0) continue;
+      {
+        NullStreamBatch _nb;
+        HIP_OK(hipMemset(d_status.p + 4 * (size_t)q, 0, sizeof(int) * 4));
+      }
+      run_mspace(q, q + 1, true);
+      run_rounds(q, q + 1);
+      again = true;
+    }
+    if (again) fetch_small();
+    for (int q = 0; q < n_live; ++q) {
+      const int b = live[q];
+      const GpmSpace& sp = h_sp[q];
+      const double* var = &h_var[(size_t)q * rank_max];
+      bool ok = h_st[4 * q + 2] == 0;
+      for (int j = 0; ok && j < sp.re; ++j) ok = std::isfinite(var[j]) && var[j] > 0.0;
+      if (!ok) {
+        item_status[b] = ICP_ERR_NOT_FINITE;
+        const size_t R = (size_t)sp.R;
+        if (variance_out && variance_out[b]) std::fill(variance_out[b], variance_out[b] + sp.rank, (double)NAN);
+        if (basis_out && basis_out[b]) std::fill(basis_out[b], basis_out[b] + R * sp.rank, (double)NAN);
+        if (info_out && info_out[b]) std::fill(info_out[b], info_out[b] + 4, (double)NAN);
+        continue;
+      }
+      if (variance_out && variance_out[b]) std::memcpy(variance_out[b], var, sizeof(double) * (size_t)sp.rank);
+      if (info_out && info_out[b]) {
+        double sum = 0.0;
+        for (int j = 0; j < sp.re; ++j) sum += var[j];
+        info_out[b][0] = (double)sp.me; info_out[b][1] = (double)sp.re;
+        info_out[b][2] = h_start[2 * (size_t)q + 1] / sp.n_points; info_out[b][3] = sum;
+      }
+    }
+  });
+  if (rc != ICP_OK) return rc;
+  return report_item_status(n_items, item_status, status, [](int code) {
+    return code == ICP_ERR_INVALID_ARG ? "an item is outside the limits: 1 <= rank <= n_pivots <= min(256, 3N), 1..8 terms with scale > 0, sigma > 0 "
+                                         "and a symmetric positive semi-definite A, finite points, 0 <= rel_tolerance < 1"
+                                       : "the decomposition of an item's Gram matrix did not converge";
+  });
+}
+
+}  // extern "C"

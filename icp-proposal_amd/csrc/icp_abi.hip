@@ -22,6 +22,7 @@
 #include "abi_log_values_many.inl"  // C ABI: icp_evaluator_log_values_many (log values of many states under many evaluators, kernels_evaluate.hip)
 #include "abi_registration_maps.inl"  // C ABI: icp_registration_maps_many / icp_distance_summaries_many (per-vertex registration maps and chain summaries, kernels_maps.hip)
 #include "abi_posterior_models.inl"  // C ABI: icp_posterior_models_many (posterior shape models of given correspondences, kernels_posterior_model.hip)
+#include "abi_gp_models.inl"  // C ABI: icp_gp_models_many (Gaussian-process shape models from analytic kernels by pivoted Cholesky, kernels_gp_model.hip)
 #include "abi_step.inl"  // the merged step (five launches): fronts, speculative decompositions, icp_chain_step / _prelaunch
 #include "abi_wide.inl"  // the wide step's host side (kernels_wide.hip)
 #include "abi_batched.inl"  // C ABI: icp_chain_step_batched_issue / _collect / _abandon

@@ -879,4 +879,56 @@ void launch_pm_operand(hipStream_t st, int n, int rmax, const PmItem* items);
 void launch_pm_gemm(hipStream_t st, int n_pieces, int rows_max, int col_tiles_max, const PmPiece* pieces);
 void launch_pm_point_variance(hipStream_t st, int n_pieces, int rows_max, const PmPiece* pieces);
 
+// ---- Gaussian-process shape models from analytic kernels (kernels_gp_model.hip; icp_gp_models_many)
+constexpr int kGpmMaxTerms = 8;     // kernel terms per item
+constexpr int kGpmMaxPivots = 256;  // what the resident decompositions serve
+constexpr int kGpmBlockRows = 256;  // rows of K a workgroup of the pivot loop owns: an item's partials are a function of its size alone
+constexpr int kGpmMaxSlabs = 32;    // row slabs of an item's Gram matrix, at most
+struct GpmTerm { double scale, sigma2, A[9]; };  // scale · exp(−‖x−y‖² / sigma2) · A
+struct GpmItem {        // one item's record (device), the same for every launch of the call
+  int R, m, n_terms, nblk;  // rows 3N; pivots asked for; kernel terms; workgroups of the pivot loop = cdiv(R, kGpmBlockRows)
+  double rel_tol;
+  GpmTerm terms[kGpmMaxTerms];
+  const double* pts;    // [R]
+  double* d;            // [R] residual diagonal
+  double* L;            // [m][R]: column j of the factor at L + j·R (the rows of a column are neighbours)
+  double* pmax;         // [2][nblk] partial maxima of d, per workgroup; the halves change roles every step
+  double* psum;         // [2][nblk] partial sums
+  int* pidx;            // [2][nblk] rows of the partial maxima
+  double* start;        // [2] max d and Σ d = trace(K) at the start (written by step 0)
+  int* m_eff;           // [1] columns made
+  int* pivots;          // [m]
+};
+struct GpmSpace {       // one item's m-space record (device): Gram matrix, decomposition, right operand
+  const double* L;
+  int R, me, mp, slab_rows, slabs;  // rows; m_eff; m_eff rounded up to 16; rows of a slab of the Gram sum; slabs
+  int rank, re, ldb;    // columns asked for; effective rank; rank rounded up to 16
+  double scale;         // exact power of two the Gram matrix is multiplied by in front of the decomposition
+  double n_points;      // N
+  double* Gpart;        // [slabs][mp][mp] lower tiles
+  double* G;            // [me][me] scale · LᵀL, exactly symmetric
+  const double* V;      // [me][me] eigenvectors (columns) as the decomposition leaves them
+  double* T;            // [me][me] G·V, then the refined eigenvectors W
+  double* Sm;           // [me][me] VᵀGV, exactly symmetric
+  double* Rm;           // [me][me] I − VᵀV, exactly symmetric
+  double* E;            // [me][me] the refinement's correction: W = V·(I + E)
+  double* lam;          // [me] refined eigenvalues of G, in the decomposition's order
+  int* order;           // [me] order[j] = the index of the j-th largest of lam (ties: the lower index)
+  double* Op;           // [mp][ldb] = W·Θ^-1/2·√N, zero padding
+  double* variance;     // [rank] θ/N descending, zero behind re
+};
+struct GpmPiece {       // rows row0 .. row0+rows-1 of one item's L·Op, resident in the chunk buffer (device)
+  const double* L; const double* Op;
+  int R, me, rank, ldb, row0, rows;
+  double* out;          // [rows][rank]
+};
+void launch_gpm_init(hipStream_t st, int n_items, int nblk_max, const GpmItem* items);
+void launch_gpm_pivot_step(hipStream_t st, int n_items, int nblk_max, int step, const GpmItem* items);
+int gpm_slab_rows(int R);  // a function of the item's size alone
+void launch_gpm_gram(hipStream_t st, int n, int mp_max, int slabs_max, const GpmSpace* items);
+void launch_gpm_refine(hipStream_t st, int n, int me_max, const GpmSpace* items);
+void launch_gpm_operand(hipStream_t st, int n, int mp_max, int ldb_max, const GpmSpace* items);
+void launch_gpm_gemm(hipStream_t st, int n_pieces, int rows_max, int col_tiles_max, const GpmPiece* pieces);
+
+
 }  // namespace icp

@@ -84,6 +84,49 @@ class StatisticalMeshModel:
         return self.ref_points + self.mean_def + (q @ np.asarray(coeffs, dtype=np.float64)).reshape(-1, 3)
 
 
+@dataclasses.dataclass
+class GaussianKernelTerm:
+    """One term scale · exp(−‖x−y‖² / sigma²) · A of a matrix-valued kernel (gp_models): Scalismo's GaussianKernel(sigma) — no factor
+    ½ — times a symmetric positive semi-definite 3 × 3 matrix A (DiagonalKernel: the identity)."""
+    scale: float
+    sigma: float
+    A: np.ndarray = None
+
+    def __post_init__(self):
+        self.scale = float(self.scale)
+        self.sigma = float(self.sigma)
+        self.A = np.eye(3) if self.A is None else np.ascontiguousarray(self.A, dtype=np.float64)
+        if self.A.shape != (3, 3):
+            raise ValueError("A is a 3 x 3 matrix")
+
+    def __call__(self, x, y):
+        """k(x, y) for points x [..., 3], y [..., 3] -> [..., 3, 3] (numpy; the long forms of the tests use it)"""
+        d = np.asarray(x, dtype=np.float64) - np.asarray(y, dtype=np.float64)
+        d2 = (d[..., 0] * d[..., 0] + d[..., 1] * d[..., 1]) + d[..., 2] * d[..., 2]
+        return (self.scale * np.exp(-(d2 / (self.sigma * self.sigma))))[..., None, None] * self.A
+
+
+def axis_of_main_variance(points) -> np.ndarray:
+    """apps/femur/CreateGPModel.scala:48-54: the left singular vectors of the points' covariance about their centre of mass."""
+    p = np.ascontiguousarray(points, dtype=np.float64).reshape(-1, 3)
+    n = 1.0 / p.shape[0]
+    c = p.sum(axis=0) * n
+    cov = ((p - c).T @ (p - c)) * n
+    u, _, _ = np.linalg.svd(cov)
+    return u
+
+
+def femur_kernel(reference_mesh) -> list:
+    """The kernel of apps/femur/CreateGPModel.scala:68-78 on `reference_mesh` (a TriangleMesh or points [N, 3]):
+    10·B·G(90) + 5·I·G(40) + 3·I·G(10) with B = U·diag(10, 1, 1)·Uᵀ, U the axes of main variance (more variance along the bone).
+    B does not depend on the signs the SVD gives its vectors; it is symmetrised exactly."""
+    pts = reference_mesh.points if hasattr(reference_mesh, "points") else reference_mesh
+    u = axis_of_main_variance(pts)
+    b = u @ np.diag([10.0, 1.0, 1.0]) @ u.T
+    b = 0.5 * (b + b.T)
+    return [GaussianKernelTerm(10.0, 90.0, b), GaussianKernelTerm(5.0, 40.0, np.eye(3)), GaussianKernelTerm(3.0, 10.0, np.eye(3))]
+
+
 def load_femur_model(n_components: int = 50, fixture_dir: str = FIXTURE_DIR) -> StatisticalMeshModel:
     """femur GPMM with `n_components`+1 basis functions (reference: data/femur/femur_gp_model_*-components.h5)."""
     z = np.load(os.path.join(fixture_dir, f"femur_gp_model_{n_components}.npz"))

@@ -531,6 +531,52 @@ ICP_API int icp_posterior_models_many(int32_t n_items, icp_ctx *const *ctxs, con
                                       double *const *alpha_out, double *const *mean_out, double *const *basis_out,
                                       double *const *variance_out, double *const *point_variance_out, int32_t *status);
 
+/* ---------------------------------------------------------------- Gaussian-process shape models from analytic kernels, many in one call
+ * What apps/femur/CreateGPModel.scala and apps/bfm/CreateGPModel.scala do before anything is registered: a low-rank model of a
+ * matrix-valued kernel on a reference mesh's own points.  The approximation is Scalismo's pivoted Cholesky factorisation
+ * (approximateGPCholesky) followed by the eigen-decomposition of an m x m Gram matrix; deterministic, no sampler.
+ *   k(x, y) = sum_t scale_t * exp(-|x - y|^2 / sigma_t^2) * A_t      (Scalismo's GaussianKernel(sigma): no factor 1/2)
+ * with 1 .. ICP_GP_MODELS_MAX_TERMS terms per item; A_t (row-major 3 x 3) exactly symmetric, positive semi-definite (checked on the host
+ * in closed form) and not zero, scale_t > 0, sigma_t > 0, all finite.  CreateGPModel.scala:68-78 is 10 B G(90) + 5 I G(40) + 3 I G(10).
+ * K is the 3N x 3N kernel matrix on the points (row 3 * vertex + coordinate), d its diagonal, summed over the terms in order.
+ *   step j = 0, 1, ...: p = the row of the largest d (ties: the lowest row).  Stop BEFORE the step when j = n_pivots, when
+ *     max d <= n_pivots * 2^-52 * (max d at the start), or when sum d <= rel_tolerance * trace(K).  Otherwise
+ *     col = K[:, p] - L[:, :j] L[p, :j]^T (products summed in column order),  L[:, j] = col / sqrt(d[p]),  d -= L[:, j]^2 (not clamped).
+ *   then, with m_eff columns: (theta_j, u_j) the eigenpairs of L L^T (through the m_eff x m_eff matrix L^T L, decomposed by the
+ *     resident routes of the chain - ranks up to 64 Jacobi, up to 256 tridiagonal - and one step of iterative refinement of their
+ *     eigenvectors, which the chain needs to 1e-11 only and a basis to rounding), descending;
+ *     variance_j = theta_j / N,  basis column j = sqrt(N) u_j  (squared norm N, as Scalismo's discretised models have them).
+ * Per item b: n_points[b] = N >= 1; points[b] [3N] finite; n_terms[b], terms[b]; 1 <= rank[b] <= n_pivots[b] <= min(256, 3N);
+ * 0 <= rel_tolerance[b] < 1 (rel_tolerance == NULL: 0 for every item).  The effective rank is min(rank, m_eff).
+ * Outputs (each array may be NULL as a whole, and each entry of it may be NULL):
+ *   variance_out[b] [rank] descending, 0 behind the effective rank;  basis_out[b] [3N * rank] row-major like icp_model_desc.basis, zero
+ *   columns behind the effective rank;  pivots_out[b] [n_pivots] rows 3 * vertex + coordinate in the order chosen, -1 behind m_eff;
+ *   residual_out[b] [3N] = d when the loop stopped;  info_out[b] [4] = m_eff, effective rank, trace(K) / N, sum of variance_out[b].
+ * With effective rank == rank, (points, triangles, NULL, basis_out[b], variance_out[b]) IS a valid icp_model_desc (mean deformation 0).
+ * The call takes no context: `device` as icp_ctx_create takes it; streams and buffers come from the library's pools.  One launch per
+ * pivot step carries every item of the call; ONE synchronisation behind the loop (the effective pivot counts), then one per round of
+ * output rows: L^T L and L (W Theta^-1/2 sqrt N) run on the f64 matrix cores (v_mfma_f64_16x16x4_f64), the rows of the bases pass through
+ * ONE chunk buffer of ICP_GP_MODELS_CHUNK_BYTES.  Device memory: 8 * 3N * (n_pivots + 2) bytes per item for L, d and the points, all items
+ * of the call at once.  No floating-point atomics; every sum of an item is a function of the item alone: its bits depend neither on
+ * the other items of the call, nor on their order, nor on how its rows fall into the chunk buffer.
+ * Whole-call errors (nothing has run, nothing is written): ICP_ERR_INVALID_ARG for n_items outside [1, 65535] or a null required
+ * argument; ICP_ERR_DEVICE.  An item outside the limits above gets status[b] = ICP_ERR_INVALID_ARG - decided for every item before
+ * the device is touched - and nothing is written for it; the other items are computed.  status[b] = ICP_ERR_NOT_FINITE (outputs NaN)
+ * if the decomposition of an item did not converge.  The return value is ICP_OK or the first failing item's status. */
+typedef struct {
+  double scale;
+  double sigma;
+  double A[9];
+} icp_kernel_term;
+#define ICP_GP_MODELS_MAX_TERMS 8
+#define ICP_GP_MODELS_MAX_PIVOTS 256
+#define ICP_GP_MODELS_CHUNK_BYTES (32u << 20)
+ICP_API int icp_gp_models_many(int32_t n_items, int device, const int32_t *n_points, const double *const *points,
+                               const int32_t *n_terms, const icp_kernel_term *const *terms, const int32_t *n_pivots,
+                               const int32_t *rank, const double *rel_tolerance, double *const *variance_out,
+                               double *const *basis_out, int32_t *const *pivots_out, double *const *residual_out,
+                               double *const *info_out, int32_t *status);
+
 /* ---------------------------------------------------------------- the per-method entry points as ONE submission per step (round 6)
  * The drop-in contract is "Scalismo's chain, unchanged": MetropolisHastings.next (constructed at
  * api/sampling/SamplingRegistration.scala:52-58) calls  logValue(current) [memoised] → propose(current) → logValue(proposal) →
