@@ -537,7 +537,11 @@ void launch_step_finish(hipStream_t st, const StepFinishArgs& a_in) {
   StepFinishArgs a = a_in;
   a.n_lds = p.n_lds;
   a.tail_base = p.tail_base;
-  a.tpr_log2 = matvec_tpr_log2(a.r, p.NT);
+  // The tails' products are summed as the per-method kernel sums them (k_transition_tails<256>: matvec_tpr_log2(r, 256) threads a row),
+  // so that a merged step gives the bits of the separate calls.  Up to rank 61 the launch has 256 threads itself; on 512 threads
+  // the two choices differ at rank 64 alone (8 threads a row instead of 4: the last bit of a transition density).  Above 64 the
+  // launch keeps the layout of its own size; there the two paths agree to the last bit or two (tests/test_gpu_chain.py).
+  a.tpr_log2 = matvec_tpr_log2(a.r, a.r <= 64 ? 256 : p.NT);
   if (t_capture) { t_capture->finish = a; t_capture->grid[4] = 2 * a.n; return; }
   ProfScope _ps(st, KID_STEP_FINISH);
   if (p.E == 1 && p.NT == 256) launch_finish<1, 256>(st, a, p.shmem);
