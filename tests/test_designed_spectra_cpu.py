@@ -13,13 +13,16 @@ import designed_spectra as DS
 import posterior_long_form as LF
 
 RANKS = (65, 129, 256)
+MULTIPLE_RANKS = (140, 141)   # tests/test_gpu_eigen_spectra.py: MULTIPLE_LADDER, the `multiple` spectrum alone
 
 
 @pytest.fixture(scope="module")
 def designed(pkg):
     out = {}
-    for r in RANKS:
+    for r in RANKS + MULTIPLE_RANKS:
         for k, name in enumerate(DS.SPECTRA):
+            if r in MULTIPLE_RANKS and name != "multiple":
+                continue
             mu = DS.SPECTRA[name](r)
             model, ids, pts, U, s2 = DS.designed_model(pkg, r, mu, 1000 * r + k)
             out[r, name] = (mu, model, U, LF.long_form(model, ids, pts, sigma2=s2))
@@ -78,3 +81,14 @@ def test_gram_matrix_is_well_conditioned(designed, r, name):
     w = np.linalg.eigvalsh(lf["Q"].T @ lf["Q"])
     print(f"rank {r} {name}: cond(G) {w[-1] / w[0]:.1e}, cond(basis) {np.linalg.cond(model.basis):.1f}")
     assert w[0] > 0 and w[-1] / w[0] < 1e8
+
+
+@pytest.mark.parametrize("r", MULTIPLE_RANKS)
+def test_multiple_spectrum_at_the_square_edge_of_the_fallback(designed, r):
+    """the two inputs of test_multiple_spectrum_on_both_sides_of_the_square_edge: the designed pair and nothing else below 1e-5·μ_max,
+    the eigenvalues within 1e-13·μ_max of the design, a well-conditioned Gram matrix — as at RANKS"""
+    from test_gpu_eigen_spectra import MULTIPLE_LADDER
+    assert MULTIPLE_LADDER == MULTIPLE_RANKS
+    test_long_form_reproduces_the_designed_spectrum(designed, r, "multiple")
+    test_regime_reports_the_intended_bands(designed, r, "multiple")
+    test_gram_matrix_is_well_conditioned(designed, r, "multiple")

@@ -21,6 +21,9 @@ from test_gpu_posterior_models import WANT, check_against_long_form, same_bits
 pytestmark = pytest.mark.gpu
 
 LADDER = (65, 128, 129, 192, 193, 200, 201, 208, 209, 256)  # both sides of every edge of tri_reduction_shape / tri_row_slots, kBigMaxRank
+# `multiple` alone: both sides of launch_eigen_big's own edge as the status-2 fall-back — the full n × (n|1) image in one CU's LDS
+# (k_eigen_big<true>, up to 140) | the packed triangle (k_eigen_big<false>); pinned by tests/test_designed_spectra_cpu.py
+MULTIPLE_LADDER = (140, 141)
 ORDER = ("wide", "close", "graded", "multiple")
 
 # launch_posterior_factor's ladder (kernels_factor.hip), restated: rank -> the kernel that factors M.  A rank needs factor_tile_count(r)
@@ -150,6 +153,22 @@ def test_every_rank_shape_on_every_spectrum(pkg, designed, r):
         it = items[name]
         check_against_long_form(it.model, res[name], it.ids, it.pts, it.sigma2, None, f"rank {r} {name}")
         assert all(v == 0 for v in pkg._native.runtime_stats(it.ctx.h).values()), name
+
+
+@pytest.mark.parametrize("r", MULTIPLE_LADDER)
+def test_multiple_spectrum_on_both_sides_of_the_square_edge(pkg, r):
+    """The `multiple` model of rank 140 and of rank 141, each alone in a call: status 2 out of the multisection, then launch_eigen_big
+    cold — with the square image in LDS at 140, on the packed triangle at 141 (LADDER runs the fall-back at 65, 128, 129, 192, 193 and
+    200: neither side of this edge).  check_decomposition and the long form, as for the ladder's ranks."""
+    it = Item(pkg, r, "multiple", list(DS.SPECTRA).index("multiple"))
+    assert it.bands == (1, 0, 0, 0, r - 2) and DS.in_regime("multiple", it.bands), it.bands
+    res = run(pkg, [it])[0]
+    assert res["status"] == 0
+    misses = check_decomposition(f"rank {r} multiple", it.Np, res["variance"], device_V(it, res))
+    assert not misses, misses
+    check_against_long_form(it.model, res, it.ids, it.pts, it.sigma2, None, f"rank {r} multiple")
+    assert all(v == 0 for v in pkg._native.runtime_stats(it.ctx.h).values())
+    it.ctx.close()
 
 
 @pytest.mark.parametrize("r", [129, 209])
