@@ -523,7 +523,10 @@ struct icp_ctx {
 
   void bind() { HIP_OK(hipSetDevice(device)); }
 
-  // scratch for K queries against a set of n_elems elements (every query may list every element as a candidate)
+  // scratch for K queries against a set of n_elems elements: every query may list min(n_elems, kCandStrideMax) candidates, up to
+  // kMaxCandidates ints in all — from K = 16,381 on against 4,096 elements or more the lists get shorter (cand_stride_for), from
+  // K = 131,069 on the queries go in batches (query_batch).  The scratch only grows, but a call's stride and batches are those of a
+  // fresh context: `want` is the most either of them can use
   QueryBuffers query_scratch(size_t K, size_t n_elems, int which = 0) {
     QueryScratch& scratch = which == 1 ? scratch_v : which == 2 ? scratch_t : which == 3 ? scratch_n : which == 4 ? scratch_tn : which == 5 ? scratch_p : which == 6 ? scratch_en : this->scratch;
     if (K > scratch.cap) {

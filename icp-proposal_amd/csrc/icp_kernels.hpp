@@ -105,8 +105,8 @@ struct QueryBuffers {   // scratch of one query batch; per-query arrays hold the
   float4* qrec;          // surface queries: f32 copy of the point
   float* thrA;           // surface queries: distance bound (inflated, f32)
   int* cnt;              // candidates per query
-  int* cand;             // candidate lists, one row of cand_stride(n_elements) ints per query
-  size_t cand_capacity;  // ints in `cand`; a batch takes floor(capacity / stride) queries
+  int* cand;             // candidate lists, one row of cand_stride_for(n_elements, K, cand_capacity) ints per query: 512 to 4,096, at most n_elements
+  size_t cand_capacity;  // ints in `cand`; a batch takes floor(capacity / cand_stride(n_elements)) − 4 queries (query_batch)
 };
 
 // Candidate lists hold at most this many entries per query.  With a hint (the previous winner) a query lists a few dozen; a list

@@ -277,20 +277,22 @@ def test_cholesky_root_sampler(case):
     assert not misses, misses
 
 
-def check_merged_step(c, tail_rel=0.0):
+def check_merged_step(c, tail_rel=0.0, Kp=None, Ke=None):
     """(f) test_chain_step_matches_separate_calls of tests/test_gpu_parity.py (independent evaluator) at the rank, on this rank's
     context and a second one for the separate calls; every third step accepted, so that steps begin while the decomposition of a newly
     accepted state is pending (k_step_begin_reg<52> / <64> from rank 32 on).  All six steps take the merged path, no fall-back runs.
     tail_rel: how far a transition density of the merged step may be from the separate call's, of its size — 0 up to rank 64: the same
-    bits; above, where the finish launch sums the tails' products over its own threads, what tests/test_gpu_chain.py allows."""
+    bits; above, where the finish launch sums the tails' products over its own threads, what tests/test_gpu_chain.py allows.
+    Kp, Ke: sample points of the two proposals and of the evaluator, 2r and 4r unless given (tests/test_gpu_counts.py)."""
     same = lambda x, y: abs(x - y) <= tail_rel * abs(y)
     model, target, r, pkg = c.model, c.target, c.r, c.pkg
-    tp = pkg.data.decimated_point_subset(target, 2 * r)
+    Kp, Ke = 2 * r if Kp is None else Kp, 4 * r if Ke is None else Ke
+    tp = pkg.data.decimated_point_subset(target, Kp)
     ctx_a, ctx_b = c.ctx, pkg.IcpContext(model, target, device=0)   # separate contexts: separate caches and search hints
 
     def mk(ctx):
-        props = [pkg.NonRigidIcpProposal(ctx, STEP, SIGMA_T, SIGMA_N, 2 * r, d, True, decimatedTargetPoints=tp) for d in ("TargetSampling", "ModelSampling")]
-        return props, pkg.IndependentPointDistanceEvaluator(ctx, 0.0, 2.0, 0, 4 * r)
+        props = [pkg.NonRigidIcpProposal(ctx, STEP, SIGMA_T, SIGMA_N, Kp, d, True, decimatedTargetPoints=tp) for d in ("TargetSampling", "ModelSampling")]
+        return props, pkg.IndependentPointDistanceEvaluator(ctx, 0.0, 2.0, 0, Ke)
     (props_a, ev_a), (props_b, ev_b) = mk(ctx_a), mk(ctx_b)
     before = ctx_a.step_paths()
     cur = make_theta(model, 600, pose=False)
