@@ -1,5 +1,6 @@
 // abi_batched.inl — part of icp_abi.hip (one translation unit; included there, in order).
-// C ABI: icp_chain_step_batched_issue / _collect / _abandon
+// C ABI: icp_chain_step_batched_issue / _collect / _abandon, icp_chain_step_batched; the queries icp_chain_step_path and
+// icp_proposal_basis_state
 extern "C" {
 
 int icp_chain_step_batched_issue(int32_t n_chains, icp_evaluator* const* evaluators, int32_t n_props, icp_proposal* const* props,
@@ -356,5 +357,37 @@ int icp_chain_step_batched_abandon(icp_step_ticket* tk) {
   batch_release(*tk);  // waits for the batch's launches, gives back what they hold; nothing of the step is recorded
   delete tk;
   return ICP_OK;
+}
+
+int icp_chain_step_batched(int32_t n_chains, icp_evaluator* const* evaluators, int32_t n_props, icp_proposal* const* props,
+                           const int32_t* generator, const double* const* theta_cur, const double* const* z,
+                           double* const* theta_prop, double* log_value_prop, double* fwd, double* bwd, int32_t* status) {
+  icp_step_ticket* tk = nullptr;
+  const int rc = icp_chain_step_batched_issue(n_chains, evaluators, n_props, props, generator, theta_cur, z, theta_prop, log_value_prop, fwd,
+                                              bwd, status, nullptr, &tk);
+  if (rc != ICP_OK) return rc;
+  return icp_chain_step_batched_collect(tk);
+}
+
+// ---- queries: which path a chain's step takes, what a proposal's basis of a state is doing
+int icp_chain_step_path(icp_evaluator* e, int32_t n_props, icp_proposal* const* props) {
+  if (!e || n_props < 0 || (n_props > 0 && !props)) return ICP_ERR_INVALID_ARG;
+  for (int i = 0; i < n_props; ++i)
+    if (!props[i] || props[i]->ctx != e->ctx) return ICP_ERR_INVALID_ARG;
+  std::lock_guard<std::recursive_mutex> lk(e->ctx->mu);
+  if (step_pipeline_covers(e, n_props, props)) return 0;
+  if (n_props >= 1 && n_props <= 2 && wide_pipeline_covers(e, n_props, props)) return 1;
+  return 2;
+}
+
+int icp_proposal_basis_state(icp_proposal* p, const double* theta) {
+  if (!p || !theta) return ICP_ERR_INVALID_ARG;
+  icp_ctx& c = *p->ctx;
+  std::lock_guard<std::recursive_mutex> lk(c.mu);
+  if (c.batch_busy) return 1;  // (its context is part of a batch in flight: whatever it is doing, it is not ready)
+  PosteriorEntry* e = p->find_entry(theta);
+  if (!e) return 0;
+  if (!e->eig_valid) return 0;
+  return *(volatile int*)(p->h_eig + e->status_off / 3) == -1 ? 1 : 2;
 }
 }  // extern "C"

@@ -29,6 +29,11 @@ struct PosteriorEntry {
   ~PosteriorEntry() { if (eig_done) (void)hipEventDestroy(eig_done); }
   hipEvent_t eigen_event() const { return (!eig_event_valid || eigen_event_stale()) ? nullptr : (eig_done_shared ? eig_done_shared : eig_done); }
   CorrBuffers corr() const { return CorrBuffers{id.p, aux.p, pt.p, keep.p, nhat.p, e.p}; }
+  // whatever the entry holds belongs to no state on record (`and_event` = false: its event and completion word stay as they are)
+  void off_record(bool and_event = true) {
+    valid = false; eig_valid = false; eig_checked = false;
+    if (and_event) { eig_event_valid = false; done_value = 0; }
+  }
 };
 
 }  // namespace
@@ -117,6 +122,16 @@ struct icp_proposal {
   unsigned eig_flip = 0;
   void await_eigen(PosteriorEntry& e);   // make the context stream wait for it
   void check_status(PosteriorEntry& e);
+  // (the on-device loops) `e` holds the posterior of `theta` again, decomposed and checked by launches that leave no event and no
+  // completion word; its basis is the warm start
+  void on_record(PosteriorEntry& e, const double* theta, int P) {
+    e.valid = true; e.eig_valid = true; e.eig_checked = true; e.eig_event_valid = false; e.done_value = 0;
+    e.theta.assign(theta, theta + P);
+    e.stamp = ++clock;
+    h_eig[e.status_off / 3] = 0;
+    warm_ptr = e.V.p;
+    warm_valid = true;
+  }
 };
 
 namespace {

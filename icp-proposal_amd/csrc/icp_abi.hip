@@ -25,5 +25,7 @@
 #include "abi_gp_models.inl"  // C ABI: icp_gp_models_many (Gaussian-process shape models from analytic kernels by pivoted Cholesky, kernels_gp_model.hip)
 #include "abi_step.inl"  // the merged step (five launches): fronts, speculative decompositions, icp_chain_step / _prelaunch
 #include "abi_wide.inl"  // the wide step's host side (kernels_wide.hip)
-#include "abi_batched.inl"  // C ABI: icp_chain_step_batched_issue / _collect / _abandon
-#include "abi_device_loop.inl"  // C ABI: icp_chains_run_on_device (the whole MH loop on the device) and the remaining queries
+#include "abi_batched.inl"  // C ABI: icp_chain_step_batched (_issue / _collect / _abandon), icp_chain_step_path, icp_proposal_basis_state
+#include "abi_loop_common.inl"  // what the two on-device MH loops below share: arguments and checks, the MhChain fill, a group's buffers, normals feed, drain and hand-out
+#include "abi_wide_loop.inl"  // the whole MH loop on the device for chains whose step is the wide one
+#include "abi_device_loop.inl"  // C ABI: icp_chains_run_on_device (the whole MH loop on the device: the merged step's loop, dispatch to the wide one)

@@ -83,7 +83,7 @@ def wide_rank_covered(r, root=False):
 
 
 def step_path(r, closed):
-    """abi_device_loop.inl, icp_chain_step_path, for the chain configurations of this module: step_pipeline_covers (abi_methods.inl)
+    """abi_batched.inl, icp_chain_step_path, for the chain configurations of this module: step_pipeline_covers (abi_methods.inl)
     holds on a closed target where step_finish_supported(r) does — on a target with a boundary a boundary-aware ModelSampling proposal
     needs the nearest-vertex pass, which the merged step has not —, then wide_pipeline_covers (abi_wide.inl: wide_rank_covered), then the
     per-stage kernels"""
@@ -130,7 +130,7 @@ def tail_direct_in_lds(r):
 
 
 def mhw_decide(r):
-    """kernels_step.hip, launch_mhw_decide, inside the on-device loop, which above 64 needs the tridiagonal route (abi_device_loop.inl)"""
+    """kernels_step.hip, launch_mhw_decide, inside the on-device loop, which above 64 needs the tridiagonal route (abi_wide_loop.inl)"""
     if not tridiag_route(r):
         return None
     return "k_mhw_decide<2>" if r <= 128 else "k_mhw_decide<4>"
@@ -178,8 +178,8 @@ DISPATCH = {
     "context": (context, "abi_context.inl: icp_ctx_create"),
     "finish_plan": (finish_plan, "kernels_step.hip: finish_plan"),
     "finish tails' threads per row": (finish_tails_tpr, "kernels_step.hip: launch_step_finish"),
-    "step path, closed target": (lambda r: step_path(r, True), "abi_device_loop.inl: icp_chain_step_path"),
-    "step path, open target": (lambda r: step_path(r, False), "abi_device_loop.inl: icp_chain_step_path"),
+    "step path, closed target": (lambda r: step_path(r, True), "abi_batched.inl: icp_chain_step_path"),
+    "step path, open target": (lambda r: step_path(r, False), "abi_batched.inl: icp_chain_step_path"),
     "factor launch": (factor_launch, "kernels_factor.hip: launch_posterior_factor"),
     "root sampler": (root_sampler, "abi_posterior.inl: root_here; abi_methods.inl: icp_proposal_set_sampler"),
     "propose, eigen sampler": (propose_launch, "kernels_posterior.hip: launch_propose; kernels_wide.hip: launch_wide_propose(_resident)"),

@@ -665,6 +665,55 @@ def test_device_loop_matches_oracle_chain(pkg, femur50, femur50_oracle, oracle, 
         assert moved, "no pose walk was accepted in any chain"
 
 
+def test_device_loop_refusal_after_a_partial_claim_leaves_chains_usable(pkg, femur50):
+    """A run refused AFTER its first chain was claimed (entries and state slot reserved, the context marked as a batch's) gives
+    everything back: the second chain of the refused call is the first one's context again; the same objects then run with two
+    contexts of their own, and the first context steps a host-stepped chain afterwards."""
+    import ctypes as C
+    nat = pkg._native
+    model, target = femur50
+    r = model.rank
+    setup = pkg.femur_icp_proposal_registration(model, target, fused=2)
+
+    def objects(ctx):  # (the proposals and the evaluator of femur_icp_proposal_registration)
+        props = [pkg.NonRigidIcpProposal(ctx, 0.1, 10.0, 5.0, 2 * r, pkg.TargetSampling, True, decimatedTargetPoints=setup.icp[0]["target_pts"]),
+                 pkg.NonRigidIcpProposal(ctx, 0.1, 10.0, 5.0, 2 * r, pkg.ModelSampling, True)]
+        ev = pkg.IndependentPointDistanceEvaluator(ctx, 0.0, 2.0, pkg.ModelToTargetEvaluation, 4 * r, decimatedTargetPoints=setup.eval["target_pts"])
+        return ev, props
+
+    def run(evs, props, thetas):
+        B = len(evs)
+        mix = nat.MhMixture(C.sizeof(nat.MhMixture), (C.c_double * 2)(0.5, 0.5), 0.9, 0.1, 0.1)
+        eh = (C.c_void_p * B)(*[e.h for e in evs])
+        ph = (C.c_void_p * (2 * B))(*[p.h for pp in props for p in pp])
+        seeds = (C.c_uint64 * B)(*range(9, 9 + B))
+        first = (C.c_int64 * B)(*([0] * B))
+        th = [np.ascontiguousarray(t, dtype=np.float64).copy() for t in thetas]
+        thp = (nat.c_double_p * B)(*[t.ctypes.data_as(nat.c_double_p) for t in th])
+        logp = np.full(B, -1e300)
+        acc = (C.c_int64 * B)(*([0] * B))
+        rc = nat.lib().icp_chains_run_on_device(B, eh, 2, ph, C.byref(mix), seeds, first, thp, logp.ctypes.data_as(nat.c_double_p), 3, None, acc)
+        return rc, nat.lib().icp_last_error().decode()
+
+    ctxs = [pkg.IcpContext(model, target, device=0) for _ in range(2)]
+    objs = [objects(c) for c in ctxs]
+    thetas = [pkg.random_initial_parameters(model, i) for i in range(2)]
+    rc, msg = run([objs[0][0], objs[0][0]], [objs[0][1], objs[0][1]], thetas)
+    assert rc == -1 and "context of its own" in msg, (rc, msg)
+    rc, msg = run([objs[0][0], objs[1][0]], [objs[0][1], objs[1][1]], thetas)
+    assert rc == 0, (rc, msg)
+    paths = [c.step_paths() for c in ctxs]
+    assert all(p["device_loop"] == 3 for p in paths), paths
+    assert all(v == 0 for c in ctxs for v in c.runtime_stats().values()), [c.runtime_stats() for c in ctxs]
+    chain = pkg.SamplingRegistration(ctxs[0], setup, thetas[0], seed=5)
+    assert chain.run(2).shape == (2, 14 + r)
+    chain.close()
+    for ev, props in objs:
+        ev.close(); [p.close() for p in props]
+    for c in ctxs:
+        c.close()
+
+
 def test_femur100_chain_from_the_deterministic_fit_accepts_and_matches_oracle(pkg, oracle):
     """BASELINE.json configs[2] with ACCEPTED steps.  From a random start this chain (K = N = 1622 correspondences, rank 101) rejects
     every ICP proposal under the reference's own transition ratio: the backward density evaluates (2 − step)·(c − α) against a posterior

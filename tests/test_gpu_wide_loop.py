@@ -253,3 +253,52 @@ def test_wide_loop_refusals(pkg):
         ev.close(); p.close()
     for c in ctxs:
         c.close()
+
+
+def test_wide_loop_refusal_after_a_partial_claim_leaves_chains_usable(pkg):
+    """A run refused AFTER its first chain was claimed (its entries reserved, the context marked as a batch's: the refusals above all
+    fall before or at the first chain's claim) gives everything back: the second chain of the refused call is the first one's context
+    again; the same objects then run with two contexts of their own, and the first context steps a host-stepped chain afterwards."""
+    import ctypes as C
+    nat = pkg._native
+    model = pkg.data.synthetic_face_model(grid=31, rank=80)
+    target = pkg.data.synthetic_partial_target(model, n_remove=60, seed=7)
+    r = model.rank
+    tp = pkg.data.decimated_point_subset(target, 4 * r)
+
+    def objects(ctx):
+        prop = pkg.NonRigidIcpProposal(ctx, 0.1, 6.0, 3.0, 2 * r, pkg.ModelSampling, True)
+        ev = pkg.CollectiveAverageHausdorffDistanceBoundaryAwareEvaluator(ctx, 0.0, 1.0, 1.0, pkg.SymmetricEvaluation, 4 * r, decimatedTargetPoints=tp)
+        return ev, prop
+
+    def run(evs, props, thetas):
+        B = len(evs)
+        mix = nat.MhMixture(C.sizeof(nat.MhMixture), (C.c_double * 2)(1.0, 0.0), 0.9, 0.1, 0.1)
+        eh = (C.c_void_p * B)(*[e.h for e in evs])
+        ph = (C.c_void_p * B)(*[p.h for p in props])
+        seeds = (C.c_uint64 * B)(*range(9, 9 + B))
+        first = (C.c_int64 * B)(*([0] * B))
+        th = [np.ascontiguousarray(t, dtype=np.float64).copy() for t in thetas]
+        thp = (nat.c_double_p * B)(*[t.ctypes.data_as(nat.c_double_p) for t in th])
+        logp = np.full(B, -1e300)
+        acc = (C.c_int64 * B)(*([0] * B))
+        rc = nat.lib().icp_chains_run_on_device(B, eh, 1, ph, C.byref(mix), seeds, first, thp, logp.ctypes.data_as(nat.c_double_p), 3, None, acc)
+        return rc, nat.lib().icp_last_error().decode()
+
+    ctxs = [pkg.IcpContext(model, target, device=0) for _ in range(2)]
+    objs = [objects(c) for c in ctxs]
+    thetas = [pkg.random_initial_parameters(model, i) for i in range(2)]
+    rc, msg = run([objs[0][0], objs[0][0]], [objs[0][1], objs[0][1]], thetas)
+    assert rc == ICP_ERR_INVALID_ARG and "context of its own" in msg, (rc, msg)
+    rc, msg = run([objs[0][0], objs[1][0]], [objs[0][1], objs[1][1]], thetas)
+    assert rc == 0, (rc, msg)
+    paths = [c.step_paths() for c in ctxs]
+    assert all(p["device_loop"] == 3 for p in paths), paths
+    assert all(v == 0 for c in ctxs for v in c.runtime_stats().values()), [c.runtime_stats() for c in ctxs]
+    chain = pkg.SamplingRegistration(ctxs[0], pkg.bfm_fitting_partial(model, target, evaluator="collective", fused=2), thetas[0], seed=5)
+    assert chain.run(2).shape == (2, 14 + r)
+    chain.close()
+    for ev, p in objs:
+        ev.close(); p.close()
+    for c in ctxs:
+        c.close()
