@@ -68,6 +68,14 @@ class KernelTerm(C.Structure):
     _fields_ = [("scale", C.c_double), ("sigma", C.c_double), ("A", C.c_double * 9)]
 
 
+KERNEL_GAUSSIAN, KERNEL_BSPLINE3 = 0, 1
+
+
+class KernelTermGeneral(C.Structure):
+    _fields_ = [("struct_size", C.c_int32), ("kind", C.c_int32), ("scale", C.c_double), ("sigma", C.c_double), ("level", C.c_int32),
+                ("mirror_axis", C.c_int32), ("mirror_gain", C.c_double), ("A", C.c_double * 9), ("weights", c_double_p)]
+
+
 # every symbol include/icp_proposal.h declares: name -> (restype, argtypes)
 SIGNATURES = {
     "icp_ctx_create": (C.c_int, [C.POINTER(ModelDesc), C.POINTER(MeshDesc), C.c_int, C.POINTER(C.c_void_p)]),
@@ -128,7 +136,12 @@ SIGNATURES = {
     "icp_gp_models_many": (C.c_int, [C.c_int32, C.c_int, c_int_p, C.POINTER(c_double_p), c_int_p, C.POINTER(C.POINTER(KernelTerm)), c_int_p,
                                      c_int_p, c_double_p, C.POINTER(c_double_p), C.POINTER(c_double_p), C.POINTER(c_int_p),
                                      C.POINTER(c_double_p), C.POINTER(c_double_p), c_int_p]),
-    "icp_chain_step": (C.c_int, [C.c_void_p, C.c_int32, C.POINTER(C.c_void_p), C.c_int32, c_double_p, c_double_p, c_double_p,
+    "icp_gp_models_general_many": (C.c_int, [C.c_int32, C.c_int, c_int_p, C.POINTER(c_double_p), c_int_p,
+                                             C.POINTER(C.POINTER(KernelTermGeneral)), c_int_p, c_int_p, c_double_p, C.POINTER(c_double_p),
+                                             C.POINTER(c_double_p), C.POINTER(c_int_p), C.POINTER(c_double_p), C.POINTER(c_double_p), c_int_p]),
+    "icp_region_weights_many": (C.c_int, [C.c_int32, C.c_int, c_int_p, C.POINTER(c_double_p), c_int_p, C.POINTER(c_double_p), c_double_p,
+                                          C.POINTER(c_double_p), c_int_p]),
+    "icp_chain_step":(C.c_int, [C.c_void_p, C.c_int32, C.POINTER(C.c_void_p), C.c_int32, c_double_p, c_double_p, c_double_p,
                                  c_double_p, c_double_p, c_double_p]),
     "icp_chain_step_batched_issue": (C.c_int, [C.c_int32, C.POINTER(C.c_void_p), C.c_int32, C.POINTER(C.c_void_p), C.POINTER(C.c_int32),
                                                C.POINTER(c_double_p), C.POINTER(c_double_p), C.POINTER(c_double_p), c_double_p,

@@ -1120,6 +1120,9 @@ def posterior_models(contexts, vertex_ids, points, sigma2=None, covariances=None
 
 _GP_WANT = ("variance", "basis", "pivots", "residual")
 GP_MAX_PIVOTS, GP_MAX_TERMS = 256, 8
+GP_MAX_LEVEL = 32    # B-spline levels lie in [-32, 32]
+GP_NOT_FINITE = -3   # ICP_ERR_NOT_FINITE: an item of a general call whose pivot loop left no column (trace K = 0)
+_KERNEL_TERMS = (_data.GaussianKernelTerm, _data.BSplineKernelTerm)
 
 
 def _psd3(a):
@@ -1148,13 +1151,17 @@ def gp_models(meshes, kernels, n_pivots, rank=None, rel_tolerance=0.0, device=0,
     squared norm N; None unless "variance" and "basis" are wanted) of the effective rank min(rank, effective pivots), and a dict with
     "n_pivots" (effective), "rank" (effective), "total_variance" trace(K)/N, "approximated_variance" Σ variance, and the wanted ones of
     "variance" [rank], "pivots" [effective] (rows 3·vertex + coordinate in the order chosen), "residual" [3N] (the residual diagonal
-    when the loop stopped)."""
+    when the loop stopped).
+    A kernel may also hold general terms — data.BSplineKernelTerm, or a data.GaussianKernelTerm with weights or a mirror gain (the face
+    kernel of apps/bfm: face_kernel) —, mixed freely with plain ones: such a call goes through icp_gp_models_general_many, and every
+    info dict then has "status": 0, or -3 (ICP_ERR_NOT_FINITE; model None, NaN arrays, the counts zero) for an item whose kernel
+    matrix has trace 0 (a mirror gain of 1, or weights that vanish), beside which the other items are computed."""
     ms = list(meshes)
     n = len(ms)
     if n == 0 or n > 65535:
         raise ValueError("at least one mesh, at most 65,535 a call")
     ks = list(kernels)
-    if ks and isinstance(ks[0], _data.GaussianKernelTerm):
+    if ks and isinstance(ks[0], _KERNEL_TERMS):
         ks = [ks] * n
     if len(ks) != n:
         raise ValueError("one kernel (a list of terms) per mesh, or one for all")
@@ -1172,6 +1179,9 @@ def gp_models(meshes, kernels, n_pivots, rank=None, rel_tolerance=0.0, device=0,
         if w not in _GP_WANT:
             raise ValueError(f"unknown output {w!r}: one of {_GP_WANT}")
     pts, terms = [], []
+    # a call whose every term is a plain Gaussian one goes through icp_gp_models_many, any other through icp_gp_models_general_many
+    general = not all(isinstance(k, _data.GaussianKernelTerm) and k.plain for kb in ks for k in kb)
+    keep = []  # (the weights' arrays, alive while the library reads them)
     for b in range(n):
         p = _f64(ms[b].points)
         if p.ndim != 2 or p.shape[1] != 3 or p.shape[0] < 1:
@@ -1185,16 +1195,42 @@ def gp_models(meshes, kernels, n_pivots, rank=None, rel_tolerance=0.0, device=0,
         kb = list(ks[b])
         if not (1 <= len(kb) <= GP_MAX_TERMS):
             raise ValueError(f"item {b}: a kernel has 1 to {GP_MAX_TERMS} terms")
-        arr = (nat.KernelTerm * len(kb))()
+        arr = ((nat.KernelTermGeneral if general else nat.KernelTerm) * len(kb))()
         for t, k in enumerate(kb):
-            if not (math.isfinite(k.scale) and k.scale > 0.0 and math.isfinite(k.sigma) and k.sigma > 0.0 and math.isfinite(k.sigma * k.sigma)
-                    and k.sigma * k.sigma > 0.0):
+            if not isinstance(k, _KERNEL_TERMS):
+                raise ValueError(f"item {b}, term {t}: a data.GaussianKernelTerm or a data.BSplineKernelTerm")
+            gauss = isinstance(k, _data.GaussianKernelTerm)
+            if gauss and not (math.isfinite(k.scale) and k.scale > 0.0 and math.isfinite(k.sigma) and k.sigma > 0.0
+                              and math.isfinite(k.sigma * k.sigma) and k.sigma * k.sigma > 0.0):
                 raise ValueError(f"item {b}, term {t}: scale and sigma must be finite and positive")
+            if not gauss:
+                if not (math.isfinite(k.scale) and k.scale > 0.0):
+                    raise ValueError(f"item {b}, term {t}: scale must be finite and positive")
+                if not (-GP_MAX_LEVEL <= k.level <= GP_MAX_LEVEL) or not (math.ldexp(float(np.abs(p).max()), k.level) < 2.0 ** 31):
+                    raise ValueError(f"item {b}, term {t}: -{GP_MAX_LEVEL} <= level <= {GP_MAX_LEVEL} and |coordinate| * 2^level < 2^31")
             a = _f64(k.A)
             if a.shape != (3, 3) or not _psd3(a):
                 raise ValueError(f"item {b}, term {t}: A must be an exactly symmetric, positive semi-definite, non-zero 3 x 3 matrix")
-            arr[t].scale, arr[t].sigma = k.scale, k.sigma
+            arr[t].scale = k.scale
             arr[t].A[:] = a.reshape(-1).tolist()
+            if not general:
+                arr[t].sigma = k.sigma
+                continue
+            if k.mirror_axis not in (0, 1, 2) or not (0.0 <= k.mirror_gain <= 1.0):
+                raise ValueError(f"item {b}, term {t}: mirror_axis is 0, 1 or 2 and 0 <= mirror_gain <= 1")
+            ax = k.mirror_axis
+            if k.mirror_gain > 0.0 and any(a[ax, c] != 0.0 or a[c, ax] != 0.0 for c in range(3) if c != ax):
+                raise ValueError(f"item {b}, term {t}: with a mirror gain, A must not couple the mirror axis to the others")
+            arr[t].struct_size = C.sizeof(nat.KernelTermGeneral)
+            arr[t].kind = nat.KERNEL_GAUSSIAN if gauss else nat.KERNEL_BSPLINE3
+            arr[t].sigma, arr[t].level = (k.sigma, 0) if gauss else (0.0, k.level)
+            arr[t].mirror_axis, arr[t].mirror_gain = ax, k.mirror_gain
+            if k.weights is not None:
+                w = _f64(k.weights)
+                if w.shape != (p.shape[0],) or not np.all(np.isfinite(w)) or not np.all(w >= 0.0) or not np.any(w > 0.0):
+                    raise ValueError(f"item {b}, term {t}: weights are [N], finite, >= 0 and not all zero")
+                keep.append(w)
+                arr[t].weights = _d(w)
         pts.append(p)
         terms.append(arr)
     shapes = {"variance": lambda b: (rk[b],), "basis": lambda b: (3 * pts[b].shape[0], rk[b]), "pivots": lambda b: (mp[b],),
@@ -1204,17 +1240,26 @@ def gp_models(meshes, kernels, n_pivots, rank=None, rel_tolerance=0.0, device=0,
     status = np.zeros(n, dtype=np.int32)
     outs = [None if w not in want else _ptr_array([o[w] for o in out], nat.c_int_p, _i) if w == "pivots"
             else _ptr_array([o[w] for o in out]) for w in _GP_WANT]
-    c_terms = (C.POINTER(nat.KernelTerm) * n)(*[C.cast(a, C.POINTER(nat.KernelTerm)) for a in terms])
+    term_t = nat.KernelTermGeneral if general else nat.KernelTerm
+    c_terms = (C.POINTER(term_t) * n)(*[C.cast(a, C.POINTER(term_t)) for a in terms])
     n_pts = np.array([p.shape[0] for p in pts], dtype=np.int32)
     n_terms = np.array([len(a) for a in terms], dtype=np.int32)
     a_mp, a_rk, a_tol = np.array(mp, dtype=np.int32), np.array(rk, dtype=np.int32), np.array(tol, dtype=np.float64)
-    rc = nat.lib().icp_gp_models_many(n, int(device), _i(n_pts), _ptr_array(pts), _i(n_terms), c_terms, _i(a_mp), _i(a_rk), _d(a_tol),
-                                      outs[0], outs[1], outs[2], outs[3], _ptr_array(list(info)), _i(status))
-    nat.check(rc, "icp_gp_models_many")
+    if general:
+        rc = nat.lib().icp_gp_models_general_many(n, int(device), _i(n_pts), _ptr_array(pts), _i(n_terms), c_terms, _i(a_mp), _i(a_rk),
+                                                  _d(a_tol), outs[0], outs[1], outs[2], outs[3], _ptr_array(list(info)), _i(status))
+        if rc != 0 and (not status.any() or not np.all((status == 0) | (status == GP_NOT_FINITE))):
+            nat.check(rc, "icp_gp_models_general_many")  # a whole-call error, or an item the checks above should have refused
+    else:
+        rc = nat.lib().icp_gp_models_many(n, int(device), _i(n_pts), _ptr_array(pts), _i(n_terms), c_terms, _i(a_mp), _i(a_rk), _d(a_tol),
+                                          outs[0], outs[1], outs[2], outs[3], _ptr_array(list(info)), _i(status))
+        nat.check(rc, "icp_gp_models_many")
     res = []
     for b in range(n):
         me, re = int(info[b, 0]), int(info[b, 1])
         d = {"n_pivots": me, "rank": re, "total_variance": float(info[b, 2]), "approximated_variance": float(info[b, 3])}
+        if general:
+            d["status"] = int(status[b])
         if "variance" in want:
             d["variance"] = out[b]["variance"][:re].copy()
         if "pivots" in want:
@@ -1222,12 +1267,56 @@ def gp_models(meshes, kernels, n_pivots, rank=None, rel_tolerance=0.0, device=0,
         if "residual" in want:
             d["residual"] = out[b]["residual"]
         model = None
-        if "variance" in want and "basis" in want:
+        if "variance" in want and "basis" in want and status[b] == 0:
             model = _data.StatisticalMeshModel(pts[b], ms[b].cells, np.zeros_like(pts[b]), out[b]["basis"][:, :re], d["variance"])
         res.append((model, d))
     return res
 
 
 def gp_model(mesh, kernel, n_pivots, rank=None, rel_tolerance=0.0, device=0, want=_GP_WANT):
-    """One item of gp_models: (model, info) of `kernel` (a list of data.GaussianKernelTerm) on `mesh`."""
+    """One item of gp_models: (model, info) of `kernel` (a list of data.GaussianKernelTerm and data.BSplineKernelTerm) on `mesh`."""
     return gp_models([mesh], [list(kernel)], n_pivots, rank, rel_tolerance, device, want)[0]
+
+
+def region_weights(points, region_points, stddev=40.0, device=0):
+    """Smoothed region weights (icp_region_weights_many; apps/bfm/FaceMask.scala computeSmoothedRegions): w[i] = exp(−d²/stddev²), d the
+    distance from points[i] to the nearest of region_points; exactly 1 at a region point.  One item — points [N, 3], region_points
+    [M, 3], M >= 1 -> [N] — or lists of them -> a list; stddev a number for all or one per item.  One launch for the whole call."""
+    single = not isinstance(points, (list, tuple))
+    ps = [points] if single else list(points)
+    rs = [region_points] if single else list(region_points)
+    n = len(ps)
+    if n == 0 or n > 65535 or len(rs) != n:
+        raise ValueError("at least one item, at most 65,535 a call, and one region per item")
+    sd = list(stddev) if isinstance(stddev, (list, tuple, np.ndarray)) else [stddev] * n
+    if len(sd) != n:
+        raise ValueError("stddev: a number, or one per item")
+    ps, rs = [_f64(p) for p in ps], [_f64(r) for r in rs]
+    sd = np.array([float(s) for s in sd], dtype=np.float64)
+    for b in range(n):
+        for a, name in ((ps[b], "points"), (rs[b], "region_points")):
+            if a.ndim != 2 or a.shape[1] != 3 or a.shape[0] < 1 or not np.all(np.isfinite(a)):
+                raise ValueError(f"item {b}: {name} are [n >= 1, 3] and finite")
+        if not (math.isfinite(sd[b]) and sd[b] > 0.0 and math.isfinite(sd[b] * sd[b]) and sd[b] * sd[b] > 0.0):
+            raise ValueError(f"item {b}: stddev must be finite and positive")
+    out = [np.zeros(p.shape[0]) for p in ps]
+    status = np.zeros(n, dtype=np.int32)
+    n_pts = np.array([p.shape[0] for p in ps], dtype=np.int32)
+    n_reg = np.array([r.shape[0] for r in rs], dtype=np.int32)
+    rc = nat.lib().icp_region_weights_many(n, int(device), _i(n_pts), _ptr_array(ps), _i(n_reg), _ptr_array(rs), _d(sd), _ptr_array(out),
+                                           _i(status))
+    nat.check(rc, "icp_region_weights_many")
+    return out[0] if single else out
+
+
+def face_kernel(mesh, mask=None, device=0):
+    """The kernel of apps/bfm/FaceKernel.scala on `mesh` (a data.TriangleMesh): five data.BSplineKernelTerm, (level, scale) = (−6, 128),
+    (−5, 64), (−4, 32), (−3, 10), (−2, 4), A = I, mirrored about x = 0 with gain 0.7 (0.7·symmetrize(k) + 0.3·k), each weighted by the
+    smoothed region of its level in `mask` (a data.FaceMask; stddev 40).  mask=None is bfm/CreateGPModel.scala's mask of 3 everywhere:
+    weights 1, nothing runs on the device.  Otherwise the five levels' weights come from ONE icp_region_weights_many call."""
+    levels = _data.FACE_KERNEL_LEVELS
+    weights = [None] * len(levels)
+    if mask is not None:
+        regions = [mask.region(mesh, level) for level, _ in levels]
+        weights = region_weights([mesh.points] * len(levels), regions, 40.0, device)
+    return [_data.BSplineKernelTerm(scale, level, np.eye(3), w, _data.FACE_KERNEL_MIRROR_GAIN, 0) for (level, scale), w in zip(levels, weights)]

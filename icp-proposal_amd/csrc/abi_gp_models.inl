@@ -1,5 +1,7 @@
-// abi_gp_models.inl — C ABI: icp_gp_models_many, Gaussian-process shape models of analytic kernels on many reference meshes
-// (kernels_gp_model.hip; the resident decompositions of kernels_eigen.hip).
+// abi_gp_models.inl — C ABI: icp_gp_models_many and icp_gp_models_general_many, Gaussian-process shape models of analytic kernels on
+// many reference meshes (kernels_gp_model.hip; the resident decompositions of kernels_eigen.hip), and icp_region_weights_many, the
+// smoothed region weights of the face kernel's terms.  Both model entry points reach gpm_models_run: icp_gp_models_many restates its
+// terms as plain general ones (Gaussian, no weights, no mirror), and an item of plain terms runs the plain expressions.
 //
 // Item b: the pivoted Cholesky factor L of its kernel matrix, up to n_pivots columns (one launch per pivot step carries every item
 // of the call), then LᵀL = W·Θ·Wᵀ and the model (Θ/N, √N·L·W·Θ^-1/2).  The host synchronises ONCE behind the pivot loop, to read how
@@ -45,18 +47,43 @@ struct StreamScope {
   explicit StreamScope(int device) : st(take_stream(device, false, 0)) {}
   ~StreamScope() { give_stream(st); }
 };
-}  // namespace
+// a term with icp_gp_models_many's meaning: Gaussian, no weights, no mirror
+bool gpm_term_plain(const icp_kernel_term_general& k) { return k.kind == ICP_KERNEL_GAUSSIAN && !k.weights && k.mirror_gain == 0.0; }
 
-extern "C" {
+// one term of item b on N points; `lattice` = the largest |coordinate| of the item
+bool gpm_term_good(const icp_kernel_term_general& k, long long N, double lattice) {
+  if (k.struct_size != (int32_t)sizeof(icp_kernel_term_general)) return false;
+  if (!(std::isfinite(k.scale) && k.scale > 0.0) || !gpm_psd(k.A)) return false;
+  if (k.kind == ICP_KERNEL_GAUSSIAN) {
+    if (!(std::isfinite(k.sigma) && k.sigma > 0.0 && std::isfinite(k.sigma * k.sigma) && k.sigma * k.sigma > 0.0)) return false;
+  } else if (k.kind == ICP_KERNEL_BSPLINE3) {
+    if (k.level < -32 || k.level > 32) return false;
+    if (!(std::ldexp(lattice, k.level) < 0x1p31)) return false;  // lattice indices are exact doubles
+  } else {
+    return false;
+  }
+  if (k.mirror_axis < 0 || k.mirror_axis > 2 || !(k.mirror_gain >= 0.0 && k.mirror_gain <= 1.0)) return false;
+  if (k.mirror_gain > 0.0)
+    for (int c = 0; c < 3; ++c)
+      if (c != k.mirror_axis && (k.A[3 * k.mirror_axis + c] != 0.0 || k.A[3 * c + k.mirror_axis] != 0.0)) return false;
+  if (k.weights) {
+    bool positive = false;
+    for (long long i = 0; i < N; ++i) {
+      if (!(std::isfinite(k.weights[i]) && k.weights[i] >= 0.0)) return false;
+      positive = positive || k.weights[i] > 0.0;
+    }
+    if (!positive) return false;
+  }
+  return true;
+}
 
-int icp_gp_models_many(int32_t n_items, int device, const int32_t* n_points, const double* const* points, const int32_t* n_terms,
-                       const icp_kernel_term* const* terms, const int32_t* n_pivots, const int32_t* rank, const double* rel_tolerance,
-                       double* const* variance_out, double* const* basis_out, int32_t* const* pivots_out, double* const* residual_out,
-                       double* const* info_out, int32_t* status) {
-  std::vector<int> item_status;
-  int rc = guard([&] {
-    require(n_items >= 1 && n_items <= 65535, "n_items must lie in [1, 65535]");
-    require(n_points && points && n_terms && terms && n_pivots && rank && status, "null argument");
+// the body of both entry points, inside their guard.  general_entry: an item whose pivot loop leaves no column is that item's failure
+// (icp_gp_models_general_many) instead of the call's.
+void gpm_models_run(int32_t n_items, int device, const int32_t* n_points, const double* const* points, const int32_t* n_terms,
+                    const icp_kernel_term_general* const* terms, const int32_t* n_pivots, const int32_t* rank, const double* rel_tolerance,
+                    double* const* variance_out, double* const* basis_out, int32_t* const* pivots_out, double* const* residual_out,
+                    double* const* info_out, std::vector<int>& item_status, bool general_entry) {
+  {
     const int B = n_items;
     // ---- validation, item by item, before the device is touched
     item_status.assign(B, ICP_OK);
@@ -69,19 +96,19 @@ int icp_gp_models_many(int32_t n_items, int device, const int32_t* n_points, con
         if (n_terms[b] < 1 || n_terms[b] > kGpmMaxTerms) return false;
         if (!(rank[b] >= 1 && rank[b] <= n_pivots[b] && n_pivots[b] <= kGpmMaxPivots && (long long)n_pivots[b] <= 3 * N)) return false;
         if (rel_tolerance && !(rel_tolerance[b] >= 0.0 && rel_tolerance[b] < 1.0)) return false;
-        for (int t = 0; t < n_terms[b]; ++t) {
-          const icp_kernel_term& k = terms[b][t];
-          if (!(std::isfinite(k.scale) && k.scale > 0.0 && std::isfinite(k.sigma) && k.sigma > 0.0 && std::isfinite(k.sigma * k.sigma))) return false;
-          if (!(k.sigma * k.sigma > 0.0) || !gpm_psd(k.A)) return false;
-        }
-        for (long long i = 0; i < 3 * N; ++i)
+        double lattice = 0.0;
+        for (long long i = 0; i < 3 * N; ++i) {
           if (!std::isfinite(points[b][i])) return false;
+          lattice = std::max(lattice, std::fabs(points[b][i]));
+        }
+        for (int t = 0; t < n_terms[b]; ++t)
+          if (!gpm_term_good(terms[b][t], N, lattice)) return false;
         return true;
       };
       if (good()) live.push_back(b);
       else item_status[b] = ICP_ERR_INVALID_ARG;
     }
-    const int n_live = (int)live.size();
+    int n_live = (int)live.size();
     if (n_live == 0) return;
 
     int ndev = 0;
@@ -101,8 +128,18 @@ int icp_gp_models_many(int32_t n_items, int device, const int32_t* n_points, con
     std::vector<GpmItem> h_items(n_live);
     std::vector<size_t> off_pts(n_live + 1, 0), off_L(n_live + 1, 0), off_part(n_live + 1, 0), off_piv(n_live + 1, 0);
     int nblk_max = 1, m_max = 1;
+    // a weighted term's weights travel behind the points, in the same upload: term t of item q at off_w[q * kGpmMaxTerms + t]
+    std::vector<size_t> off_w((size_t)n_live * kGpmMaxTerms, 0);
+    size_t n_weights = 0;
+    bool any_general = false;
     for (int q = 0; q < n_live; ++q) {
       const int b = live[q], R = 3 * n_points[b], nblk = cdiv(R, kGpmBlockRows);
+      for (int t = 0; t < n_terms[b]; ++t) {
+        any_general = any_general || !gpm_term_plain(terms[b][t]);
+        if (!terms[b][t].weights) continue;
+        off_w[(size_t)q * kGpmMaxTerms + t] = n_weights;
+        n_weights += (size_t)n_points[b];
+      }
       off_pts[q + 1] = off_pts[q] + (size_t)R;
       off_L[q + 1] = off_L[q] + (size_t)R * n_pivots[b];
       off_part[q + 1] = off_part[q] + 2 * (size_t)nblk;
@@ -114,8 +151,15 @@ int icp_gp_models_many(int32_t n_items, int device, const int32_t* n_points, con
     DBuf<int> d_pidx, d_meff, d_piv;
     DBuf<GpmItem> d_items;
     {
-      std::vector<double> h_pts(off_pts[n_live]);
-      for (int q = 0; q < n_live; ++q) std::memcpy(&h_pts[off_pts[q]], points[live[q]], sizeof(double) * (off_pts[q + 1] - off_pts[q]));
+      const size_t w0 = off_pts[n_live];
+      std::vector<double> h_pts(w0 + n_weights);
+      for (int q = 0; q < n_live; ++q) {
+        const int b = live[q];
+        std::memcpy(&h_pts[off_pts[q]], points[b], sizeof(double) * (off_pts[q + 1] - off_pts[q]));
+        for (int t = 0; t < n_terms[b]; ++t)
+          if (terms[b][t].weights)
+            std::memcpy(&h_pts[w0 + off_w[(size_t)q * kGpmMaxTerms + t]], terms[b][t].weights, sizeof(double) * (size_t)n_points[b]);
+      }
       NullStreamBatch _nb;
       d_pts.upload(h_pts.data(), h_pts.size());
       d_d.alloc(off_pts[n_live]);
@@ -133,8 +177,14 @@ int icp_gp_models_many(int32_t n_items, int device, const int32_t* n_points, con
           GpmTerm& tm = it.terms[t];
           tm = GpmTerm{};
           if (t >= it.n_terms) continue;
-          tm.scale = terms[b][t].scale; tm.sigma2 = terms[b][t].sigma * terms[b][t].sigma;
-          std::memcpy(tm.A, terms[b][t].A, sizeof(tm.A));
+          const icp_kernel_term_general& k = terms[b][t];
+          tm.scale = k.scale;
+          std::memcpy(tm.A, k.A, sizeof(tm.A));
+          tm.kind = k.kind; tm.axis = k.mirror_axis; tm.gain = k.mirror_gain;
+          if (k.kind == ICP_KERNEL_GAUSSIAN) tm.sigma2 = k.sigma * k.sigma;
+          else tm.c = std::ldexp(1.0, k.level);
+          if (k.weights) tm.w = d_pts.p + w0 + off_w[(size_t)q * kGpmMaxTerms + t];
+          it.general = it.general || !gpm_term_plain(k);
         }
         it.pts = d_pts.p + off_pts[q]; it.d = d_d.p + off_pts[q]; it.L = d_L.p + off_L[q];
         it.pmax = d_pmax.p + off_part[q]; it.psum = d_psum.p + off_part[q]; it.pidx = d_pidx.p + off_part[q];
@@ -142,8 +192,8 @@ int icp_gp_models_many(int32_t n_items, int device, const int32_t* n_points, con
       }
       d_items.upload(h_items.data(), h_items.size());
     }
-    launch_gpm_init(st, n_live, nblk_max, d_items.p);
-    for (int j = 0; j < m_max; ++j) launch_gpm_pivot_step(st, n_live, nblk_max, j, d_items.p);
+    launch_gpm_init(st, n_live, nblk_max, d_items.p, any_general);
+    for (int j = 0; j < m_max; ++j) launch_gpm_pivot_step(st, n_live, nblk_max, j, d_items.p, any_general);
     std::vector<int> h_meff(n_live), h_piv(off_piv[n_live]);
     std::vector<double> h_start(2 * (size_t)n_live);
     HIP_OK(hipMemcpyAsync(h_meff.data(), d_meff.p, sizeof(int) * h_meff.size(), hipMemcpyDeviceToHost, st));
@@ -153,9 +203,32 @@ int icp_gp_models_many(int32_t n_items, int device, const int32_t* n_points, con
       if (residual_out && residual_out[live[q]])
         HIP_OK(hipMemcpyAsync(residual_out[live[q]], d_d.p + off_pts[q], sizeof(double) * (off_pts[q + 1] - off_pts[q]), hipMemcpyDeviceToHost, st));
     HIP_OK(hipStreamSynchronize(st));  // the one synchronisation behind the loop: the effective pivot counts
+    // plain terms: A ≠ 0 and a tolerance < 1 leave a column.  General terms can make trace(K) = 0 (a mirror gain of 1, weights that
+    // vanish where A does not): such an item fails alone — NaN outputs, info zero — and takes no part in the m-space work
+    std::vector<int> with_column;
     for (int q = 0; q < n_live; ++q) {
-      if (h_meff[q] < 1 || h_meff[q] > n_pivots[live[q]]) fail(ICP_ERR_DEVICE, "the pivot loop left no column");  // (A ≠ 0, tolerance < 1: cannot be)
-      if (pivots_out && pivots_out[live[q]]) std::memcpy(pivots_out[live[q]], &h_piv[off_piv[q]], sizeof(int) * (size_t)n_pivots[live[q]]);
+      const int b = live[q];
+      if (h_meff[q] > n_pivots[b] || (h_meff[q] < 1 && !general_entry)) fail(ICP_ERR_DEVICE, "the pivot loop left no column");
+      if (pivots_out && pivots_out[b]) std::memcpy(pivots_out[b], &h_piv[off_piv[q]], sizeof(int) * (size_t)n_pivots[b]);
+      if (h_meff[q] >= 1) {
+        with_column.push_back(q);
+        continue;
+      }
+      item_status[b] = ICP_ERR_NOT_FINITE;
+      const size_t R = 3 * (size_t)n_points[b];
+      if (variance_out && variance_out[b]) std::fill(variance_out[b], variance_out[b] + rank[b], (double)NAN);
+      if (basis_out && basis_out[b]) std::fill(basis_out[b], basis_out[b] + R * rank[b], (double)NAN);
+      if (residual_out && residual_out[b]) std::fill(residual_out[b], residual_out[b] + R, (double)NAN);
+      if (info_out && info_out[b]) std::fill(info_out[b], info_out[b] + 4, 0.0);
+    }
+    if ((int)with_column.size() != n_live) {  // (the records behind the loop: start of L, columns made, trace)
+      for (size_t i = 0; i < with_column.size(); ++i) {
+        const int q = with_column[i];
+        live[i] = live[q]; off_L[i] = off_L[q]; h_meff[i] = h_meff[q];
+        h_start[2 * i] = h_start[2 * (size_t)q]; h_start[2 * i + 1] = h_start[2 * (size_t)q + 1];
+      }
+      n_live = (int)with_column.size();
+      if (n_live == 0) return;
     }
 
     // ---- m-space: kGpmGroup slots of scratch sized for the call's largest decomposition; the chunk
@@ -349,12 +422,142 @@ int icp_gp_models_many(int32_t n_items, int device, const int32_t* n_points, con
         info_out[b][2] = h_start[2 * (size_t)q + 1] / sp.n_points; info_out[b][3] = sum;
       }
     }
+  }
+}
+}  // namespace
+
+extern "C" {
+
+int icp_gp_models_many(int32_t n_items, int device, const int32_t* n_points, const double* const* points, const int32_t* n_terms,
+                       const icp_kernel_term* const* terms, const int32_t* n_pivots, const int32_t* rank, const double* rel_tolerance,
+                       double* const* variance_out, double* const* basis_out, int32_t* const* pivots_out, double* const* residual_out,
+                       double* const* info_out, int32_t* status) {
+  std::vector<int> item_status;
+  int rc = guard([&] {
+    require(n_items >= 1 && n_items <= 65535, "n_items must lie in [1, 65535]");
+    require(n_points && points && n_terms && terms && n_pivots && rank && status, "null argument");
+    // the terms restated as plain general ones (an item without terms, or with a count outside the limits, keeps a null list: refused)
+    std::vector<std::vector<icp_kernel_term_general>> restated(n_items);
+    std::vector<const icp_kernel_term_general*> lists(n_items, nullptr);
+    for (int b = 0; b < n_items; ++b) {
+      if (!terms[b] || n_terms[b] < 1 || n_terms[b] > kGpmMaxTerms) continue;
+      restated[b].resize(n_terms[b]);
+      for (int t = 0; t < n_terms[b]; ++t) {
+        icp_kernel_term_general& g = restated[b][t];
+        g = icp_kernel_term_general{};
+        g.struct_size = (int32_t)sizeof(icp_kernel_term_general);
+        g.kind = ICP_KERNEL_GAUSSIAN;
+        g.scale = terms[b][t].scale; g.sigma = terms[b][t].sigma;
+        std::memcpy(g.A, terms[b][t].A, sizeof(g.A));
+      }
+      lists[b] = restated[b].data();
+    }
+    gpm_models_run(n_items, device, n_points, points, n_terms, lists.data(), n_pivots, rank, rel_tolerance, variance_out, basis_out, pivots_out,
+                   residual_out, info_out, item_status, false);
   });
   if (rc != ICP_OK) return rc;
   return report_item_status(n_items, item_status, status, [](int code) {
     return code == ICP_ERR_INVALID_ARG ? "an item is outside the limits: 1 <= rank <= n_pivots <= min(256, 3N), 1..8 terms with scale > 0, sigma > 0 "
                                          "and a symmetric positive semi-definite A, finite points, 0 <= rel_tolerance < 1"
                                        : "the decomposition of an item's Gram matrix did not converge";
+  });
+}
+
+int icp_gp_models_general_many(int32_t n_items, int device, const int32_t* n_points, const double* const* points, const int32_t* n_terms,
+                               const icp_kernel_term_general* const* terms, const int32_t* n_pivots, const int32_t* rank,
+                               const double* rel_tolerance, double* const* variance_out, double* const* basis_out, int32_t* const* pivots_out,
+                               double* const* residual_out, double* const* info_out, int32_t* status) {
+  std::vector<int> item_status;
+  int rc = guard([&] {
+    require(n_items >= 1 && n_items <= 65535, "n_items must lie in [1, 65535]");
+    require(n_points && points && n_terms && terms && n_pivots && rank && status, "null argument");
+    gpm_models_run(n_items, device, n_points, points, n_terms, terms, n_pivots, rank, rel_tolerance, variance_out, basis_out, pivots_out,
+                   residual_out, info_out, item_status, true);
+  });
+  if (rc != ICP_OK) return rc;
+  return report_item_status(n_items, item_status, status, [](int code) {
+    return code == ICP_ERR_INVALID_ARG
+               ? "an item is outside the limits: those of icp_gp_models_many; struct_size; a kind of 0 or 1; a B-spline level in [-32, 32] with "
+                 "|coordinate| * 2^level < 2^31; 0 <= mirror_gain <= 1, mirror_axis 0..2, an A that does not couple the mirror axis when the "
+                 "gain is positive; weights finite, >= 0 and not all zero"
+               : "an item's pivot loop left no column (trace K = 0), or the decomposition of its Gram matrix did not converge";
+  });
+}
+
+int icp_region_weights_many(int32_t n_items, int device, const int32_t* n_points, const double* const* points, const int32_t* n_region,
+                            const double* const* region_points, const double* stddev, double* const* weights_out, int32_t* status) {
+  std::vector<int> item_status;
+  int rc = guard([&] {
+    require(n_items >= 1 && n_items <= 65535, "n_items must lie in [1, 65535]");
+    require(n_points && points && n_region && region_points && stddev && weights_out && status, "null argument");
+    item_status.assign(n_items, ICP_OK);
+    std::vector<int> live;
+    for (int b = 0; b < n_items; ++b) {
+      auto good = [&] {
+        if (!points[b] || !region_points[b] || !weights_out[b]) return false;
+        const long long N = n_points[b], M = n_region[b];
+        if (N < 1 || 3 * N > (long long)INT32_MAX || M < 1 || 3 * M > (long long)INT32_MAX) return false;
+        if (!(std::isfinite(stddev[b]) && stddev[b] > 0.0 && std::isfinite(stddev[b] * stddev[b]) && stddev[b] * stddev[b] > 0.0)) return false;
+        for (long long i = 0; i < 3 * N; ++i)
+          if (!std::isfinite(points[b][i])) return false;
+        for (long long i = 0; i < 3 * M; ++i)
+          if (!std::isfinite(region_points[b][i])) return false;
+        return true;
+      };
+      if (good()) live.push_back(b);
+      else item_status[b] = ICP_ERR_INVALID_ARG;
+    }
+    const int n_live = (int)live.size();
+    if (n_live == 0) return;
+    int ndev = 0;
+    hipError_t e = hipGetDeviceCount(&ndev);
+    if (e != hipSuccess || ndev <= 0)
+      fail(ICP_ERR_DEVICE, std::string("no usable HIP device (this library has no CPU fallback): ") + hipGetErrorString(e));
+    if (device < 0) {
+      const char* lr = std::getenv("LOCAL_RANK");
+      device = lr ? std::atoi(lr) % ndev : 0;
+    }
+    require(device < ndev, "device ordinal out of range");
+    DeviceScope _dev(device);
+    StreamScope _st(device);
+    hipStream_t st = _st.st;
+    // every item's points, then every item's region, in ONE upload; the weights come back as one copy per item
+    std::vector<size_t> off_p(n_live + 1, 0), off_r(n_live + 1, 0), off_o(n_live + 1, 0);
+    int n_max = 1;
+    for (int q = 0; q < n_live; ++q) {
+      off_p[q + 1] = off_p[q] + 3 * (size_t)n_points[live[q]];
+      off_r[q + 1] = off_r[q] + 3 * (size_t)n_region[live[q]];
+      off_o[q + 1] = off_o[q] + (size_t)n_points[live[q]];
+      n_max = std::max(n_max, (int)n_points[live[q]]);
+    }
+    std::vector<double> h_in(off_p[n_live] + off_r[n_live]);
+    std::vector<GpmRegion> h_items(n_live);
+    DBuf<double> d_in, d_w;
+    DBuf<GpmRegion> d_items;
+    {
+      for (int q = 0; q < n_live; ++q) {
+        std::memcpy(&h_in[off_p[q]], points[live[q]], sizeof(double) * (off_p[q + 1] - off_p[q]));
+        std::memcpy(&h_in[off_p[n_live] + off_r[q]], region_points[live[q]], sizeof(double) * (off_r[q + 1] - off_r[q]));
+      }
+      NullStreamBatch _nb;
+      d_in.upload(h_in.data(), h_in.size());
+      d_w.alloc(off_o[n_live]);
+      for (int q = 0; q < n_live; ++q) {
+        GpmRegion& it = h_items[q];
+        it.pts = d_in.p + off_p[q]; it.reg = d_in.p + off_p[n_live] + off_r[q]; it.w = d_w.p + off_o[q];
+        it.n = n_points[live[q]]; it.n_reg = n_region[live[q]];
+        it.s2 = stddev[live[q]] * stddev[live[q]];
+      }
+      d_items.upload(h_items.data(), h_items.size());
+    }
+    launch_gpm_region_weights(st, n_live, n_max, d_items.p);
+    for (int q = 0; q < n_live; ++q)
+      HIP_OK(hipMemcpyAsync(weights_out[live[q]], d_w.p + off_o[q], sizeof(double) * (off_o[q + 1] - off_o[q]), hipMemcpyDeviceToHost, st));
+    HIP_OK(hipStreamSynchronize(st));
+  });
+  if (rc != ICP_OK) return rc;
+  return report_item_status(n_items, item_status, status, [](int) {
+    return "an item is outside the limits: n_points >= 1, n_region >= 1, stddev > 0, finite points";
   });
 }
 

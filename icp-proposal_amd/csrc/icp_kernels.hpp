@@ -884,9 +884,17 @@ constexpr int kGpmMaxTerms = 8;     // kernel terms per item
 constexpr int kGpmMaxPivots = 256;  // what the resident decompositions serve
 constexpr int kGpmBlockRows = 256;  // rows of K a workgroup of the pivot loop owns: an item's partials are a function of its size alone
 constexpr int kGpmMaxSlabs = 32;    // row slabs of an item's Gram matrix, at most
-struct GpmTerm { double scale, sigma2, A[9]; };  // scale · exp(−‖x−y‖² / sigma2) · A
+// scale · exp(−‖x−y‖² / sigma2) · A (a plain term), or the general term of icp_gp_models_general_many:
+// scale · w(x) · w(y) · A · (b(x, y) + gain · s · b(x, ȳ)) with b the Gaussian (kind 0) or the cubic B-spline on cells of 1/c (kind 1)
+struct GpmTerm {
+  double scale, sigma2, A[9];
+  double c, gain;       // 2^level; the mirror gain γ
+  const double* w;      // [N] per-vertex weights (device) or null: 1
+  int kind, axis;       // ICP_KERNEL_GAUSSIAN / ICP_KERNEL_BSPLINE3; the mirror axis
+};
 struct GpmItem {        // one item's record (device), the same for every launch of the call
   int R, m, n_terms, nblk;  // rows 3N; pivots asked for; kernel terms; workgroups of the pivot loop = cdiv(R, kGpmBlockRows)
+  int general;          // 0: every term is plain (Gaussian, no weights, gain 0) and the plain expressions run
   double rel_tol;
   GpmTerm terms[kGpmMaxTerms];
   const double* pts;    // [R]
@@ -922,8 +930,18 @@ struct GpmPiece {       // rows row0 .. row0+rows-1 of one item's L·Op, residen
   int R, me, rank, ldb, row0, rows;
   double* out;          // [rows][rank]
 };
-void launch_gpm_init(hipStream_t st, int n_items, int nblk_max, const GpmItem* items);
-void launch_gpm_pivot_step(hipStream_t st, int n_items, int nblk_max, int step, const GpmItem* items);
+struct GpmRegion {      // one item of icp_region_weights_many (device)
+  const double* pts;    // [3·n] query points
+  const double* reg;    // [3·n_reg] the region's points
+  double* w;            // [n] exp(−(min squared distance to the region) / s2)
+  int n, n_reg;
+  double s2;            // stddev²
+};
+// any_general = false: the kernels as they are without general terms (the plain path's code and registers); true: one launch serves
+// plain and general items side by side, a plain item running the plain expressions
+void launch_gpm_init(hipStream_t st, int n_items, int nblk_max, const GpmItem* items, bool any_general);
+void launch_gpm_pivot_step(hipStream_t st, int n_items, int nblk_max, int step, const GpmItem* items, bool any_general);
+void launch_gpm_region_weights(hipStream_t st, int n_items, int n_max, const GpmRegion* items);
 int gpm_slab_rows(int R);  // a function of the item's size alone
 void launch_gpm_gram(hipStream_t st, int n, int mp_max, int slabs_max, const GpmSpace* items);
 void launch_gpm_refine(hipStream_t st, int n, int me_max, const GpmSpace* items);

@@ -15,6 +15,11 @@
 //                         not for a basis orthonormal to rounding), the refined eigenvalues, their descending order
 //   GP4 k_gpm_operand     Op = W·Θ^-1/2·√N in descending θ, zero-padded to 16s; the variances
 //   GP5 k_gpm_gemm        rows of L·Op on the f64 matrix cores into the chunk buffer: a wave owns 32 rows × 64 columns
+// General terms (icp_gp_models_general_many, what apps/bfm/CreateGPModel.scala needs: cubic B-spline base kernels, per-vertex weights on
+// both arguments, the mirror symmetrisation) run in the <true> instances of GP0 and GP1, which a call with at least one such item
+// launches; there an item's flag — uniform over the workgroup — chooses between the plain expressions and gpm_general_value.  A call
+// of plain items launches the <false> instances: the code as it is without general terms.  K's diagonal of a general item is the
+// kernel's value of the row against itself.  k_gpm_region_weights (icp_region_weights_many) makes FaceMask's smoothed region weights.
 // The decomposition between GP3 and GP4a is the chain's (kernels_eigen.hip) with sqrt_lambda ≡ 1; only its eigenvectors are used.
 //
 // Layout of L: column by column ([m][3N]).  GP1 reads one value per row and column made so far, a wave's 64 rows next to each other
@@ -75,7 +80,87 @@ __device__ __forceinline__ double gpm_kernel_value(const GpmItem& it, double x0,
   return acc;
 }
 
+// ---- general terms (icp_gp_models_general_many): B-spline, weighted, mirrored.  One operation at a time (the unit is built without
+// contraction); the lattice indices are doubles, exact below 2^31.
+__device__ __forceinline__ double gpm_beta3(double t) {
+  const double a = fabs(t);
+  if (a < 1.0) return (2.0 / 3.0 - a * a) + ((0.5 * a) * a) * a;
+  if (a < 2.0) return (((1.0 / 6.0) * (2.0 - a)) * (2.0 - a)) * (2.0 - a);
+  return 0.0;
+}
+// S(u, v) = Σ_k β(u − k)·β(v − k), k = ⌈max(u, v) − 2⌉ … ⌊min(u, v) + 2⌋ ascending: at most five k
+__device__ __forceinline__ double gpm_spline_sum(double u, double v) {
+  const double k0 = ceil(fmax(u, v) - 2.0), k1 = floor(fmin(u, v) + 2.0);
+  double s = 0.0;
+  for (double k = k0; k <= k1; k += 1.0) s = s + gpm_beta3(u - k) * gpm_beta3(v - k);
+  return s;
+}
+// the scalar base kernel of a term between x and p
+__device__ __forceinline__ double gpm_base(const GpmTerm& tm, double x0, double x1, double x2, double p0, double p1, double p2) {
+  if (tm.kind == 0) {
+    const double dx = x0 - p0, dy = x1 - p1, dz = x2 - p2;
+    const double d2 = (dx * dx + dy * dy) + dz * dz;
+    return exp(-(d2 / tm.sigma2));
+  }
+  const double c = tm.c;
+  return (gpm_spline_sum(x0 * c, p0 * c) * gpm_spline_sum(x1 * c, p1 * c)) * gpm_spline_sum(x2 * c, p2 * c);
+}
+// K[3·v + c][3·vp + cp] of a general item, the terms summed in order: ((scale·(w(v)·w(vp)))·(b(x, p) + (γ·s_c)·b(x, p̄)))·A[c][cp].
+// A plain term among them has gpm_kernel_value's bits (scale·1 = scale, b + 0·b̄ = b).  `pv` is the pivot as GP1 stages it, uniform
+// over the workgroup: the point p [0..2], term t's mirrored point [3 + 3t ..], term t's weight of the pivot's vertex [kGpmPivotW + t].
+constexpr int kGpmPivotW = 3 + 3 * kGpmMaxTerms, kGpmPivotDoubles = kGpmPivotW + kGpmMaxTerms;
+__device__ __forceinline__ double gpm_general_value(const GpmItem& it, int v, double x0, double x1, double x2, int c, const double* pv, int cp) {
+  double acc = 0.0;
+  for (int t = 0; t < it.n_terms; ++t) {
+    const GpmTerm& tm = it.terms[t];
+    const double a = tm.A[3 * c + cp];
+    double ww = 1.0;
+    if (tm.w) ww = as_global(tm.w)[v] * pv[kGpmPivotW + t];
+    double val = gpm_base(tm, x0, x1, x2, pv[0], pv[1], pv[2]);
+    if (tm.gain > 0.0) {
+      const double sgn = c == tm.axis ? -1.0 : 1.0;
+      const double bm = gpm_base(tm, x0, x1, x2, pv[3 + 3 * t], pv[4 + 3 * t], pv[5 + 3 * t]);
+      val = val + (tm.gain * sgn) * bm;
+    }
+    acc = acc + ((tm.scale * ww) * val) * a;
+  }
+  return acc;
+}
+// the pivot of a general item into `pv` (LDS), by the workgroup's first kGpmPivotDoubles threads; vp = the pivot's vertex
+__device__ __forceinline__ void gpm_stage_pivot(const GpmItem& it, int vp, double* pv) {
+  const int t = threadIdx.x;
+  const global_ptr<const double> pts = as_global(it.pts);
+  if (t < 3) {
+    pv[t] = pts[3 * vp + t];
+  } else if (t < kGpmPivotW) {
+    const int k = (t - 3) / 3, a = (t - 3) - 3 * k;
+    const double x = pts[3 * vp + a];
+    pv[t] = k < it.n_terms && a == it.terms[k].axis ? -x : x;
+  } else if (t < kGpmPivotDoubles) {
+    const int k = t - kGpmPivotW;
+    pv[t] = k < it.n_terms && it.terms[k].w ? as_global(it.terms[k].w)[vp] : 1.0;
+  }
+}
+// d[3·v + c] of a general item: gpm_general_value's expression of the row against itself
+__device__ __forceinline__ double gpm_general_diagonal(const GpmItem& it, int v, double x0, double x1, double x2, int c) {
+  double acc = 0.0;
+  for (int t = 0; t < it.n_terms; ++t) {
+    const GpmTerm& tm = it.terms[t];
+    double ww = 1.0;
+    if (tm.w) ww = as_global(tm.w)[v] * as_global(tm.w)[v];
+    double val = gpm_base(tm, x0, x1, x2, x0, x1, x2);
+    if (tm.gain > 0.0) {
+      const double sgn = c == tm.axis ? -1.0 : 1.0;
+      const double bm = gpm_base(tm, x0, x1, x2, tm.axis == 0 ? -x0 : x0, tm.axis == 1 ? -x1 : x1, tm.axis == 2 ? -x2 : x2);
+      val = val + (tm.gain * sgn) * bm;
+    }
+    acc = acc + ((tm.scale * ww) * val) * tm.A[4 * c];
+  }
+  return acc;
+}
+
 // GP0.  blockIdx = (block of rows, item).
+template <bool kGeneral>
 __global__ void __launch_bounds__(kGpmBlockRows) k_gpm_init(const GpmItem* __restrict__ items) {
   __shared__ double sv[kGpmBlockRows], ss[kGpmBlockRows];
   __shared__ int si[kGpmBlockRows];
@@ -86,7 +171,14 @@ __global__ void __launch_bounds__(kGpmBlockRows) k_gpm_init(const GpmItem* __res
   if (row < it.R) {
     const int c = row % 3;
     double acc = 0.0;
-    for (int k = 0; k < it.n_terms; ++k) acc = acc + it.terms[k].scale * it.terms[k].A[4 * c];
+    if (kGeneral && it.general) {  // (uniform over the workgroup) the kernel's value of the row against itself
+      const int v = row / 3;
+      const global_ptr<const double> pts = as_global(it.pts);
+      const double x0 = pts[3 * v], x1 = pts[3 * v + 1], x2 = pts[3 * v + 2];
+      acc = gpm_general_diagonal(it, v, x0, x1, x2, c);
+    } else {
+      for (int k = 0; k < it.n_terms; ++k) acc = acc + it.terms[k].scale * it.terms[k].A[4 * c];
+    }
     it.d[row] = acc;
     x = GpmBest{acc, row, acc};
   }
@@ -99,10 +191,12 @@ __global__ void __launch_bounds__(kGpmBlockRows) k_gpm_init(const GpmItem* __res
 }
 
 // GP1.  blockIdx = (block of rows, item); `step` = j.  Reads the partials' half j & 1, writes the other one.
+template <bool kGeneral>
 __global__ void __launch_bounds__(kGpmBlockRows) k_gpm_pivot_step(const GpmItem* __restrict__ items, int step) {
   __shared__ double sv[kGpmBlockRows], ss[kGpmBlockRows];
   __shared__ int si[kGpmBlockRows];
   __shared__ double Lp[kGpmMaxPivots];
+  __shared__ double pv[kGpmPivotDoubles];  // (the <true> instance alone uses it)
   const GpmItem& it = items[blockIdx.y];
   if ((int)blockIdx.x >= it.nblk || step >= it.m) return;
   const int t = threadIdx.x, nblk = it.nblk, R = it.R;
@@ -131,12 +225,17 @@ __global__ void __launch_bounds__(kGpmBlockRows) k_gpm_pivot_step(const GpmItem*
   if (blockIdx.x == 0 && t == 0) { it.pivots[step] = p; it.m_eff[0] = step + 1; }
   const global_ptr<const double> L = as_global((const double*)it.L), pts = as_global(it.pts);
   for (int k = t; k < step; k += kGpmBlockRows) Lp[k] = L[(size_t)k * R + p];
+  if (kGeneral && it.general) gpm_stage_pivot(it, p / 3, pv);  // (uniform over the workgroup) the pivot's point, mirrors and weights
   __syncthreads();
   const int row = blockIdx.x * kGpmBlockRows + t;
   x = GpmBest{-INFINITY, INT_MAX, 0.0};
   if (row < R) {
     const int v = row / 3, c = row - 3 * v, vp = p / 3, cp = p - 3 * vp;
-    const double kv = gpm_kernel_value(it, pts[3 * v], pts[3 * v + 1], pts[3 * v + 2], c, pts[3 * vp], pts[3 * vp + 1], pts[3 * vp + 2], cp);
+    double kv;
+    if (kGeneral && it.general)  // (uniform over the workgroup)
+      kv = gpm_general_value(it, v, pts[3 * v], pts[3 * v + 1], pts[3 * v + 2], c, pv, cp);
+    else
+      kv = gpm_kernel_value(it, pts[3 * v], pts[3 * v + 1], pts[3 * v + 2], c, pts[3 * vp], pts[3 * vp + 1], pts[3 * vp + 2], cp);
     double s = 0.0;
     const global_ptr<const double> Lr = L + row;
 #pragma unroll 8
@@ -349,18 +448,50 @@ __global__ void __launch_bounds__(64) k_gpm_gemm(const GpmPiece* __restrict__ pi
     }
 }
 
+// Region weights (icp_region_weights_many; FaceMask.computeSmoothedRegions).  blockIdx = (block of 256 query points, item); a thread
+// owns one query point; the region's points pass through LDS 256 at a time.  A minimum does not depend on the order it is taken in.
+constexpr int kGpmRegionTile = 256;
+__global__ void __launch_bounds__(kGpmRegionTile) k_gpm_region_weights(const GpmRegion* __restrict__ items) {
+  __shared__ double sr[3 * kGpmRegionTile];
+  const GpmRegion& it = items[blockIdx.y];
+  if ((int)blockIdx.x * kGpmRegionTile >= it.n) return;  // (uniform)
+  const int t = threadIdx.x, i = blockIdx.x * kGpmRegionTile + t;
+  const bool ok = i < it.n;
+  const global_ptr<const double> pts = as_global(it.pts), reg = as_global(it.reg);
+  const int ic = ok ? i : it.n - 1;
+  const double x0 = pts[3 * ic], x1 = pts[3 * ic + 1], x2 = pts[3 * ic + 2];
+  double best = INFINITY;
+  for (int r0 = 0; r0 < it.n_reg; r0 += kGpmRegionTile) {
+    const int cnt = min(kGpmRegionTile, it.n_reg - r0);
+    __syncthreads();  // (the tile may still be read)
+    for (int k = t; k < 3 * cnt; k += kGpmRegionTile) sr[k] = reg[(size_t)3 * r0 + k];
+    __syncthreads();
+    for (int k = 0; k < cnt; ++k) {
+      const double dx = x0 - sr[3 * k], dy = x1 - sr[3 * k + 1], dz = x2 - sr[3 * k + 2];
+      best = fmin(best, (dx * dx + dy * dy) + dz * dz);
+    }
+  }
+  if (ok) it.w[i] = exp(-(best / it.s2));
+}
+
 }  // namespace
 
 // rows of a slab of the Gram sum: 1,024, or as many more (in steps of 1,024) as keep the slabs at kGpmMaxSlabs
 int gpm_slab_rows(int R) { return 1024 * std::max(1, cdiv(R, 1024 * kGpmMaxSlabs)); }
 
-void launch_gpm_init(hipStream_t st, int n_items, int nblk_max, const GpmItem* items) {
+void launch_gpm_init(hipStream_t st, int n_items, int nblk_max, const GpmItem* items, bool any_general) {
   if (n_items <= 0) return;
-  hipLaunchKernelGGL(k_gpm_init, dim3(nblk_max, n_items), dim3(kGpmBlockRows), 0, st, items);
+  if (any_general) hipLaunchKernelGGL(k_gpm_init<true>, dim3(nblk_max, n_items), dim3(kGpmBlockRows), 0, st, items);
+  else hipLaunchKernelGGL(k_gpm_init<false>, dim3(nblk_max, n_items), dim3(kGpmBlockRows), 0, st, items);
 }
-void launch_gpm_pivot_step(hipStream_t st, int n_items, int nblk_max, int step, const GpmItem* items) {
+void launch_gpm_pivot_step(hipStream_t st, int n_items, int nblk_max, int step, const GpmItem* items, bool any_general) {
   if (n_items <= 0) return;
-  hipLaunchKernelGGL(k_gpm_pivot_step, dim3(nblk_max, n_items), dim3(kGpmBlockRows), 0, st, items, step);
+  if (any_general) hipLaunchKernelGGL(k_gpm_pivot_step<true>, dim3(nblk_max, n_items), dim3(kGpmBlockRows), 0, st, items, step);
+  else hipLaunchKernelGGL(k_gpm_pivot_step<false>, dim3(nblk_max, n_items), dim3(kGpmBlockRows), 0, st, items, step);
+}
+void launch_gpm_region_weights(hipStream_t st, int n_items, int n_max, const GpmRegion* items) {
+  if (n_items <= 0 || n_max <= 0) return;
+  hipLaunchKernelGGL(k_gpm_region_weights, dim3(cdiv(n_max, kGpmRegionTile), n_items), dim3(kGpmRegionTile), 0, st, items);
 }
 void launch_gpm_gram(hipStream_t st, int n, int mp_max, int slabs_max, const GpmSpace* items) {
   if (n <= 0) return;

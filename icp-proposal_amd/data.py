@@ -84,26 +84,102 @@ class StatisticalMeshModel:
         return self.ref_points + self.mean_def + (q @ np.asarray(coeffs, dtype=np.float64)).reshape(-1, 3)
 
 
+def _general_fields(term):
+    """A, weights, mirror_gain and mirror_axis of a kernel term, as arrays and numbers"""
+    term.A = np.eye(3) if term.A is None else np.ascontiguousarray(term.A, dtype=np.float64)
+    if term.A.shape != (3, 3):
+        raise ValueError("A is a 3 x 3 matrix")
+    if term.weights is not None:
+        term.weights = np.ascontiguousarray(term.weights, dtype=np.float64)
+        if term.weights.ndim != 1:
+            raise ValueError("weights are one number per vertex")
+    term.mirror_gain = float(term.mirror_gain)
+    term.mirror_axis = int(term.mirror_axis)
+
+
 @dataclasses.dataclass
 class GaussianKernelTerm:
     """One term scale · exp(−‖x−y‖² / sigma²) · A of a matrix-valued kernel (gp_models): Scalismo's GaussianKernel(sigma) — no factor
-    ½ — times a symmetric positive semi-definite 3 × 3 matrix A (DiagonalKernel: the identity)."""
+    ½ — times a symmetric positive semi-definite 3 × 3 matrix A (DiagonalKernel: the identity).  Optionally a general term
+    (icp_gp_models_general_many): per-vertex `weights` [N] on both arguments, and the mirror symmetrisation
+    k(x, y) + mirror_gain · Ī · k(x, ȳ) about the plane coordinate `mirror_axis` = 0.  Without them the term is a plain one."""
     scale: float
     sigma: float
     A: np.ndarray = None
+    weights: np.ndarray = None
+    mirror_gain: float = 0.0
+    mirror_axis: int = 0
 
     def __post_init__(self):
         self.scale = float(self.scale)
         self.sigma = float(self.sigma)
-        self.A = np.eye(3) if self.A is None else np.ascontiguousarray(self.A, dtype=np.float64)
-        if self.A.shape != (3, 3):
-            raise ValueError("A is a 3 x 3 matrix")
+        _general_fields(self)
+
+    @property
+    def plain(self):
+        return self.weights is None and self.mirror_gain == 0.0
 
     def __call__(self, x, y):
-        """k(x, y) for points x [..., 3], y [..., 3] -> [..., 3, 3] (numpy; the long forms of the tests use it)"""
+        """scale · exp(−‖x−y‖²/σ²) · A for points x [..., 3], y [..., 3] -> [..., 3, 3]: the plain term, without weights and mirror
+        (numpy; the long forms of the tests use it)"""
         d = np.asarray(x, dtype=np.float64) - np.asarray(y, dtype=np.float64)
         d2 = (d[..., 0] * d[..., 0] + d[..., 1] * d[..., 1]) + d[..., 2] * d[..., 2]
         return (self.scale * np.exp(-(d2 / (self.sigma * self.sigma))))[..., None, None] * self.A
+
+
+@dataclasses.dataclass
+class BSplineKernelTerm:
+    """One term scale · w(x) · w(y) · A · (b(x, y) + mirror_gain · s · b(x, ȳ)) with b the cubic B-spline kernel on cells of 2^−level
+    (Scalismo's BSplineKernel(order 3, scale level); include/icp_proposal.h states the arithmetic): what apps/bfm/FaceKernel.scala is
+    made of.  `weights` [N] per vertex or None (1); ȳ is y with coordinate `mirror_axis` negated, s = −1 on that coordinate's row."""
+    scale: float
+    level: int
+    A: np.ndarray = None
+    weights: np.ndarray = None
+    mirror_gain: float = 0.0
+    mirror_axis: int = 0
+
+    def __post_init__(self):
+        self.scale = float(self.scale)
+        if int(self.level) != self.level:
+            raise ValueError("level is a whole number")
+        self.level = int(self.level)
+        _general_fields(self)
+
+    plain = False
+
+
+FACE_KERNEL_LEVELS = ((-6, 128.0), (-5, 64.0), (-4, 32.0), (-3, 10.0), (-2, 4.0))  # apps/bfm/FaceKernel.scala: (level, scale)
+FACE_KERNEL_MIRROR_GAIN = 0.7  # 0.7·symmetrize(k) + 0.3·k = k(x, y) + 0.7·Ī·k(x, ȳ)
+
+
+@dataclasses.dataclass
+class FaceMask:
+    """apps/bfm/FaceMask.scala as far as the face kernel needs it: one level per vertex; the region of a level is the vertices whose
+    value is >= that level (bfm/CreateGPModel.scala: 3 everywhere)."""
+    level_mask: np.ndarray
+
+    def __post_init__(self):
+        self.level_mask = np.ascontiguousarray(self.level_mask, dtype=np.int32)
+        if self.level_mask.ndim != 1:
+            raise ValueError("level_mask is one level per vertex")
+
+    def region(self, mesh, level):
+        """the points of the vertices whose level is >= `level`"""
+        pts = mesh.points if hasattr(mesh, "points") else np.asarray(mesh, dtype=np.float64)
+        if pts.shape[0] != self.level_mask.shape[0]:
+            raise ValueError("the mask has one level per vertex of the mesh")
+        reg = pts[self.level_mask >= level]
+        if reg.shape[0] == 0:
+            raise ValueError(f"no vertex of the mask reaches level {level}")
+        return reg
+
+    def smoothed_region_weights(self, mesh, level, stddev=40.0, device=0):
+        """FaceMask.computeSmoothedRegions: exp(−d²/stddev²) per vertex, d the distance to the nearest point of the level's region
+        (icp_region_weights_many)"""
+        from . import api
+        pts = mesh.points if hasattr(mesh, "points") else np.asarray(mesh, dtype=np.float64)
+        return api.region_weights(pts, self.region(mesh, level), stddev, device)
 
 
 def axis_of_main_variance(points) -> np.ndarray:

@@ -533,7 +533,8 @@ ICP_API int icp_posterior_models_many(int32_t n_items, icp_ctx *const *ctxs, con
 
 /* ---------------------------------------------------------------- Gaussian-process shape models from analytic kernels, many in one call
  * What apps/femur/CreateGPModel.scala and apps/bfm/CreateGPModel.scala do before anything is registered: a low-rank model of a
- * matrix-valued kernel on a reference mesh's own points.  The approximation is Scalismo's pivoted Cholesky factorisation
+ * matrix-valued kernel on a reference mesh's own points (the femur kernel through this entry point; the face kernel of apps/bfm, whose
+ * terms are B-splines with weights and a mirror, through icp_gp_models_general_many below).  The approximation is Scalismo's pivoted Cholesky factorisation
  * (approximateGPCholesky) followed by the eigen-decomposition of an m x m Gram matrix; deterministic, no sampler.
  *   k(x, y) = sum_t scale_t * exp(-|x - y|^2 / sigma_t^2) * A_t      (Scalismo's GaussianKernel(sigma): no factor 1/2)
  * with 1 .. ICP_GP_MODELS_MAX_TERMS terms per item; A_t (row-major 3 x 3) exactly symmetric, positive semi-definite (checked on the host
@@ -576,6 +577,61 @@ ICP_API int icp_gp_models_many(int32_t n_items, int device, const int32_t *n_poi
                                const int32_t *rank, const double *rel_tolerance, double *const *variance_out,
                                double *const *basis_out, int32_t *const *pivots_out, double *const *residual_out,
                                double *const *info_out, int32_t *status);
+
+/* ---------------------------------------------------------------- general kernel terms: B-spline, weighted and mirrored
+ * What apps/bfm/CreateGPModel.scala needs of icp_gp_models_many (FaceKernel.scala:26-108, FaceMask.scala:41-54): the project's own
+ * restatement; parity with Scalismo is unpinned.  For x, y on the mesh's own points, v(x) the vertex of x, term t, components c, c':
+ *   k_t(x, y)[c][c'] = scale_t * w_t(v(x)) * w_t(v(y)) * A_t[c][c'] * ( b_t(x, y) + gain_t * s_c * b_t(x, ym) )
+ * b_t, the scalar base kernel:
+ *   ICP_KERNEL_GAUSSIAN  exp(-|x - y|^2 / sigma^2), the squared distance as (dx*dx + dy*dy) + dz*dz: icp_gp_models_many's expression;
+ *   ICP_KERNEL_BSPLINE3  with c = 2^level:  b(x, y) = S(x0 c, y0 c) * S(x1 c, y1 c) * S(x2 c, y2 c),
+ *     S(u, v) = sum over k = ceil(max(u, v) - 2) .. floor(min(u, v) + 2), ascending, of beta(u - k) * beta(v - k)  (at most five k; an
+ *     empty range gives 0),  beta(t), a = |t|:  (2/3 - a*a) + ((0.5*a)*a)*a for a < 1;  ((1/6*(2 - a))*(2 - a))*(2 - a) for 1 <= a < 2;
+ *     0 otherwise.  (Scalismo's BSplineKernel(order 3, scale level); its triple loop agrees with the product of the three sums to
+ *     rounding.)  Lattice indices are exact doubles: the host requires |x_d| * 2^level < 2^31 for every coordinate of the item.
+ * w_t: per-vertex weights [N], >= 0, finite, at least one positive; NULL: 1.
+ * Mirror: ym = y with coordinate mirror_axis negated; gain_t = mirror_gain in [0, 1]; s_c = -1 for c == mirror_axis, else +1.  With
+ *   mirror_gain > 0, A_t must not couple the mirror axis to the others (A[a][b] == 0 for b != a).  DEVIATION from the reference, which
+ *   evaluates the weight of the mirrored argument AT the mirrored point (an unsymmetric kernel matrix unless the mask is mirror-
+ *   symmetric): here the weight of ym is the weight of y - exact for a mirror-symmetric mask, and K is symmetric positive semi-definite
+ *   for every 0 <= mirror_gain <= 1.  FaceKernel = k(x, y) + 0.7 * Im * k(x, ym): five ICP_KERNEL_BSPLINE3 terms (level, scale) =
+ *   (-6, 128), (-5, 64), (-4, 32), (-3, 10), (-2, 4), A = I, the level's weights, mirror_gain 0.7, mirror_axis 0.
+ * A term's value is ((scale * (w(v(x)) * w(v(y)))) * (b(x, y) + (gain * s_c) * b(x, ym))) * A[c][c'], the terms summed in order; the
+ * diagonal d[3v + c] is the same expression at y = x (no longer constant over the mesh).  A term with kind 0, no weights and gain 0
+ * (a plain term) has icp_gp_models_many's bits, and an item whose every term is plain runs icp_gp_models_many's code: the two entry
+ * points reach one implementation.  The pivot rule, the stopping rules, the decomposition, the outputs and the limits are
+ * icp_gp_models_many's.  Per item, checked before the device is touched (status[b] = ICP_ERR_INVALID_ARG, nothing written): all of
+ * icp_gp_models_many's checks; struct_size; kind; for the B-spline -32 <= level <= 32 and the lattice range; 0 <= mirror_gain <= 1;
+ * mirror_axis in {0, 1, 2}; the decoupling of A when mirror_gain > 0; the weights.
+ * Decided on the device: with mirror_gain = 1, or where the weights vanish, rows of K are zero and trace(K) may be 0: an item whose
+ * pivot loop leaves NO column gets status[b] = ICP_ERR_NOT_FINITE, NaN in variance_out, basis_out and residual_out, pivots -1 and
+ * info_out = {0, 0, 0, 0}; the other items complete (icp_gp_models_many cannot meet the case: its diagonal is positive).
+ *
+ * icp_region_weights_many: FaceMask.computeSmoothedRegions, many in one call.  Item b: weights_out[b][i] = exp(-(d2 / (stddev *
+ * stddev))), d2 the smallest (dx*dx + dy*dy) + dz*dz from point i of points[b] [3 * n_points] to the n_region[b] >= 1 points of
+ * region_points[b]; 1.0 exactly at a region point.  stddev[b] > 0 (40 in the reference); everything finite.  One launch for the
+ * whole call (a thread per point, the region tiled through LDS, f64); an item's bits depend on the item alone.  Statuses as above. */
+#define ICP_KERNEL_GAUSSIAN 0
+#define ICP_KERNEL_BSPLINE3 1
+typedef struct {
+  int32_t struct_size;      /* sizeof(icp_kernel_term_general) */
+  int32_t kind;             /* ICP_KERNEL_GAUSSIAN 0, ICP_KERNEL_BSPLINE3 1 */
+  double scale;             /* > 0, finite */
+  double sigma;             /* Gaussian: > 0, finite; else ignored */
+  int32_t level;            /* B-spline: 2^level cells per unit, [-32, 32]; else ignored */
+  int32_t mirror_axis;      /* 0, 1 or 2 */
+  double mirror_gain;       /* [0, 1] */
+  double A[9];
+  const double *weights;    /* [N] or NULL */
+} icp_kernel_term_general;
+ICP_API int icp_gp_models_general_many(int32_t n_items, int device, const int32_t *n_points, const double *const *points,
+                                       const int32_t *n_terms, const icp_kernel_term_general *const *terms, const int32_t *n_pivots,
+                                       const int32_t *rank, const double *rel_tolerance, double *const *variance_out,
+                                       double *const *basis_out, int32_t *const *pivots_out, double *const *residual_out,
+                                       double *const *info_out, int32_t *status);
+ICP_API int icp_region_weights_many(int32_t n_items, int device, const int32_t *n_points, const double *const *points,
+                                    const int32_t *n_region, const double *const *region_points, const double *stddev,
+                                    double *const *weights_out, int32_t *status);
 
 /* ---------------------------------------------------------------- the per-method entry points as ONE submission per step (round 6)
  * The drop-in contract is "Scalismo's chain, unchanged": MetropolisHastings.next (constructed at
