@@ -6,7 +6,7 @@ The directory name carries a hyphen (it mirrors the reference repository's name)
 from . import data  # noqa: F401
 from . import _native  # noqa: F401
 from .api import *  # noqa: F401,F403
-from .api import (BatchedStepTicket, expect_contexts, chain_eval_step, chain_step, chain_step_batched, chain_step_prelaunch, initial_parameters, posterior_variability,
+from .api import (BatchedStepTicket, expect_contexts, chain_eval_step, chain_step, chain_step_batched, chain_step_prelaunch, chain_step_prelaunch2, initial_parameters, posterior_variability,
                   posterior_variability_maps, transformed_meshes, model_coefficients, posterior_models, gp_models, gp_model, region_weights, face_kernel,
                   evaluate_reconstruction_to_ground_truth, registration_metrics, dice_coefficient, log_values, registration_maps, distance_summaries)  # noqa: F401
 from . import sampling  # noqa: F401

@@ -108,6 +108,9 @@ SIGNATURES = {
     "icp_ctx_profile_search_counters": (C.c_int, [C.c_void_p, C.c_int32]),
     "icp_ctx_set_idle_hook": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p]),
     "icp_chain_step_prelaunch": (C.c_int, [C.c_void_p, C.c_int32, C.c_void_p, C.c_int32, C.c_void_p, C.c_void_p]),
+    "icp_chain_step_prelaunch2": (C.c_int, [C.c_void_p, C.c_int32, C.c_void_p, C.c_int32, C.c_void_p, C.c_void_p, C.c_int32, C.c_void_p,
+                                            C.POINTER(C.c_int32)]),
+    "icp_ctx_twin_stats": (C.c_int, [C.c_void_p, C.POINTER(C.c_int64)]),
     "icp_ctx_profile_stop": (C.c_int, [C.c_void_p, C.POINTER(KernelStat), C.c_int32, C.POINTER(C.c_int32)]),
     "icp_chain_eval_step": (C.c_int, [C.c_void_p, C.c_int32, C.POINTER(C.c_void_p), c_double_p, c_double_p, c_double_p,
                                       c_double_p, c_double_p]),
@@ -202,6 +205,13 @@ def step_paths(ctx_handle=None) -> dict:
     out = (C.c_int64 * 4)()
     check(lib().icp_ctx_step_paths(ctx_handle, out), "icp_ctx_step_paths")
     return {"merged": int(out[0]), "wide": int(out[1]), "per_stage": int(out[2]), "device_loop": int(out[3])}
+
+
+def twin_stats(ctx_handle) -> dict:
+    """icp_ctx_twin_stats: twin passes issued, second-lane results used, second-lane results dropped (icp_chain_step_prelaunch2)."""
+    out = (C.c_int64 * 3)()
+    check(lib().icp_ctx_twin_stats(ctx_handle, out), "icp_ctx_twin_stats")
+    return {"passes": int(out[0]), "lane1_used": int(out[1]), "lane1_dropped": int(out[2])}
 
 
 def runtime_stats(ctx_handle=None) -> dict:

@@ -178,6 +178,10 @@ class IcpContext:
         """How many chain steps of this context took which path (icp_ctx_step_paths)."""
         return nat.step_paths(self.h)
 
+    def twin_stats(self) -> dict:
+        """Twin passes issued, second-lane results used and dropped (icp_ctx_twin_stats)."""
+        return nat.twin_stats(self.h)
+
     def profile_start(self, max_launches: int = 200000, count_searches: bool = False):
         """count_searches: also count the tests the searches execute (rows "count.*" of profile_stop; slows the filter launches
         down — for a short leg of its own, not for timing)."""
@@ -577,6 +581,20 @@ def chain_step_prelaunch(evaluator: _Evaluator, proposals, theta_cur, generator:
     arr = (C.c_void_p * n)(*[p.h for p in proposals])
     key = np.ascontiguousarray(z, dtype=np.float64) if generator >= 0 else _theta(theta_prop)
     nat.check(nat.lib().icp_chain_step_prelaunch(evaluator.h, n, arr, int(generator), _d(a), _d(key)), "icp_chain_step_prelaunch")
+
+
+def chain_step_prelaunch2(evaluator: _Evaluator, proposals, theta_cur, generator: int, key, generator2: int, key2) -> int:
+    """icp_chain_step_prelaunch2: the next step and the one after it, both from theta_cur, as the two lanes of one set of launches
+    (key / key2: z where the generator is >= 0, the proposed state otherwise).  -> lanes issued (0, 1 or 2)."""
+    n = len(proposals)
+    a = _theta(theta_cur)
+    arr = (C.c_void_p * n)(*[p.h for p in proposals])
+    k1 = np.ascontiguousarray(key, dtype=np.float64)
+    k2 = np.ascontiguousarray(key2, dtype=np.float64)
+    lanes = C.c_int32(0)
+    nat.check(nat.lib().icp_chain_step_prelaunch2(evaluator.h, n, arr, int(generator), _d(a), _d(k1), int(generator2), _d(k2), C.byref(lanes)),
+              "icp_chain_step_prelaunch2")
+    return int(lanes.value)
 
 
 def direction_schedule(n_fits: int, n_recursions: int, seed) -> np.ndarray:

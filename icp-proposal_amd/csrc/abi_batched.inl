@@ -70,7 +70,7 @@ int icp_chain_step_batched_issue(int32_t n_chains, icp_evaluator* const* evaluat
       it.lk = std::unique_lock<std::recursive_mutex>(c.mu);
       if (c.batch_busy) fail(ICP_ERR_BUSY, "a chain's context already belongs to a batch in flight");
       if (it.e->front.valid || c.front_stream_used) {  // half steps launched ahead by the pipelined entry points: drained
-        if (it.e->front.valid) release_front(it.e->front);
+        release_fronts(it.e);
         c.bind();
         HIP_OK(hipStreamSynchronize(c.stream));
         c.front_stream.sync();

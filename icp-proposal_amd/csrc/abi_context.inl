@@ -272,14 +272,16 @@ int icp_ctx_create_keyed(const icp_model_desc* model, const icp_mesh_desc* targe
     pinned_alloc((void**)&ctx->h_stage, sizeof(double) * ctx->stage_cap);
     ctx->d_stage.alloc(ctx->stage_cap);
     const size_t res_cap = std::max<size_t>(2048, 3 * (size_t)N + 64);
-    pinned_alloc((void**)&ctx->h_out, sizeof(double) * (icp_ctx::kStatusDoubles + res_cap));
+    pinned_alloc((void**)&ctx->h_out, sizeof(double) * (icp_ctx::kStatusDoubles + res_cap + icp_ctx::kTwinDoubles));
+    ctx->h_twin = ctx->h_out + icp_ctx::kStatusDoubles + res_cap;
+    ctx->h_twin_status = (int*)(ctx->h_twin + icp_ctx::kTwinDoubles - 8);
     ctx->d_out.alloc(icp_ctx::kStatusDoubles + res_cap);
     ctx->h_status = (int*)ctx->h_out;
     ctx->h_res = ctx->h_out + icp_ctx::kStatusDoubles;
     ctx->d_status.p = (int*)ctx->d_out.p; ctx->d_status.n = 2 * icp_ctx::kStatusDoubles; ctx->d_status.owned = false;
     ctx->d_res.p = ctx->d_out.p + icp_ctx::kStatusDoubles; ctx->d_res.n = res_cap; ctx->d_res.owned = false;
     pinned_alloc((void**)&ctx->h_flag, sizeof(int) * 16);
-    ctx->h_flag[0] = 0;
+    ctx->h_flag[0] = ctx->h_flag[1] = 0;
     ctx->d_done.alloc(4);
     ctx->d_done.fill_bytes(0);
     ctx->d_wait_ticks.alloc(2);
@@ -404,7 +406,7 @@ int icp_ctx_set_target(icp_ctx* ctx, const icp_mesh_desc* target) {
   });
 }
 
-namespace { void release_front(StepFront& F); }
+namespace { void release_front(StepFront& F); void release_fronts(icp_evaluator* e); }
 
 int icp_ctx_set_rotation(icp_ctx* ctx, const double* angles, const double* R) {
   return guard([&] {
@@ -426,7 +428,7 @@ int icp_ctx_set_rotation(icp_ctx* ctx, const double* angles, const double* R) {
         for (int i = 0; i < kPosteriorMemo; ++i) any = any || (p->memo[i].valid && same(p->memo[i].theta));
       for (icp_evaluator* ev : ctx->evaluators) {
         for (auto& m : ev->memo) any = any || (m.valid && same(m.theta));
-        any = any || (ev->front.valid && same(ev->front.theta_cur));
+        any = any || (ev->front.valid && same(ev->front.theta_cur)) || (ev->twin.valid && same(ev->twin.F.theta_cur));
       }
       if (!any) return;
       if (ctx->batch_busy) throw IcpError{ICP_ERR_BUSY, "the context belongs to a batch in flight"};
@@ -435,7 +437,7 @@ int icp_ctx_set_rotation(icp_ctx* ctx, const double* angles, const double* R) {
       ctx->front_stream.sync();
       sync_eigen(*ctx);
       for (icp_evaluator* ev : ctx->evaluators) {
-        if (ev->front.valid) release_front(ev->front);
+        release_fronts(ev);
         for (auto& m : ev->memo)
           if (m.valid && same(m.theta)) m.valid = false;
         ev->last_prop.clear();

@@ -52,7 +52,7 @@ void merged_loop_claim(const LoopRun& a, std::vector<MergedLoopChain>& chains) {
     if (a.mix->w_pose > 0.0)
       require(c.rotations_mismatched == 0, "pose walks on the device: a caller-supplied rotation matrix disagreed with the library's Rz·Ry·Rx (icp_ctx_rotation_convention)");
     Bound _b(&c);
-    if (ch.e->front.valid) release_front(ch.e->front);
+    release_fronts(ch.e);
     for (int i = 0; i < n_props; ++i) {
       icp_proposal* p = ch.props[i];
       p->resolve_speculation(a.theta[b]);

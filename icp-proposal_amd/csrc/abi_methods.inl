@@ -114,6 +114,7 @@ int icp_proposal_create(icp_ctx* ctx, const icp_proposal_params* params, icp_pro
       p->hint_nn.alloc(std::max(p->K, 1));
       p->hint_nn.fill_bytes(0xFF);
       p->nn_id.alloc(std::max(p->K, 1));
+      p->nn_id2.alloc(std::max(p->K, 1));
     } else {
       require(params->n_model_ids >= 0 && params->n_model_ids <= ctx->N, "n_model_ids out of range");
       p->K = params->n_model_ids;
@@ -146,7 +147,7 @@ int icp_proposal_create(icp_ctx* ctx, const icp_proposal_params* params, icp_pro
   return rc;
 }
 
-namespace { void release_front(StepFront& F); }
+namespace { void release_front(StepFront& F); void release_fronts(icp_evaluator* e); bool fronts_use(const icp_evaluator* e, const icp_proposal* p); }
 
 void icp_proposal_destroy(icp_proposal* p) {
   if (!p) return;
@@ -159,7 +160,7 @@ void icp_proposal_destroy(icp_proposal* p) {
     DeviceQuiesce _q;
     if (p->bound_eval) unbind_chain(p->bound_eval);
     for (icp_evaluator* ev : p->ctx->evaluators)  // a half step launched ahead with this proposal holds entries of it
-      if (ev->front.valid && (ev->front.props[0] == p || ev->front.props[1] == p)) release_front(ev->front);
+      if (fronts_use(ev, p)) release_fronts(ev);
     if (g_host_timing.on && eigen_speculation_supported(p->ctx->r)) eigen_debug_dump(p->work.p, p->ctx->r);
     if (p->h_cancel) pinned_free(p->h_cancel);
     if (p->h_eig) pinned_free(p->h_eig);
@@ -184,7 +185,7 @@ int icp_proposal_set_sampler(icp_proposal* p, int32_t sampler) {
     HIP_OK(hipStreamSynchronize(c.stream));
     sync_eigen(c);
     for (icp_evaluator* ev : c.evaluators)
-      if (ev->front.valid && (ev->front.props[0] == p || ev->front.props[1] == p)) release_front(ev->front);
+      if (fronts_use(ev, p)) release_fronts(ev);
     // Ranks above 64 have no decomposition of the root kind: there the posterior's own factorisation hands the factor out
     // (PosteriorFactorIO::Lout / Sout, written only when the posterior is computed), and the eigen route has no `root` form.  A
     // memoised posterior would be a memo hit that never rewrites V / S the new way — the sampler would draw from one kind of
@@ -352,6 +353,7 @@ int icp_evaluator_create(icp_ctx* ctx, const icp_evaluator_params* params, icp_e
     HIP_OK(hipStreamSynchronize(ctx->stream));
     ev->t2m_tri.alloc(Ka); ev->t2m_nnv.alloc(Ka);
     ev->t2m_cp.alloc(3 * Ka); ev->t2m_d2.alloc(Ka);
+    ev->t2m_tri2.alloc(Ka); ev->t2m_cp2.alloc(3 * Ka); ev->t2m_d2_2.alloc(Ka);
     ctx->evaluators.push_back(ev);
     *out = ev;
   });
@@ -367,7 +369,7 @@ void icp_evaluator_destroy(icp_evaluator* e) {
   DeviceQuiesce _q;
   unbind_chain(e);
   // a pre-launched half step holds a state slot of the context and memo entries of its proposals
-  if (e->front.valid) release_front(e->front);
+  release_fronts(e);
   auto& evs = e->ctx->evaluators;
   evs.erase(std::remove(evs.begin(), evs.end(), e), evs.end());
   delete e;

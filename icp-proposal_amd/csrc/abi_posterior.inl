@@ -45,15 +45,17 @@ struct icp_proposal {
   DBuf<double> target_pts;
   DBuf<int> hint_nn;      // TargetSampling: last nearest model vertex of each target point
   DBuf<int> nn_id;
+  DBuf<int> nn_id2;       // … of lane 1 of a twin pass
   DBuf<double> work;      // r*r scratch of the eigen / direct-tail kernels
   DBuf<double> xrows;     // (wide step, folded regression) the correspondences' operand rows: K · 4 · 16·⌈(r + 1)/16⌉ values (StepRegressionArgs::X)
   DBuf<double> Mpart;     // split-K partial normal matrices of the regression kernel, two halves: the merged step alternates
                           // between them so that a speculative decomposition can still read the previous step's
   size_t mpart_half_doubles = 0;
   int mpart_half = 0;
-  static constexpr int kMpartRing = 4;  // (a speculative decomposition reads the partials of the step that started it: with four
-                                        // buffers used in turn the writer of a buffer practically never finds its reader still at work)
-  PosteriorEntry* mpart_reader[kMpartRing] = {nullptr, nullptr, nullptr, nullptr};  // the entry whose decomposition reads the buffer
+  static constexpr int kMpartRing = 8;  // (a speculative decomposition reads the partials of the step that started it: with eight
+                                        // buffers used in turn — a twin pass takes two — the writer of a buffer practically never finds
+                                        // its reader still at work: three fronts lie between them, as with four buffers and one lane)
+  PosteriorEntry* mpart_reader[kMpartRing] = {};  // the entry whose decomposition reads the buffer
   double* mpart_for_write(int half, hipStream_t st);  // `st` (where the writer runs) waits for that reader first, if it is still at work
   DBuf<double> fscratch;  // (r+1)·r + 8 factorisation scratch (ranks too large for LDS)
   const double* warm_ptr = nullptr;  // eigenvectors of the most recent posterior (inside its memo entry): warm start of the next
@@ -77,6 +79,7 @@ struct icp_proposal {
   void speculate_eigen(PosteriorEntry& e, const PosteriorEntry& cur, int splits, int half /* of Mpart: the step's partials */,
                        const int* ready, int ready_seq, EigenSpec* spec_out, EigenRequest* rq_out);
   void resolve_speculation(const double* theta_cur);
+  void withdraw_speculation();
   DBuf<int> status;       // 3 ints per memo entry: {chol(M), chol(G+σ²M), eigen}
   // (pinned: the copy of `status` into it is a true asynchronous copy — into a pageable vector it was a synchronising one, 20-30 µs
   // per step of the per-stage paths)
@@ -152,20 +155,41 @@ struct StepFront {
   double* mpart[2] = {nullptr, nullptr};
   int mpart_half[2] = {0, 0};
   int Ksurf = 0;
+  // Lane of a twin pass (icp_chain_step_prelaunch2: the chain's next two proposals from one state, in one set of launches).  Lane 1
+  // has a state slot, memo entries, Mpart ring slots, query scratch sets and pinned result areas of its own; it reads the search
+  // hints and leaves them as they are.  mate: lane 1 of the front this one leads (in the evaluator), released with it.
+  int lane = 0;
+  StepFront* mate = nullptr;
+  const double* h_coeffs = nullptr;  // pinned: the proposed coefficients (launch 1) …
+  double* h_reduce = nullptr;        // … and launch 4's likelihood reduction, per lane and parity
 };
 constexpr int kCoeffArea = 512;  // doubles per half of that area (>= kMaxRank)
 constexpr int kReduceArea = 16 + 2 * kCoeffArea;  // pinned result of launch 4's likelihood reduction: 8 doubles per parity
+static_assert(icp_ctx::kTwinDoubles == kReduceArea + 16 + 8, "lane 1's pinned areas have the layout of lane 0's");
+// lane 1 of a twin pass whose lane 0 has been consumed: its finish launch is on the device (or done), its results are lane 1's
+// pinned areas; the next icp_chain_step takes them if it is the step they were made for, or drops them
+struct TwinPending {
+  bool valid = false;
+  StepFront F;
+  StepFinishArgs f{};
+  int seq = 0;
+};
 }  // namespace
 
 struct icp_evaluator {
   icp_ctx* ctx = nullptr;
   icp_evaluator_params prm{};
   StepFront front;  // pre-launched first half of the next step, if any
+  StepFront front2; // … and of the step after it, where the front is a twin pass (front.mate)
+  TwinPending twin; // lane 1 of the twin pass being finished
+  DBuf<int> t2m_tri2;            // lane 1's results of the target -> model search
+  DBuf<double> t2m_cp2, t2m_d2_2;
   int front_parity = 0;
   // Acceptance estimate of the chain stepped through this evaluator (icp_chain_step): the decomposition of the PROPOSED
   // state is started speculatively unless next to nothing is being accepted.
   std::vector<double> last_prop;  // the state the previous merged step proposed
   double acc_ema = 0.5;
+  bool acc_counted = false;  // the step being repeated (a timed-out first launch) has been counted into acc_ema already
   DBuf<double> target_pts;
   // target-side queries against the CURRENT model surface
   int Kt = 0;              // number of target-side query points (decimated target, or all target vertices for Hausdorff)
@@ -591,6 +615,26 @@ void icp_proposal::resolve_speculation(const double* theta_cur) {
   __atomic_store_n(h_cancel + (spec_seq & 15), spec_seq, __ATOMIC_RELEASE);  // rejected (or the entry was recycled meanwhile)
   e.eig_valid = false;
   e.eig_checked = false;
+}
+
+// The step that started (or planned) the decomposition of its proposed state is being repeated from scratch — its first launch
+// timed out on its word, nothing of it has been recorded.  The launch is cancelled, and the repeated step's decomposition takes
+// the same place in the cycle of 128, so that every 128th cold start stays on the step it falls on in an undisturbed chain.  A
+// planned place was never launched and is given back; a launched one is not given out again (a dropped launch still raises its
+// entry's completion word to its number): the count skips to the same place of the next cycle.
+void icp_proposal::withdraw_speculation() {
+  if (plan_entry) {
+    plan_entry->planned = false;
+    plan_entry = nullptr;
+    --eig_seq;
+  }
+  if (!spec_entry) return;
+  PosteriorEntry& e = *spec_entry;
+  spec_entry = nullptr;
+  __atomic_store_n(h_cancel + (spec_seq & 15), spec_seq, __ATOMIC_RELEASE);
+  e.eig_valid = false;
+  e.eig_checked = false;
+  eig_seq += 127;
 }
 
 // must be called after a synchronising copy of `status` into h_status

@@ -16,10 +16,38 @@ void release_front(StepFront& F);
 void drop_front(icp_evaluator* e) {
   if (!e->front.valid) return;
   const int parity = e->front.parity;
+  if (e->front.mate) ++e->ctx->twin_stats[2];  // (lane 1 goes with it)
   release_front(e->front);
   e->front_parity = parity ^ 1;
 }
+// Lane 1 of the twin pass whose lane 0 has been consumed, when the caller's next step is not the one it was made for (lane 0 was
+// accepted).  Its part of the finish launch may still be running — it writes the entries' M and alpha, reads their coefficients —
+// so the host sees its flag first (it trails lane 0's by a few µs at most); then the slots go back.
+void drop_twin(icp_evaluator* e) {
+  if (!e->twin.valid) return;
+  icp_ctx& c = *e->ctx;
+  volatile int* flag = c.h_flag + 1;
+  const auto t_start = std::chrono::steady_clock::now();
+  long spins = 0;
+  while (*flag != e->twin.seq) {
+    if ((++spins & 0xFFFF) == 0 && std::chrono::steady_clock::now() - t_start > std::chrono::seconds(2)) break;
+  }
+  if (*flag != e->twin.seq) (void)hipStreamSynchronize(e->twin.F.stream);
+  release_front(e->twin.F);
+  e->twin = TwinPending{};
+  ++c.twin_stats[2];
+}
+// everything an evaluator holds of steps launched ahead
+void release_fronts(icp_evaluator* e) {
+  drop_twin(e);
+  if (e->front.valid) release_front(e->front);
+}
+bool fronts_use(const icp_evaluator* e, const icp_proposal* p) {
+  return (e->front.valid && (e->front.props[0] == p || e->front.props[1] == p)) ||
+         (e->twin.valid && (e->twin.F.props[0] == p || e->twin.F.props[1] == p));
+}
 void release_front(StepFront& F) {
+  if (F.mate) { StepFront* m = F.mate; F.mate = nullptr; if (m->valid || m->s) release_front(*m); }
   if (F.s) F.s->reserved = false;
   for (int i = 0; i < F.n_props; ++i)
     if (F.ep[i]) F.ep[i]->reserved = false;
@@ -116,8 +144,10 @@ void front_launches(icp_evaluator* e, int n_props, icp_proposal* const* props, i
 // launches 1-3 of the step (theta_cur --generator/key--> proposal); `key` = z or the proposed state (see StepFront)
 // (batched: the launches are being captured for icp_chain_step_batched — one stream, nothing to wait for on the device
 // but the decomposition)
+// F2 (with generator2 / key2): the step after it as well, from the same theta_cur, as lane 1 of a twin pass — ONE set of launches
 void enqueue_front(icp_evaluator* e, int n_props, icp_proposal* const* props, int generator, const double* theta_cur,
-                   const double* key, StepFront& F, bool batched = false) {
+                   const double* key, StepFront& F, bool batched = false, StepFront* F2 = nullptr, int generator2 = -1,
+                   const double* key2 = nullptr) {
   icp_ctx& c = *e->ctx;
   const int r = c.r;
   F = StepFront{};
@@ -126,9 +156,18 @@ void enqueue_front(icp_evaluator* e, int n_props, icp_proposal* const* props, in
   F.theta_cur.assign(theta_cur, theta_cur + 10 + r);
   F.key.assign(key, key + (generator >= 0 ? r : 10 + r));
   F.parity = (e->front_parity ^= 1);
+  F.h_coeffs = c.h_res + 16 + F.parity * kCoeffArea;
+  F.h_reduce = c.h_res + kReduceArea + F.parity * 8;  // (its own half: the host may still be reading the previous step's)
+  if (F2) {
+    *F2 = F;
+    F2->lane = 1; F2->generator = generator2;
+    F2->key.assign(key2, key2 + (generator2 >= 0 ? r : 10 + r));
+    F2->h_coeffs = c.h_twin + 16 + F.parity * kCoeffArea;
+    F2->h_reduce = c.h_twin + kReduceArea + F.parity * 8;
+    F.mate = F2;  // (from here on lane 1 is released with lane 0)
+  }
   // ---- cached side: posterior of the current state for every proposal (+ its KL basis for the generating one)
   PosteriorEntry** ec = F.ec;
-  PosteriorEntry** ep = F.ep;
   bool missing = false;
   for (int i = 0; i < n_props; ++i) missing = missing || !props[i]->find_entry(theta_cur);
   if (missing && c.front_stream_used) {  // the posteriors are computed on `stream` with the scratch a step in flight may still use
@@ -149,22 +188,41 @@ void enqueue_front(icp_evaluator* e, int n_props, icp_proposal* const* props, in
   }
   c.stream_used_elsewhere = false;
   start_decompositions(c, n_props, props, ec, m_in_flight);
-  bool eigen_first_use = false;
-  if (generator >= 0) {
+  if (F2) { F2->stream = F.stream; for (int i = 0; i < n_props; ++i) F2->ec[i] = ec[i]; }
+  // (per lane; two lanes that draw from the same basis: the first one fetches its status)
+  for (StepFront* L : {&F, F2}) {
+    if (!L || L->generator < 0) continue;
+    PosteriorEntry* g = ec[L->generator];
     // (await_eigen on the front's stream: through the decomposition's own completion word when it has one — see launch 1)
-    if (ec[generator]->done_value == 0 && ec[generator]->eigen_event()) HIP_OK(hipStreamWaitEvent(F.stream, ec[generator]->eigen_event(), 0));
-    eigen_first_use = !ec[generator]->eig_checked;  // (possibly of an earlier prefetch or speculation): fetch its status
-    ec[generator]->eig_checked = true;
+    if (g->done_value == 0 && g->eigen_event()) HIP_OK(hipStreamWaitEvent(F.stream, g->eigen_event(), 0));
+    L->eigen_first_use = !g->eig_checked;  // (possibly of an earlier prefetch or speculation): fetch its status
+    g->eig_checked = true;
   }
-  F.eigen_first_use = eigen_first_use;
 
-  // ---- new side: one state slot, one memo entry per proposal
-  StateSlot& s = c.fresh_state();
-  s.reserved = true;
-  F.s = &s;
-  s.pose = c.pose_of(generator >= 0 ? theta_cur : key);
-  for (int i = 0; i < n_props; ++i) { ep[i] = &props[i]->fresh_entry(); ep[i]->reserved = true; }
-  front_launches(e, n_props, props, generator, key, F, batched, two_streams);
+  // ---- new side: one state slot, one memo entry per proposal (and lane)
+  for (StepFront* L : {&F, F2}) {
+    if (!L) continue;
+    StateSlot& s = c.fresh_state();
+    s.reserved = true;
+    L->s = &s;
+    s.pose = c.pose_of(L->generator >= 0 ? theta_cur : L->key.data());
+    for (int i = 0; i < n_props; ++i) { L->ep[i] = &props[i]->fresh_entry(); L->ep[i]->reserved = true; }
+  }
+  if (!F2) {
+    front_launches(e, n_props, props, generator, key, F, batched, two_streams);
+  } else {
+    // both lanes' launches are captured (arguments finalised, grids known) and issued as one set
+    StepCapture caps[2];
+    struct CaptureGuard { ~CaptureGuard() { step_capture(nullptr); } } capture_guard;
+    step_capture(&caps[0]);
+    front_launches(e, n_props, props, generator, key, F, batched, two_streams);
+    step_capture(&caps[1]);
+    front_launches(e, n_props, props, generator2, key2, *F2, batched, two_streams);
+    step_capture(nullptr);
+    launch_step_twin_front(F.stream, caps[0], caps[1]);
+    F2->valid = true;
+    ++c.twin_stats[0];
+  }
   F.valid = true;
 }
 
@@ -190,21 +248,30 @@ void front_launches(icp_evaluator* e, int n_props, icp_proposal* const* props, i
   const int Ksurf = std::max(ev_m2t ? evp.n_model_ids : 0, pm ? pm->K : 0);
   F.Ksurf = Ksurf;
   require(Ksurf <= c.N, "model id count exceeds the number of model points");
-  QueryBuffers qs = c.query_scratch(Ksurf, c.target.T);
+  if (!F.h_coeffs) {  // (a front made by the on-device loop: lane 0's areas)
+    F.h_coeffs = c.h_res + 16 + F.parity * kCoeffArea;
+    F.h_reduce = c.h_res + kReduceArea + F.parity * 8;
+  }
+  // lane 1 of a twin pass: scratch sets and result buffers of its own; the hints are read and left as they are
+  const int lane = F.lane, sw = lane ? 7 : 0;
+  QueryBuffers qs = c.query_scratch(Ksurf, c.target.T, sw);
   QueryBuffers qv{};
-  if (pt) qv = c.query_scratch(pt->K, c.N, 1);
+  if (pt) qv = c.query_scratch(pt->K, c.N, sw + 1);
 
   SurfaceTask st_surf = make_surface_task(c.target.T, c.target.verts.p, c.target.tris.p, c.target.spheres.p, Ksurf, s.x.p,
                                           c.hint_surf.p, qs, s.surf_cp.p, s.surf_d2.p, s.surf_tri.p);
   VertexTask st_vert{};
-  if (pt) st_vert = make_vertex_task(c.N, s.x.p, pt->K, pt->target_pts.p, pt->hint_nn.p, qv, nullptr, pt->nn_id.p);
+  if (pt) st_vert = make_vertex_task(c.N, s.x.p, pt->K, pt->target_pts.p, pt->hint_nn.p, qv, nullptr, lane ? pt->nn_id2.p : pt->nn_id.p);
+  st_surf.keep_hint = st_vert.keep_hint = lane;
   st_vert.thr2 = nullptr;  // bounds are computed by the filter launch itself (see vertex_filter)
   // the evaluator's reverse direction (IndependentPointDistanceEvaluator.scala:49-54, Collective…Evaluator.scala:55-64): its
   // decimated-target points against the surface of the NEW instance — spheres and bounds are taken by the filter launch itself
   SurfaceTask st_t2m{};
   if (ev_t2m) {
-    QueryBuffers qt = c.query_scratch(e->Kt, c.T, 2);
-    st_t2m = make_surface_task(c.T, s.x.p, c.tris.p, nullptr, e->Kt, e->d_tpts, e->hint_tri.p, qt, e->t2m_cp.p, e->t2m_d2.p, e->t2m_tri.p);
+    QueryBuffers qt = c.query_scratch(e->Kt, c.T, sw + 2);
+    st_t2m = make_surface_task(c.T, s.x.p, c.tris.p, nullptr, e->Kt, e->d_tpts, e->hint_tri.p, qt, lane ? e->t2m_cp2.p : e->t2m_cp.p,
+                               lane ? e->t2m_d2_2.p : e->t2m_d2.p, lane ? e->t2m_tri2.p : e->t2m_tri.p);
+    st_t2m.keep_hint = lane;
     st_t2m.order = c.tri_order.p;
     st_t2m.thrA = nullptr;
   }
@@ -230,7 +297,7 @@ void front_launches(icp_evaluator* e, int n_props, icp_proposal* const* props, i
   b.n_out = 0;
   b.out[b.n_out++] = s.coeffs.p;
   for (int i = 0; i < n_props; ++i) b.out[b.n_out++] = ep[i]->coeffs.p;
-  b.out[b.n_out++] = c.h_res + 16 + F.parity * kCoeffArea;
+  b.out[b.n_out++] = const_cast<double*>(F.h_coeffs);
   b.x = s.x.p;
   b.has_surf = 1; b.surf = st_surf;
   b.has_vert = pt ? 1 : 0; b.vert = st_vert;
@@ -308,11 +375,11 @@ void front_launches(icp_evaluator* e, int n_props, icp_proposal* const* props, i
   if (n_props == 1) g.ustart[2] = g.ustart[1];
   g.reduce_kind = evp.kind == ICP_EVAL_INDEPENDENT_POINT_DISTANCE ? 1 : 2;
   g.Kred = ev_m2t ? evp.n_model_ids : 0; g.d2 = s.surf_d2.p; g.mean = evp.gauss_mean; g.sigma = evp.gauss_sigma;
-  g.Kred2 = ev_t2m ? e->Kt : 0; g.d2b = e->t2m_d2.p;
-  g.red_out = c.h_res + kReduceArea + F.parity * 8;  // (its own half: the host may still be reading the previous step's)
+  g.Kred2 = ev_t2m ? e->Kt : 0; g.d2b = lane ? e->t2m_d2_2.p : e->t2m_d2.p;
+  g.red_out = F.h_reduce;
   for (int i = 0; i < n_props; ++i) { F.mpart[i] = g.Mpart[i]; F.mpart_half[i] = props[i]->mpart_half; }
   launch_step_regression(F.stream, g);
-  if (!batched) {  // 4b: many partials are summed by many CUs before the one-workgroup factorisation (see launch_step_reduce)
+  if (!batched && !F.mate && !lane) {  // (a twin pass is not issued where 4b would be needed: twin_splits_ok) 4b: many partials are summed by many CUs before the one-workgroup factorisation (see launch_step_reduce)
     bool many = false;
     for (int i = 0; i < n_props; ++i) many = many || splits[i] >= kStepReduceSplits;
     if (many) {
@@ -337,7 +404,7 @@ bool chain_step_record(icp_evaluator* e, int n_props, icp_proposal* const* props
   const int Ksurf = F.Ksurf;
   const bool eigen_first_use = F.eigen_first_use;
   const bool eigen_status_pinned = eigen_speculation_supported(r);
-  const double* h_coeffs = c.h_res + 16 + F.parity * kCoeffArea;
+  const double* h_coeffs = F.h_coeffs;
   if (eigen_first_use && eigen_status_pinned) {  // this step's first launch waited for that decomposition: its status is in
     icp_proposal* p = props[generator];
     const int st = p->h_eig[ec[generator]->status_off / 3];
@@ -388,7 +455,7 @@ bool chain_step_record(icp_evaluator* e, int n_props, icp_proposal* const* props
       saved[8 + t] = c.h_res[0];
       std::memcpy(c.h_res, saved.data(), sizeof(double) * saved.size());
     }
-  for (int i = 0; i < 8; ++i) c.h_res[i] = c.h_res[kReduceArea + F.parity * 8 + i];  // launch 4's reductions, where finish_eval looks
+  for (int i = 0; i < 8; ++i) c.h_res[i] = F.h_reduce[i];  // launch 4's reductions, where finish_eval looks
   icp_evaluator::Memo* m = eval_store(e, theta_prop);
   m->status = finish_eval(e, c.h_res, &m->value, m->aux);
   *log_value_prop = m->value;
@@ -428,46 +495,91 @@ bool chain_step_covered(icp_evaluator* e, int n_props, icp_proposal* const* prop
   return !per_stage;
 }
 
+// a twin pass has no launch 4b (launch_step_reduce): only where no posterior of the step has that many split-K partials
+bool twin_splits_ok(const icp_ctx& c, int n_props, icp_proposal* const* props) {
+  for (int i = 0; i < n_props; ++i) {
+    const int leaves = regression_splits(props[i]->K);
+    if (leaves / regression_fold(props[i]->K, c.r, 1) >= kStepReduceSplits) return false;
+  }
+  return true;
+}
+
+// icp_chain_step_prelaunch and icp_chain_step_prelaunch2 (generator2 / key2: the step after the next, or key2 == nullptr); -> lanes issued
+int chain_step_prelaunch(icp_evaluator* e, int32_t n_props, icp_proposal* const* props, int32_t generator, const double* theta_cur,
+                         const double* key, int32_t generator2, const double* key2) {
+  require(e != nullptr, "null argument");
+  if (n_props == 0) {  // "nothing further": drop a pending half step (and lane 1 of a twin pass being finished)
+    std::lock_guard<std::recursive_mutex> lk0(e->ctx->mu);
+    drop_front(e);
+    drop_twin(e);
+    return 0;
+  }
+  require(theta_cur && key, "null argument");
+  require(n_props >= 1 && n_props <= 2 && props, "bad proposal list");
+  require(generator < n_props && generator2 < n_props, "generator index out of range");
+  icp_ctx& c = *e->ctx;
+  for (int i = 0; i < n_props; ++i) require(props[i] && props[i]->ctx == &c, "proposal belongs to another context");
+  check_theta_finite(&c, theta_cur);
+  auto check_key = [&](int g, const double* k) {
+    if (g < 0) check_theta_finite(&c, k);
+    else
+      for (int j = 0; j < c.r; ++j)
+        if (!std::isfinite(k[j])) fail(ICP_ERR_NOT_FINITE, "z contains a non-finite value");
+  };
+  check_key(generator, key);
+  if (key2) check_key(generator2, key2);
+  std::lock_guard<std::recursive_mutex> lk(c.mu);
+  drop_front(e);
+  if (c.pipeline_off) return 0;
+  // with several chains in the process the device is not idle during one chain's turn-around, and the launches of a
+  // dropped half step cost the others host time (tools/multichain.py)
+  if (g_live_contexts.load(std::memory_order_relaxed) > 1) return 0;
+  if (!chain_step_covered(e, n_props, props, generator, theta_cur, key)) return 0;  // nothing to pre-launch
+  // every posterior of the assumed current state must be on record already (the step in flight computed them)
+  for (int i = 0; i < n_props; ++i)
+    if (!props[i]->find_entry(theta_cur)) return 0;
+  // the step after it beside it, as lane 1 of a twin pass: where the merged launches cover that one, too
+  // (ranks <= 64: the decomposition's status reaches the host by itself, no copy on the step's stream)
+  // Lane 1 is used only if lane 0's proposal is rejected: while the chain accepts more than every second step (acc_ema, as the
+  // speculative decompositions use it — the first steps of a chain from the mean: 17 of 20) it would be dropped more often than
+  // used, and its launches cost the accepted path about 1 % (the 20-step window of tools/ab_config1.py): one lane there.
+  const bool twin = key2 && !c.twin_off && e->acc_ema <= 0.5 && eigen_speculation_supported(c.r) && chain_step_covered(e, n_props, props, generator2, theta_cur, key2) &&
+                    twin_splits_ok(c, n_props, props) &&
+                    !(generator < 0 && generator2 < 0 && std::memcmp(key, key2, sizeof(double) * (10 + (size_t)c.r)) == 0);
+  Bound _b(&c, true);
+  try {
+    if (twin) enqueue_front(e, n_props, props, generator, theta_cur, key, e->front, false, &e->front2, generator2, key2);
+    else enqueue_front(e, n_props, props, generator, theta_cur, key, e->front);
+  } catch (...) {
+    release_front(e->front);
+    throw;
+  }
+  return twin ? 2 : 1;
+}
+
 }  // namespace
 
 extern "C" {
 
 int icp_chain_step_prelaunch(icp_evaluator* e, int32_t n_props, icp_proposal* const* props, int32_t generator, const double* theta_cur,
                              const double* z_or_theta_prop) {
+  return guard([&] { (void)chain_step_prelaunch(e, n_props, props, generator, theta_cur, z_or_theta_prop, -1, nullptr); });
+}
+
+int icp_chain_step_prelaunch2(icp_evaluator* e, int32_t n_props, icp_proposal* const* props, int32_t generator, const double* theta_cur,
+                              const double* z_or_theta_prop, int32_t generator2, const double* z_or_theta_prop2, int32_t* lanes_issued) {
+  if (lanes_issued) *lanes_issued = 0;
   return guard([&] {
-    require(e != nullptr, "null argument");
-    if (n_props == 0) {  // "nothing further": drop a pending half step
-      std::lock_guard<std::recursive_mutex> lk0(e->ctx->mu);
-      drop_front(e);
-      return;
-    }
-    require(theta_cur && z_or_theta_prop, "null argument");
-    require(n_props >= 1 && n_props <= 2 && props, "bad proposal list");
-    require(generator < n_props, "generator index out of range");
-    icp_ctx& c = *e->ctx;
-    for (int i = 0; i < n_props; ++i) require(props[i] && props[i]->ctx == &c, "proposal belongs to another context");
-    check_theta_finite(&c, theta_cur);
-    if (generator < 0) check_theta_finite(&c, z_or_theta_prop);
-    else
-      for (int j = 0; j < c.r; ++j)
-        if (!std::isfinite(z_or_theta_prop[j])) fail(ICP_ERR_NOT_FINITE, "z contains a non-finite value");
-    std::lock_guard<std::recursive_mutex> lk(c.mu);
-    drop_front(e);
-    if (c.pipeline_off) return;
-    // with several chains in the process the device is not idle during one chain's turn-around, and the launches of a
-    // dropped half step cost the others host time (tools/multichain.py)
-    if (g_live_contexts.load(std::memory_order_relaxed) > 1) return;
-    if (!chain_step_covered(e, n_props, props, generator, theta_cur, z_or_theta_prop)) return;  // nothing to pre-launch
-    // every posterior of the assumed current state must be on record already (the step in flight computed them)
-    for (int i = 0; i < n_props; ++i)
-      if (!props[i]->find_entry(theta_cur)) return;
-    Bound _b(&c, true);
-    try {
-      enqueue_front(e, n_props, props, generator, theta_cur, z_or_theta_prop, e->front);
-    } catch (...) {
-      release_front(e->front);
-      throw;
-    }
+    const int lanes = chain_step_prelaunch(e, n_props, props, generator, theta_cur, z_or_theta_prop, generator2, z_or_theta_prop2);
+    if (lanes_issued) *lanes_issued = lanes;
+  });
+}
+
+int icp_ctx_twin_stats(icp_ctx* ctx, int64_t out[3]) {
+  return guard([&] {
+    require(ctx && out, "null argument");
+    std::lock_guard<std::recursive_mutex> lk(ctx->mu);
+    for (int i = 0; i < 3; ++i) out[i] = ctx->twin_stats[i];
   });
 }
 
@@ -491,9 +603,13 @@ int icp_chain_step(icp_evaluator* e, int32_t n_props, icp_proposal* const* props
     std::lock_guard<std::recursive_mutex> lk(c.mu);
     const int r = c.r;
     const double* key = generator >= 0 ? z : theta_prop;
-    const bool reuse = n_props <= 2 && front_matches(e->front, n_props, props, generator, theta_cur, key, r);
-    if (e->front.valid && !reuse) drop_front(e);  // pre-launched for another outcome: dropped
-    per_stage = !reuse && !chain_step_covered(e, n_props, props, generator, theta_cur, theta_prop);
+    // lane 1 of the twin pass whose lane 0 the previous call consumed: this is the step it was made for (lane 0 was rejected), or
+    // it is dropped — and with it the front launched behind it, for a state the chain has left
+    const bool lane1 = n_props <= 2 && front_matches(e->twin.F, n_props, props, generator, theta_cur, key, r);
+    if (e->twin.valid && !lane1) drop_twin(e);
+    const bool reuse = !lane1 && n_props <= 2 && front_matches(e->front, n_props, props, generator, theta_cur, key, r);
+    if (e->front.valid && !reuse && !lane1) drop_front(e);  // pre-launched for another outcome: dropped
+    per_stage = !reuse && !lane1 && !chain_step_covered(e, n_props, props, generator, theta_cur, theta_prop);
     if (per_stage) {
       // what the five merged launches do not cover as a configuration takes the wide step (a batch of one chain)
       wide = wide_depth < 2 && n_props >= 1 && n_props <= 2 && !step_pipeline_covers(e, n_props, props) &&
@@ -504,7 +620,7 @@ int icp_chain_step(icp_evaluator* e, int32_t n_props, icp_proposal* const* props
     g_host_timing.start();
 
     for (int i = 0; i < n_props; ++i) props[i]->resolve_speculation(theta_cur);
-    if (!e->last_prop.empty()) {  // did the caller keep the state the previous step proposed?
+    if (!e->last_prop.empty() && !e->acc_counted) {  // did the caller keep the state the previous step proposed?
       const bool accepted = std::memcmp(e->last_prop.data(), theta_cur, sizeof(double) * (10 + (size_t)r)) == 0;
       e->acc_ema = 0.9 * e->acc_ema + (accepted ? 0.1 : 0.0);
     }
@@ -513,8 +629,20 @@ int icp_chain_step(icp_evaluator* e, int32_t n_props, icp_proposal* const* props
       StepFront* f;
       ~FrontGuard() { if (f) release_front(*f); }
     } front_guard{&F};
-    if (reuse) { F = e->front; e->front = StepFront{}; }
-    else enqueue_front(e, n_props, props, generator, theta_cur, key, F);
+    StepFront F1;  // lane 1 of a twin front, until its finish launch is out
+    FrontGuard front1_guard{&F1};
+    StepFinishArgs f{};
+    int step_seq = 0;
+    if (lane1) {  // launches 1-5 are out (or done): the previous call issued them
+      F = e->twin.F; f = e->twin.f; step_seq = e->twin.seq;
+      e->twin = TwinPending{};
+    } else if (reuse) {
+      F = e->front; e->front = StepFront{};
+      if (F.mate) { F1 = *F.mate; *F.mate = StepFront{}; F.mate = nullptr; }
+    } else {
+      enqueue_front(e, n_props, props, generator, theta_cur, key, F);
+    }
+    const bool twin = F1.valid;
     g_host_timing.mark(0);
     PosteriorEntry** ec = F.ec;
     PosteriorEntry** ep = F.ep;
@@ -523,8 +651,10 @@ int icp_chain_step(icp_evaluator* e, int32_t n_props, icp_proposal* const* props
     // the decompositions of ranks <= 64 leave their status in pinned memory themselves; the others need a copy
     const bool eigen_status_pinned = eigen_speculation_supported(r);
     const bool eigen_enqueued = eigen_first_use && !eigen_status_pinned;
-    for (int i = 0; i < 16; ++i) c.h_res[i] = 0.0;
-    for (int i = 0; i < 16; ++i) c.h_status[i] = 0;
+    if (!lane1) {
+      for (int i = 0; i < 16; ++i) c.h_res[i] = 0.0;
+      for (int i = 0; i < 16; ++i) c.h_status[i] = 0;
+    }
 
     // Adaptive (speculation_mode): an accepted step finds its basis ≈ 50 µs earlier; a rejected one has paid one launch for
     // nothing: ≈ 3 µs of host time, a few CUs — and the eigen stream, which the next decomposition shares, until the launch has
@@ -540,26 +670,47 @@ int icp_chain_step(icp_evaluator* e, int32_t n_props, icp_proposal* const* props
     const bool plan_only = spec_mode == 0 && e->acc_ema >= 0.1 && spec_possible;
     // test hook: the speculative decompositions wait for a word that never comes, time out and are repeated
     static const int starve = dev_env("ICP_TEST_STARVE_SPECULATION") ? (1 << 24) : 0;
-    const int step_seq = ++c.step_seq;
 
-    // 5: factorisations + tails (results go straight to pinned host memory)
-    StepFinishArgs f{};
-    f.n = n_props; f.r = r; f.Ginv = c.Ginv.p; f.sigma2 = kSigma2;
-    for (int i = 0; i < n_props; ++i) {
-      icp_proposal* p = props[i];
-      f.Mpart[i] = F.mpart[i]; f.splits[i] = F.splits[i];
-      f.M[i] = ep[i]->M.p; f.alpha[i] = ep[i]->alpha.p;
-      f.status[i] = p->status.p + ep[i]->status_off;
-      f.host_status[i] = c.h_status + 8 + i;
-      f.fwd[i] = TransitionTailIO{ec[i]->alpha.p, ec[i]->M.p, ec[i]->coeffs.p, ep[i]->coeffs.p, p->prm.step_length,
-                                  c.h_res + 8 + 2 * i, c.h_status + 2 * i};
-      f.bwd[i] = TransitionTailIO{ep[i]->alpha.p, ep[i]->M.p, ep[i]->coeffs.p, ec[i]->coeffs.p, p->prm.step_length,
-                                  c.h_res + 9 + 2 * i, c.h_status + 2 * i + 1};
+    // 5: factorisations + tails (results go straight to pinned host memory: `res` / `st`, lane 1's into areas of its own)
+    auto finish_args = [&](const StepFront& L, double* res, int* st) {
+      StepFinishArgs a{};
+      a.n = n_props; a.r = r; a.Ginv = c.Ginv.p; a.sigma2 = kSigma2;
+      for (int i = 0; i < n_props; ++i) {
+        icp_proposal* p = props[i];
+        PosteriorEntry* lc = L.ec[i];
+        PosteriorEntry* lp = L.ep[i];
+        a.Mpart[i] = L.mpart[i]; a.splits[i] = L.splits[i];
+        a.M[i] = lp->M.p; a.alpha[i] = lp->alpha.p;
+        a.status[i] = p->status.p + lp->status_off;
+        a.host_status[i] = st + 8 + i;
+        a.fwd[i] = TransitionTailIO{lc->alpha.p, lc->M.p, lc->coeffs.p, lp->coeffs.p, p->prm.step_length, res + 8 + 2 * i, st + 2 * i};
+        a.bwd[i] = TransitionTailIO{lp->alpha.p, lp->M.p, lp->coeffs.p, lc->coeffs.p, p->prm.step_length, res + 9 + 2 * i, st + 2 * i + 1};
+      }
+      a.seq = step_seq;
+      return a;
+    };
+    if (!lane1) {
+      step_seq = ++c.step_seq;
+      f = finish_args(F, c.h_res, c.h_status);
+      f.done_counter = c.d_done.p; f.host_flag = c.h_flag;
+      f.ready_flag = c.d_done.p + 2;  // (speculative decompositions and the next step's first launches wait for it)
+      c.last_back_seq = step_seq;
+      if (twin) {
+        // one finish launch for both lanes; lane 1 has a completion counter and a host flag of its own, so that this step's
+        // results are not held back by it.  Lane 1 stays with the evaluator: the next call takes it, or drops it.
+        for (int i = 0; i < 16; ++i) c.h_twin[i] = 0.0;
+        for (int i = 0; i < 16; ++i) c.h_twin_status[i] = 0;
+        StepFinishArgs f1 = finish_args(F1, c.h_twin, c.h_twin_status);
+        f1.done_counter = c.d_done.p + 3; f1.host_flag = c.h_flag + 1;
+        launch_step_twin_finish(F.stream, f, f1);
+        e->twin.F = F1; e->twin.f = f1; e->twin.seq = step_seq; e->twin.valid = true;
+        F1 = StepFront{};  // (its slots belong to e->twin now)
+      } else {
+        launch_step_finish(F.stream, f);
+      }
     }
-    f.done_counter = c.d_done.p; f.host_flag = c.h_flag; f.seq = step_seq;
-    f.ready_flag = c.d_done.p + 2;  // (speculative decompositions and the next step's first launches wait for it)
-    c.last_back_seq = step_seq;
-    launch_step_finish(F.stream, f);
+    // (lane 1: nothing to launch on the step streams.  Lane 0 was rejected, its speculative decomposition has just been cancelled —
+    // resolve_speculation above —, and lane 1's own goes out below: its input is complete)
     g_host_timing.mark(1);
     // the caller's outcome-independent host work runs beside the device — first of all the pre-launch of the next step's
     // first half, which the device can start as soon as the finish launch above has
@@ -586,7 +737,7 @@ int icp_chain_step(icp_evaluator* e, int32_t n_props, icp_proposal* const* props
     } else {
       // results and flag are written into pinned memory by the kernels: poll the flag (≈ 4 µs less than a stream
       // synchronisation); give up after 2 s and let the synchronisation report what went wrong
-      volatile int* flag = c.h_flag;
+      volatile int* flag = f.host_flag;
       const auto t_start = std::chrono::steady_clock::now();
       long spins = 0;
       while (*flag != f.seq) {
@@ -598,13 +749,20 @@ int icp_chain_step(icp_evaluator* e, int32_t n_props, icp_proposal* const* props
       }
       c.stage_used = 0;
     }
+    if (lane1) {
+      for (int i = 0; i < 16; ++i) c.h_res[i] = c.h_twin[i];
+      for (int i = 0; i < 16; ++i) c.h_status[i] = c.h_twin_status[i];
+    }
 
     // ---- bookkeeping with the results in hand
     g_host_timing.mark_wait(eigen_first_use);
     if (c.h_wait_error[0]) {
       // A first launch did not see the word it waits for within 50 ms and went ahead unordered.  That is what a tool does
       // that lets one kernel run at a time in an order of its own (rocprofv3 --pmc): drain everything, switch the pipelining
-      // off for this context, and do the step again — nothing of it has been recorded.
+      // off for this context, and do the step again — nothing of it has been recorded.  (The decomposition started or planned
+      // for its proposed state is withdrawn first: the repeated step starts it again, in the same place of the count.)
+      for (int i = 0; i < n_props; ++i) props[i]->withdraw_speculation();
+      e->acc_counted = true;
       HIP_OK(hipStreamSynchronize(c.stream));
       c.front_stream.sync();  // (a half step launched ahead may time out here, too)
       sync_eigen(c);
@@ -614,20 +772,23 @@ int icp_chain_step(icp_evaluator* e, int32_t n_props, icp_proposal* const* props
       c.pipeline_off = true;
       ++c.stats.pipeline_fallbacks; ++g_runtime_stats.pipeline_fallbacks;
       ++c.stats.step_redos; ++g_runtime_stats.step_redos;
-      if (e->front.valid) release_front(e->front);
+      release_fronts(e);  // (lane 1 of a twin pass included: nothing of either lane has been recorded)
       redo = true;
       return;
     }
     if (!chain_step_record(e, n_props, props, generator, theta_cur, F, f, theta_prop, log_value_prop, fwd, bwd, &status)) {
       ++c.stats.step_redos; ++g_runtime_stats.step_redos;
+      drop_twin(e);  // (lane 1 may have drawn from the same basis)
       redo = true;
       return;
     }
+    if (lane1) ++c.twin_stats[1];
     s.reserved = false;
     for (int i = 0; i < n_props; ++i) ep[i]->reserved = false;
     front_guard.f = nullptr;
     ++c.paths.n[0]; ++g_step_paths.n[0];
     e->last_prop.assign(theta_prop, theta_prop + 10 + r);
+    e->acc_counted = false;
     g_host_timing.mark(4);
     g_host_timing.end();
   });

@@ -422,7 +422,8 @@ struct icp_ctx {
   // ICP_NO_PIPELINE=1, or a first launch once timed out on its word (a tool that lets one kernel run at a time, in an order
   // of its own): every step on `stream`, nothing launched ahead, no device-side waits
   bool pipeline_off = std::getenv("ICP_NO_PIPELINE") != nullptr;
-  bool stream_used_elsewhere = false;            // an entry point other than the chain step has enqueued on `stream`
+  bool twin_off = std::getenv("ICP_NO_TWIN") != nullptr;  // ICP_NO_TWIN=1: one step per front (icp_chain_step_prelaunch2 issues one lane)
+  bool stream_used_elsewhere = false;           // an entry point other than the chain step has enqueued on `stream`
   int last_back_seq = 0;                         // sequence number of the last finish launch
   int* h_wait_error = nullptr;                   // pinned: a front gave up waiting (never expected)
   std::recursive_mutex mu;
@@ -447,6 +448,7 @@ struct icp_ctx {
   QueryScratch scratch_tn; // … and nearest model vertices of the evaluator's target-side surface points (their own candidate counters)
   QueryScratch scratch_p;  // the proposal's own model ids where the evaluator's searches run as a sequence of their own (the wide step)
   QueryScratch scratch_en; // … and the nearest vertices of the evaluator's own ids in that case
+  QueryScratch scratch_twin[3];  // sets 0-2 once more, for lane 1 of a twin pass (which = 7, 8, 9)
   // staging for small host<->device transfers of one API call
   double* h_stage = nullptr;  // pinned
   DBuf<double> d_stage;
@@ -462,7 +464,14 @@ struct icp_ctx {
   DBuf<int> d_status;         // view
   DBuf<int> d_done;            // [0] completion counter of the step's last launch; [1] counter and [2] "partials ready" word
                                // of its regression launch
-  int* h_flag = nullptr;       // pinned: sequence number of the last finished step
+  int* h_flag = nullptr;       // pinned: sequence number of the last finished step ([1]: of lane 1 of the last twin pass)
+  // lane 1 of a twin pass (icp_chain_step_prelaunch2) has result areas of its own, in the layout of h_res / h_status: [0,16) the
+  // tails' results, the two coefficient areas, launch 4's reductions; 16 status ints.  They lie behind h_res in the same pinned block.
+  static constexpr size_t kTwinDoubles = 16 + 2 * 512 + 16 + 8;
+  double* h_twin = nullptr;
+  int* h_twin_status = nullptr;
+  // icp_ctx_twin_stats: twin passes issued, lane-1 results used, lane-1 results dropped
+  int64_t twin_stats[3] = {0, 0, 0};
   int step_seq = 0;
   std::vector<struct icp_evaluator*> evaluators;  // live evaluators (a proposal being destroyed drops their pending half steps)
   std::vector<struct icp_proposal*> proposals;    // live proposals (icp_ctx_set_rotation forgets what they memoised under a triple)
@@ -528,7 +537,7 @@ struct icp_ctx {
   // K = 131,069 on the queries go in batches (query_batch).  The scratch only grows, but a call's stride and batches are those of a
   // fresh context: `want` is the most either of them can use
   QueryBuffers query_scratch(size_t K, size_t n_elems, int which = 0) {
-    QueryScratch& scratch = which == 1 ? scratch_v : which == 2 ? scratch_t : which == 3 ? scratch_n : which == 4 ? scratch_tn : which == 5 ? scratch_p : which == 6 ? scratch_en : this->scratch;
+    QueryScratch& scratch = which >= 7 ? scratch_twin[which - 7] : which == 1 ? scratch_v : which == 2 ? scratch_t : which == 3 ? scratch_n : which == 4 ? scratch_tn : which == 5 ? scratch_p : which == 6 ? scratch_en : this->scratch;
     if (K > scratch.cap) {
       HIP_OK(hipStreamSynchronize(stream));
       front_stream.sync();

@@ -101,7 +101,7 @@ void wide_loop_claim(const LoopRun& a, std::vector<WideLoopChain>& chains) {
     // chain's lock over its whole claim, sets the mark at the claim's end.)
     c.batch_busy = true;
     ch.busy = true;
-    if (ch.e->front.valid) release_front(ch.e->front);
+    release_fronts(ch.e);
     for (int i = 0; i < n_props; ++i) {
       icp_proposal* p = ch.props[i];
       p->resolve_speculation(a.theta[b]);

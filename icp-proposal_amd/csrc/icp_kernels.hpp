@@ -145,6 +145,7 @@ struct SurfaceTask {  // one batch of closest-point-on-surface queries against o
   double* d2;
   int* tri;
   int tblocks, ksplit, kchunk;  // filter decomposition: tblocks × ksplit workgroups
+  int keep_hint;                // != 0: `hint` is read, the new winner is not written back (the second lane of a twin pass)
   // profiling only (nullptr otherwise): executed tests, counted per wave — [0] ball tests (one query against a wave's patch),
   // [1] sphere tests (one query against one triangle's bounding sphere), [2] exact point–triangle evaluations of the resolve stage
   unsigned long long* stats;
@@ -161,6 +162,7 @@ struct VertexTask {  // one batch of nearest-vertex queries against one vertex s
   double* d2;  // outputs, any may be null
   int* idx;
   int vblocks, ksplit, kchunk;
+  int keep_hint;              // as SurfaceTask::keep_hint
   unsigned long long* stats;  // profiling only: [3] exact point–vertex distances of the filter (every pair), [4] of the resolve stage
 };
 
@@ -476,6 +478,19 @@ size_t step_batch_bytes(int B);
 // decompositions' completion words; ordered like this they can never keep them from becoming resident.  After 2 s the gate opens
 // anyway and says so in gate.error (pinned).
 struct StepBatchGate { const int* counter = nullptr; int expected = 0; int* error = nullptr; };
+// The twin pass of a lone chain (icp_chain_step_prelaunch2): the chain's next TWO proposals, both from the present state, go through
+// ONE set of five launches as two lanes — blockIdx.y = lane, the grid is the larger lane's, the other lane's surplus workgroups
+// return.  Both lanes' records travel by value in the kernel-argument segment (indexed with the uniform lane, as EigenBatch<2>);
+// the device bodies are those of the one-lane kernels, so a lane's values are the bits of a launch of its own.
+template <class T> struct StepTwin { T a[2]; };
+static_assert(sizeof(StepTwin<StepBeginArgs>) + 64 <= 4096 && sizeof(StepTwin<StepSearchArgs>) + 64 <= 4096 &&
+              sizeof(StepTwin<StepRegressionArgs>) + 64 <= 4096 && sizeof(StepTwin<StepFinishArgs>) + 64 <= 4096,
+              "both lanes' records must fit the kernel argument segment");
+// launches 1-4 from two captures (step_capture: arguments finalised, grids known); both lanes wait for the same words
+void launch_step_twin_front(hipStream_t st, const StepCapture& lane0, const StepCapture& lane1);
+// launch 5: per lane n factor + backward tails and n forward tails, a completion counter and a host flag per lane
+// (lane 1's ready_flag is ignored: the word is raised once)
+void launch_step_twin_finish(hipStream_t st, const StepFinishArgs& lane0, const StepFinishArgs& lane1);
 void launch_step_batch(hipStream_t st, int B, const StepCapture* caps, void* pinned, void* device, hipStream_t st_finish = nullptr,
                        hipEvent_t ev = nullptr, StepBatchGate gate = StepBatchGate{});
 // ---- the on-device Metropolis–Hastings loop (kernels_step.hip: k_mh_front / k_mh_decide; icp_abi.hip:

@@ -307,7 +307,7 @@ __device__ __forceinline__ void surface_resolve(const SurfaceTask& q, int k, dou
     if (q.cp) { q.cp[3 * k] = c.x; q.cp[3 * k + 1] = c.y; q.cp[3 * k + 2] = c.z; }
     if (q.d2) q.d2[k] = best;
     if (q.tri) q.tri[k] = bi == kNoIndex ? -1 : bi;
-    if (q.hint) q.hint[k] = bi == kNoIndex ? -1 : bi;
+    if (q.hint && !q.keep_hint) q.hint[k] = bi == kNoIndex ? -1 : bi;
     if (q.stats) atomicAdd(q.stats + 2, (unsigned long long)(listed ? n : q.T));  // (an overflowed list: at most T, through the spheres)
   }
   *best_out = best;
@@ -461,7 +461,7 @@ __device__ __forceinline__ void vertex_resolve(const VertexTask& q, int k, doubl
   if (lane_id() == 0) {
     if (q.d2) q.d2[k] = best;
     if (q.idx) q.idx[k] = bi == kNoIndex ? -1 : bi;
-    if (q.hint) q.hint[k] = bi == kNoIndex ? -1 : bi;
+    if (q.hint && !q.keep_hint) q.hint[k] = bi == kNoIndex ? -1 : bi;
     if (q.stats) atomicAdd(q.stats + 4, (unsigned long long)(listed ? n : q.V));
   }
   *best_out = best;

@@ -453,6 +453,44 @@ __global__ void __launch_bounds__(NT) k_step_finish_batch(const StepFinishArgs* 
   step_finish_body<E, NT>(a, blockIdx.x);
 }
 
+// ---------------------------------------------------------------- the same five launches for the two lanes of a twin pass
+//
+// blockIdx.y = lane, both records in the kernel arguments (StepTwin); the bodies are the one-lane kernels'.  Both lanes of launch 1
+// wait for the same two words, one poll per workgroup as in the one-lane form.
+
+__global__ void __launch_bounds__(kStepBlock) k_step_begin_twin(StepTwin<StepBeginArgs> t) {
+  const StepBeginArgs& a = t.a[blockIdx.y];
+  if ((int)blockIdx.x >= step_begin_grid(a)) return;
+  step_begin_body(a, blockIdx.x);
+}
+template <int RMAX>
+__global__ void __launch_bounds__(kStepBlock) k_step_begin_twin_reg(StepTwin<StepBeginArgs> t) {
+  const StepBeginArgs& a = t.a[blockIdx.y];
+  if ((int)blockIdx.x >= step_begin_grid(a)) return;
+  step_begin_body_reg<RMAX>(a, blockIdx.x);
+}
+__global__ void __launch_bounds__(kSearchBlock) k_step_filter_twin(StepTwin<StepSearchArgs> t) {
+  const StepSearchArgs& a = t.a[blockIdx.y];
+  if ((int)blockIdx.x >= a.fstart[a.n_surf + a.n_vert]) return;
+  step_filter_body(a, blockIdx.x);
+}
+__global__ void __launch_bounds__(64) k_step_resolve_twin(StepTwin<StepSearchArgs> t) {
+  const StepSearchArgs& a = t.a[blockIdx.y];
+  if ((int)blockIdx.x >= a.rstart[a.n_surf + a.n_vert]) return;
+  step_resolve_body(a, blockIdx.x);
+}
+__global__ void __launch_bounds__(kStepBlock) k_step_regression_twin(StepTwin<StepRegressionArgs> t) {
+  const StepRegressionArgs& a = t.a[blockIdx.y];
+  if ((int)blockIdx.x >= step_regression_grid(a)) return;
+  step_regression_body(a, blockIdx.x);
+}
+template <int E, int NT>
+__global__ void __launch_bounds__(NT) k_step_finish_twin(StepTwin<StepFinishArgs> t) {
+  const StepFinishArgs& a = t.a[blockIdx.y];
+  if ((int)blockIdx.x >= 2 * a.n) return;
+  step_finish_body<E, NT>(a, blockIdx.x);
+}
+
 thread_local StepCapture* t_capture = nullptr;
 
 struct FinishPlan { int E /* tiles per thread */, NT, n_lds, tail_base; size_t shmem; bool ok; };
@@ -532,8 +570,8 @@ void launch_step_reduce(hipStream_t st, const StepReduceArgs& a) {
   hipLaunchKernelGGL(k_step_reduce, dim3(cdiv(a.nn, 256), a.n), dim3(256), 0, st, a);
 }
 
-void launch_step_finish(hipStream_t st, const StepFinishArgs& a_in) {
-  const FinishPlan p = finish_plan(a_in.r);
+namespace {
+StepFinishArgs finish_args_final(const StepFinishArgs& a_in, const FinishPlan& p) {
   StepFinishArgs a = a_in;
   a.n_lds = p.n_lds;
   a.tail_base = p.tail_base;
@@ -542,6 +580,64 @@ void launch_step_finish(hipStream_t st, const StepFinishArgs& a_in) {
   // the two choices differ at rank 64 alone (8 threads a row instead of 4: the last bit of a transition density).  Above 64 the
   // launch keeps the layout of its own size; there the two paths agree to the last bit or two (tests/test_gpu_chain.py).
   a.tpr_log2 = matvec_tpr_log2(a.r, a.r <= 64 ? 256 : p.NT);
+  return a;
+}
+template <int E, int NT>
+void launch_finish_twin(hipStream_t st, const StepTwin<StepFinishArgs>& t, int gx, size_t shmem) {
+  static size_t lds_granted = 0;
+  if (shmem > lds_granted) { set_dyn_lds((const void*)k_step_finish_twin<E, NT>, shmem); lds_granted = shmem; }
+  hipLaunchKernelGGL((k_step_finish_twin<E, NT>), dim3(gx, 2), dim3(NT), shmem, st, t);
+}
+}  // namespace
+
+void launch_step_twin_front(hipStream_t st, const StepCapture& l0, const StepCapture& l1) {
+  {
+    StepTwin<StepBeginArgs> t;
+    t.a[0] = l0.begin; t.a[1] = l1.begin;
+    const dim3 grid(std::max(l0.grid[0], l1.grid[0]), 2);
+    ProfScope _ps(st, KID_STEP_BEGIN);
+    static const bool no_reg = dev_env("ICP_BEGIN_STREAMED") != nullptr;  // (A/B switch, as launch_step_begin)
+    // (the register-holding variant where BOTH lanes draw from a decomposition still in flight; same bits either way)
+    const int r = l0.begin.r;
+    const bool hold = l0.begin.hold_regs && l1.begin.hold_regs && !no_reg;
+    if (hold && r >= 32 && r <= 52) hipLaunchKernelGGL(k_step_begin_twin_reg<52>, grid, dim3(kStepBlock), 0, st, t);
+    else if (hold && r >= 32 && r <= 64) hipLaunchKernelGGL(k_step_begin_twin_reg<64>, grid, dim3(kStepBlock), 0, st, t);
+    else hipLaunchKernelGGL(k_step_begin_twin, grid, dim3(kStepBlock), 0, st, t);
+  }
+  StepTwin<StepSearchArgs> q;
+  q.a[0] = l0.search; q.a[1] = l1.search;
+  if (const int gx = std::max(l0.grid[1], l1.grid[1]); gx > 0) {
+    ProfScope _ps(st, KID_STEP_FILTER);
+    hipLaunchKernelGGL(k_step_filter_twin, dim3(gx, 2), dim3(kSearchBlock), 0, st, q);
+  }
+  if (const int gx = std::max(l0.grid[2], l1.grid[2]); gx > 0) {
+    ProfScope _ps(st, KID_STEP_RESOLVE);
+    hipLaunchKernelGGL(k_step_resolve_twin, dim3(gx, 2), dim3(64), 0, st, q);
+  }
+  if (const int gx = std::max(l0.grid[3], l1.grid[3]); gx > 0) {
+    StepTwin<StepRegressionArgs> g;
+    g.a[0] = l0.regression; g.a[1] = l1.regression;
+    ProfScope _ps(st, KID_STEP_REGRESSION);
+    hipLaunchKernelGGL(k_step_regression_twin, dim3(gx, 2), dim3(kStepBlock), 0, st, g);
+  }
+}
+
+void launch_step_twin_finish(hipStream_t st, const StepFinishArgs& l0, const StepFinishArgs& l1) {
+  const FinishPlan p = finish_plan(l0.r);
+  StepTwin<StepFinishArgs> t;
+  t.a[0] = finish_args_final(l0, p);
+  t.a[1] = finish_args_final(l1, p);
+  t.a[1].ready_flag = nullptr;  // (raised once, by lane 0)
+  const int gx = 2 * std::max(l0.n, l1.n);
+  ProfScope _ps(st, KID_STEP_FINISH);
+  if (p.E == 1 && p.NT == 256) launch_finish_twin<1, 256>(st, t, gx, p.shmem);
+  else if (p.E == 2 && p.NT == 512) launch_finish_twin<2, 512>(st, t, gx, p.shmem);
+  else launch_finish_twin<2, 1024>(st, t, gx, p.shmem);
+}
+
+void launch_step_finish(hipStream_t st, const StepFinishArgs& a_in) {
+  const FinishPlan p = finish_plan(a_in.r);
+  const StepFinishArgs a = finish_args_final(a_in, p);
   if (t_capture) { t_capture->finish = a; t_capture->grid[4] = 2 * a.n; return; }
   ProfScope _ps(st, KID_STEP_FINISH);
   if (p.E == 1 && p.NT == 256) launch_finish<1, 256>(st, a, p.shmem);

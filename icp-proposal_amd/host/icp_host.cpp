@@ -14,6 +14,9 @@
 
 #include "icp_host.hpp"
 
+// (the harness also runs against a library built before the twin pass existed: the entry point is looked at before it is called)
+#pragma weak icp_chain_step_prelaunch2
+
 // java.lang.Double.toString for the magnitudes proposal names are made of (api/sampling/MixedProposalDistributions.scala:31-54
 // interpolates Scala Doubles: "RandomShape-0.1", "RotationYaw-0.01"): the shortest decimal that round-trips, with a
 // fractional part; computerised scientific notation below 1e-3 and from 1e7 ("1.0E-4")
@@ -115,43 +118,85 @@ struct icp_host_chain {
   ModelFittingParameters current;
   RecordLogger logger;
   double current_p = 0.0;
-  // the standard normals of step `ahead_step`, drawn by the idle hook of the native library while the step before it is
-  // on the device (counter-based RNG: a pure function of (seed, step, lane), so drawing early changes nothing)
-  std::vector<double> ahead, ahead2;  // … and of the step after that
-  uint64_t ahead_step = ~0ull, ahead2_step = ~0ull;
+  // the standard normals of the steps ahead, drawn by the idle hook of the native library while a step is on the device
+  // (counter-based RNG: a pure function of (seed, step, lane), so drawing early changes nothing).  A ring keyed by the step
+  // number: the step being finished reads its own while the hook draws those of the three steps behind it — the twin pass
+  // launched ahead takes steps two and three from here.
+  static constexpr int kAhead = 4;
+  std::vector<double> ahead[kAhead];
+  uint64_t ahead_step[kAhead] = {~0ull, ~0ull, ~0ull, ~0ull};
   std::thread::id runner;  // the thread inside icp_host_chain_run (chains that share a context share its hook slot)
-  void draw_normals(uint64_t step, std::vector<double>& out) const {
+  const std::vector<double>& normals_of(uint64_t step) {
+    const int k = (int)(step % kAhead);
+    if (ahead_step[k] != step) {
+      StepRandom rnd{seed, step};
+      for (size_t j = 0; j < ahead[k].size(); ++j) ahead[k][j] = rnd.normal(j);
+      ahead_step[k] = step;
+    }
+    return ahead[k];
+  }
+  const double* normals_if_drawn(uint64_t step) const { return ahead_step[step % kAhead] == step ? ahead[step % kAhead].data() : nullptr; }
+  void forget_ahead() {
+    for (uint64_t& s : ahead_step) s = ~0ull;
+    front_begin = front_end = 0;
+  }
+  // The front launched ahead (icp_chain_step_prelaunch2): the steps [front_begin, front_end) it was made for — one step, or two as
+  // the lanes of a twin pass — and the state it starts from.  ONE front is kept ahead of the step being finished.
+  uint64_t front_begin = 0, front_end = 0;
+  std::vector<double> front_state;
+  // what icp_chain_step will be asked for at `step` if the chain is still at `current` then: the mixture's leaf (peeked, the draw
+  // is a pure function of the step number) and its numbers; false: a leaf whose step is not launched ahead (a pose walk)
+  struct StepAhead { int generator = -1; const double* key = nullptr; ModelFittingParameters prop; };
+  bool step_ahead(uint64_t step, StepAhead& out) {
+    const std::vector<double>& z = normals_of(step);
     StepRandom rnd{seed, step};
-    for (size_t j = 0; j < out.size(); ++j) out[j] = rnd.normal(j);
+    rnd.ahead = z.data(); rnd.n_ahead = (int)z.size();
+    ProposalGeneratorWithTransition* leaf = root->peek(rnd, 0);
+    if (auto* ip = dynamic_cast<NonRigidIcpProposal*>(leaf)) {
+      if (!ip->stepper) return false;
+      out.generator = ip->stepperIndex; out.key = z.data();
+      return true;
+    }
+    if (auto* rw = dynamic_cast<RandomShapeUpdateProposal*>(leaf)) {
+      out.prop = rw->propose(current, rnd, 0);
+      out.generator = -1; out.key = out.prop.data();
+      return true;
+    }
+    return false;
   }
   static void draw_ahead(void* self) {
     icp_host_chain* ch = static_cast<icp_host_chain*>(self);
     if (std::this_thread::get_id() != ch->runner) return;  // another chain's step on a shared context: not our turn
-    const uint64_t next = (uint64_t)ch->logger.index + 1;
-    // the normals of step `next` were drawn one step earlier (below), so that the pre-launch can go out at once
-    if (ch->ahead_step != next) {
-      if (ch->ahead2_step == next) { ch->ahead.swap(ch->ahead2); ch->ahead2_step = ~0ull; }
-      else ch->draw_normals(next, ch->ahead);
-      ch->ahead_step = next;
-      // Two steps out of three are rejected: the next step then starts from the SAME state, and its proposal is a pure
-      // function of that state and of the numbers just drawn.  Its first launches are issued now, behind the step in
-      // flight, so the device does not idle through the host's turn-around; if this step is accepted instead they are
-      // dropped (icp_chain_step_prelaunch).
-      if (ch->prefetcher.whole_step && !ch->icp.empty() && ch->icp.size() <= 2) {
-        StepRandom rnd{ch->seed, next};
-        rnd.ahead = ch->ahead.data(); rnd.n_ahead = (int)ch->ahead.size();
-        ProposalGeneratorWithTransition* leaf = ch->root->peek(rnd, 0);
-        icp_proposal* hs[2] = {nullptr, nullptr};
-        for (size_t i = 0; i < ch->icp.size(); ++i) hs[i] = ch->icp[i]->h;
-        if (auto* ip = dynamic_cast<NonRigidIcpProposal*>(leaf)) {
-          if (ip->stepper) (void)icp_chain_step_prelaunch(ch->likelihood->h, (int)ch->icp.size(), hs, ip->stepperIndex, ch->current.data(), ch->ahead.data());
-        } else if (auto* rw = dynamic_cast<RandomShapeUpdateProposal*>(leaf)) {
-          const ModelFittingParameters prop = rw->propose(ch->current, rnd, 0);
-          (void)icp_chain_step_prelaunch(ch->likelihood->h, (int)ch->icp.size(), hs, -1, ch->current.data(), prop.data());
+    const uint64_t now = (uint64_t)ch->logger.index;  // the step being finished
+    // Two steps out of three are rejected: the next steps then start from the SAME state, and their proposals are pure
+    // functions of that state and of numbers that depend on the step number alone.  The first launches of the next TWO
+    // steps are issued now, as one set (a twin pass), behind the step in flight, so the device does not idle through the
+    // host's turn-around and a rejected step finds its successor's results waiting; if a step is accepted instead, what was
+    // launched for the steps behind it is dropped (icp_chain_step_prelaunch2).
+    if (ch->prefetcher.whole_step && !ch->icp.empty() && ch->icp.size() <= 2) {
+      if (ch->front_state != ch->current.allParameters) ch->front_begin = ch->front_end = 0;  // (made for a state the chain has left)
+      if (ch->front_begin <= now) {  // the front that covers this step has been taken (or there was none): the next one
+        const uint64_t start = std::max(now + 1, ch->front_end);
+        StepAhead a, b;
+        if (ch->step_ahead(start, a)) {
+          icp_proposal* hs[2] = {nullptr, nullptr};
+          for (size_t i = 0; i < ch->icp.size(); ++i) hs[i] = ch->icp[i]->h;
+          int32_t lanes = 0;
+          if (icp_chain_step_prelaunch2) {
+            const bool two = ch->step_ahead(start + 1, b);
+            (void)icp_chain_step_prelaunch2(ch->likelihood->h, (int)ch->icp.size(), hs, a.generator, ch->current.data(), a.key,
+                                            two ? b.generator : -1, two ? b.key : nullptr, &lanes);
+          } else if (start == now + 1) {  // (a library without the twin pass)
+            if (icp_chain_step_prelaunch(ch->likelihood->h, (int)ch->icp.size(), hs, a.generator, ch->current.data(), a.key) == ICP_OK) lanes = 1;
+          }
+          ch->front_begin = lanes ? start : 0;
+          ch->front_end = lanes ? start + (uint64_t)lanes : 0;
+          if (lanes) ch->front_state = ch->current.allParameters;
         }
       }
     }
-    if (ch->ahead2_step != next + 1) { ch->draw_normals(next + 1, ch->ahead2); ch->ahead2_step = next + 1; }
+    (void)ch->normals_of(now + 1);  // (so that the next hook's front can go out at once)
+    (void)ch->normals_of(now + 2);
   }
 };
 
@@ -242,8 +287,7 @@ int icp_host_chain_create(icp_ctx* ctx, const icp_host_chain_config* cfg, const 
       if (cfg->fused >= 2)
         for (size_t i = 0; i < ch->icp.size(); ++i) { ch->icp[i]->stepper = &ch->prefetcher; ch->icp[i]->stepperIndex = (int)i; }
     }
-    ch->ahead.assign(ch->r, 0.0);
-    ch->ahead2.assign(ch->r, 0.0);
+    for (auto& z : ch->ahead) z.assign(ch->r, 0.0);
     if (cfg->fused == 2) check(icp_ctx_set_idle_hook(ctx, &icp_host_chain::draw_ahead, ch), "icp_ctx_set_idle_hook");
     ch->current.allParameters.assign(theta0, theta0 + 10 + ch->r);
     ch->logger.P = 10 + ch->r;
@@ -266,13 +310,14 @@ int icp_host_chain_run(icp_host_chain* ch, int32_t n_steps, double* records) {
     ch->runner = std::this_thread::get_id();
     for (int s = 0; s < n_steps; ++s) {  // SamplingRegistration.scala:58-85: chain.iterator(...).take(n)
       StepRandom rnd{ch->seed, (uint64_t)ch->logger.index};
-      if (ch->ahead_step == rnd.step) { rnd.ahead = ch->ahead.data(); rnd.n_ahead = (int)ch->ahead.size(); }
+      if (const double* z = ch->normals_if_drawn(rnd.step)) { rnd.ahead = z; rnd.n_ahead = ch->r; }
       ch->current = ch->mh->next(ch->current, rnd, &ch->logger);
       ch->current_p = ch->mh->cached_current_p;
     }
     ch->logger.out = nullptr;
     // no further step for now: whatever was launched ahead for it is dropped
     if (ch->prefetcher.whole_step && ch->likelihood) (void)icp_chain_step_prelaunch(ch->likelihood->h, 0, nullptr, -1, nullptr, nullptr);
+    ch->front_begin = ch->front_end = 0;
   });
 }
 
@@ -579,7 +624,7 @@ static int run_on_device(icp_host_chain* const* chains, int32_t n_chains, int32_
     ch->prefetcher.submitted_index = -1;
     ch->likelihood->has_prefetch = false;
     for (auto* p : ch->icp) { p->prefetched[0].valid = false; p->prefetched[1].valid = false; }
-    ch->ahead_step = ~0ull; ch->ahead2_step = ~0ull;
+    ch->forget_ahead();
   }
   return ICP_OK;
 }

@@ -449,6 +449,21 @@ ICP_API int icp_chain_step(icp_evaluator *e, int32_t n_props, icp_proposal *cons
 ICP_API int icp_chain_step_prelaunch(icp_evaluator *e, int32_t n_props, icp_proposal *const *props, int32_t generator,
                                      const double *theta_cur, const double *z_or_theta_prop);
 
+/* The same with the step AFTER the next one beside it (the twin pass): while the chain stays where it is — two steps out of three
+ * are rejected — its next two proposals both start from theta_cur, so both go through ONE set of launches as two lanes
+ * (generator2 / z_or_theta_prop2: the second step's; NULL: icp_chain_step_prelaunch).  The icp_chain_step that asks for the first
+ * step finishes both lanes in one launch and returns the first one's results; if its proposal is rejected, the call for the second
+ * step finds that step's results in pinned memory and launches nothing; any other call drops the second lane.  Results are those
+ * of one step at a time, bit for bit (the same device code per lane; the decompositions keep their order).  One lane is issued
+ * where two are not possible: a second step the merged launches do not cover, ranks above 64, posteriors with 32 or more split-K
+ * partials, ICP_NO_TWIN=1 in the environment.  *lanes_issued (optional): 0, 1 or 2 — a caller keeps ONE such front ahead of
+ * the step being finished and uses the count to know which step the next front starts at. */
+ICP_API int icp_chain_step_prelaunch2(icp_evaluator *e, int32_t n_props, icp_proposal *const *props, int32_t generator,
+                                      const double *theta_cur, const double *z_or_theta_prop, int32_t generator2,
+                                      const double *z_or_theta_prop2, int32_t *lanes_issued);
+/* out: twin passes issued, second-lane results used, second-lane results dropped (icp_chain_step_prelaunch2) */
+ICP_API int icp_ctx_twin_stats(icp_ctx *ctx, int64_t out[3]);
+
 /* B chains per launch (SURVEY.md §8b "*_batched variants", §8e "within a GPU, batch B chains per launch"; the
  * reference runs its chains from a ForkJoin pool, apps/femur/RunMHRandomInitComparison.scala:66): icp_chain_step for
  * n_chains independent chains in ONE sequence of five launches (chain = second grid dimension), the decompositions of

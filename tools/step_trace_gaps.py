@@ -1,0 +1,74 @@
+#!/usr/bin/env python3
+"""The two chains of a rejected lone-chain step, from a rocprofv3 kernel trace of the benchmark.
+
+Finish chain: from the start of a finish launch (k_step_finish*) to the start of the next one, and the gap between the end of one
+and the start of the next.  Front chain: start-to-start distance of the first launches (k_step_begin*) that belong to consecutive
+finish launches (a step's first launch is the last one that started before its finish launch; fronts dropped after an accepted
+step have no finish launch and are left out).  With one finish launch per step (no twin passes) the records of the same command
+(bench.py --dump-outputs, column 1: accepted) tell rejected from accepted steps: the interval behind step k is a rejected step's
+if step k was rejected.  With twin passes a finish launch serves one or two steps: the intervals are tabulated by the kind of the
+launch they start at (twin or one-lane) instead.
+
+usage: step_trace_gaps.py <kernel_trace.csv> [records.npy] [label]   (markdown on stdout)"""
+import bisect
+import csv
+import statistics
+import sys
+
+rows = list(csv.DictReader(open(sys.argv[1])))
+records = sys.argv[2] if len(sys.argv) > 2 and sys.argv[2].endswith(".npy") else None
+label = sys.argv[-1] if len(sys.argv) > 2 and not sys.argv[-1].endswith(".npy") else "trace"
+
+
+def spans(word):
+    return sorted((int(r["Start_Timestamp"]), int(r["End_Timestamp"]), "twin" in r["Kernel_Name"]) for r in rows if word in r["Kernel_Name"])
+
+
+begin, finish = spans("k_step_begin"), spans("k_step_finish")
+begin_start = [b[0] for b in begin]
+own_begin = [begin[max(bisect.bisect_left(begin_start, f[0]) - 1, 0)][0] for f in finish]  # the first launch of each finish launch's step(s)
+
+
+def line(name, v):
+    if not v:
+        return "| %s | 0 | | | | |" % name
+    v = sorted(v)
+    return "| %s | %d | %.1f | %.1f | %.1f | %.1f |" % (name, len(v), statistics.median(v), v[len(v) // 10], v[(9 * len(v)) // 10],
+                                                        sum(v) / len(v))
+
+
+n = len(finish)
+groups = {}
+if records:
+    import numpy as np
+    acc = np.load(records)[:, 1] != 0
+    if len(acc) <= n and not any(f[2] for f in finish):
+        kind = [None] * (n - len(acc)) + ["accepted" if a else "rejected" for a in acc]  # (the timed steps are the last ones)
+    else:
+        records = None
+if not records:
+    kind = ["twin pass" if f[2] else "one-lane" for f in finish]
+for k in range(n - 1):
+    if kind[k] is None:
+        continue
+    g = groups.setdefault(kind[k], {"f2f": [], "gap": [], "b2b": []})
+    g["f2f"].append((finish[k + 1][0] - finish[k][0]) / 1e3)
+    g["gap"].append((finish[k + 1][0] - finish[k][1]) / 1e3)
+    g["b2b"].append((own_begin[k + 1] - own_begin[k]) / 1e3)
+print("# %s: intervals between the launches of consecutive steps\n" % label)
+print("| interval (us), by the step / launch it starts at | count | median | p10 | p90 | mean |")
+print("|---|---:|---:|---:|---:|---:|")
+for key in sorted(groups):
+    print(line("%s: begin start -> next begin start" % key, groups[key]["b2b"]))
+    print(line("%s: finish start -> next finish start" % key, groups[key]["f2f"]))
+    print(line("%s: finish end -> next finish start" % key, groups[key]["gap"]))
+names = {}
+for r in rows:
+    nm = r["Kernel_Name"]
+    if "k_step_" in nm:
+        k = nm.split("k_step_")[1].split("(")[0].split("<")[0]
+        names.setdefault(k, []).append((int(r["End_Timestamp"]) - int(r["Start_Timestamp"])) / 1e3)
+print("\n| launch | calls | avg us | median us |")
+print("|---|---:|---:|---:|")
+for k in sorted(names):
+    print("| k_step_%s | %d | %.2f | %.2f |" % (k, len(names[k]), sum(names[k]) / len(names[k]), statistics.median(names[k])))
