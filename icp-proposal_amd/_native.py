@@ -111,6 +111,7 @@ SIGNATURES = {
     "icp_chain_step_prelaunch2": (C.c_int, [C.c_void_p, C.c_int32, C.c_void_p, C.c_int32, C.c_void_p, C.c_void_p, C.c_int32, C.c_void_p,
                                             C.POINTER(C.c_int32)]),
     "icp_ctx_twin_stats": (C.c_int, [C.c_void_p, C.POINTER(C.c_int64)]),
+    "icp_ctx_twin_eigen_stats": (C.c_int, [C.c_void_p, C.POINTER(C.c_int64)]),
     "icp_ctx_profile_stop": (C.c_int, [C.c_void_p, C.POINTER(KernelStat), C.c_int32, C.POINTER(C.c_int32)]),
     "icp_chain_eval_step": (C.c_int, [C.c_void_p, C.c_int32, C.POINTER(C.c_void_p), c_double_p, c_double_p, c_double_p,
                                       c_double_p, c_double_p]),
@@ -212,6 +213,14 @@ def twin_stats(ctx_handle) -> dict:
     out = (C.c_int64 * 3)()
     check(lib().icp_ctx_twin_stats(ctx_handle, out), "icp_ctx_twin_stats")
     return {"passes": int(out[0]), "lane1_used": int(out[1]), "lane1_dropped": int(out[2])}
+
+
+def twin_eigen_stats(ctx_handle) -> dict:
+    """icp_ctx_twin_eigen_stats: second-lane decompositions started with the first lane's, kept, cancelled because the first lane
+    was accepted, started cold."""
+    out = (C.c_int64 * 4)()
+    check(lib().icp_ctx_twin_eigen_stats(ctx_handle, out), "icp_ctx_twin_eigen_stats")
+    return {"started_early": int(out[0]), "kept": int(out[1]), "cancelled_by_lane0": int(out[2]), "started_cold": int(out[3])}
 
 
 def runtime_stats(ctx_handle=None) -> dict:

@@ -182,6 +182,10 @@ class IcpContext:
         """Twin passes issued, second-lane results used and dropped (icp_ctx_twin_stats)."""
         return nat.twin_stats(self.h)
 
+    def twin_eigen_stats(self) -> dict:
+        """Second-lane decompositions started early, kept, cancelled by an accepted first lane, started cold (icp_ctx_twin_eigen_stats)."""
+        return nat.twin_eigen_stats(self.h)
+
     def profile_start(self, max_launches: int = 200000, count_searches: bool = False):
         """count_searches: also count the tests the searches execute (rows "count.*" of profile_stop; slows the filter launches
         down — for a short leg of its own, not for timing)."""

@@ -449,7 +449,7 @@ int icp_ctx_set_rotation(icp_ctx* ctx, const double* angles, const double* R) {
           PosteriorEntry& en = p->memo[i];
           if (en.valid && same(en.theta)) { en.valid = false; en.eig_valid = false; en.eig_checked = false; }
         }
-        p->spec_entry = nullptr;
+        p->forget_speculation();
       }
     };
     if (!R) {  // withdraw the entry

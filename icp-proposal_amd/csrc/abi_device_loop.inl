@@ -178,7 +178,12 @@ void merged_loop_chain_records(const LoopRun& a, MergedLoopChain& ch, MergedLoop
   m.coeff_prop = ch.slot->coeffs.p;
   m.red = gr.res.p + (size_t)k * 32;
   m.chol_status = gr.stat.p + (size_t)k * 16 + 8;
-  for (int i = 0; i < n_props; ++i) m.eig_seq[i] = ch.props[i]->eig_seq;
+  // (the loop counts on from the place and raises the completion words of the set's entries to the places it takes, at most one per
+  // step: the host's numbers stay above them whatever becomes of the loop — booked, forgotten or failed)
+  for (int i = 0; i < n_props; ++i) {
+    m.eig_seq[i] = ch.props[i]->eig.place;
+    ch.props[i]->eig.foreign_words_up_to(ch.props[i]->eig.place + a.n_steps);
+  }
   for (int i = 0; i < 16; ++i) { c.h_res[i] = 0.0; c.h_status[i] = 0; }
 }
 
@@ -249,7 +254,7 @@ void merged_loop_forget(MergedLoopChain& ch, int i) {
   // (the entries' events and completion words — the claim's own decomposition may have left them — stay as they are)
   for (int sel = 0; sel < 2; ++sel) ch.set[sel][i]->off_record(false);
   ch.props[i]->warm_valid = false;
-  ch.props[i]->spec_entry = nullptr;
+  ch.props[i]->forget_speculation();
 }
 
 // nothing is handed out unless every chain came through: the chains' errors, then the decompositions behind the LAST step's decisions —
@@ -290,8 +295,8 @@ void merged_loop_book(const LoopRun& a, std::vector<MergedLoopChain>& chains, co
         if (sel == m.cur_sel) p->on_record(*ch.set[sel][i], a.theta[b], a.P);
         else ch.set[sel][i]->off_record();
       }
-      p->eig_seq = m.eig_seq[i];
-      p->spec_entry = nullptr;
+      p->forget_speculation();
+      p->eig.place = m.eig_seq[i];
     }
     ch.slot->valid = false;
     loop_count_steps(ch.e, a.n_steps);

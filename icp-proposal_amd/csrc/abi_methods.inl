@@ -122,6 +122,10 @@ int icp_proposal_create(icp_ctx* ctx, const icp_proposal_params* params, icp_pro
     p->prm.target_points = nullptr;  // caller memory is not retained
     p->work.alloc(eigen_work_doubles(ctx->r));
     p->work.fill_bytes(0);  // holds the completion counter of the eigenvector replay kernel
+    if (eigen_speculation_supported(ctx->r)) {  // lane 1's of a twin pass (zeroed like `work`: the replay kernel's counters)
+      p->work_twin.alloc(eigen_work_doubles(ctx->r));
+      p->work_twin.fill_bytes(0);
+    }
     if (ctx->eig_stream2) {  // ranks above 64: the second eigen stream's work area
       p->work2.alloc(eigen_work_doubles(ctx->r));
       p->work2.fill_bytes(0);
@@ -196,7 +200,7 @@ int icp_proposal_set_sampler(icp_proposal* p, int32_t sampler) {
       if (refactor) p->memo[i].valid = false;
     }
     p->side_parts = nullptr; p->side_parts_entry = nullptr;
-    p->spec_entry = nullptr;
+    p->forget_speculation();
     p->warm_valid = false;
     p->sampler = sampler;
   });

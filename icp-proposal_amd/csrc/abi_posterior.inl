@@ -19,7 +19,7 @@ struct PosteriorEntry {
                                   // an event record is 2-3 µs of host time on the accepted path)
   int done_value = 0;             // … and what the entry's word in icp_proposal::eig_words holds once it is complete (0: none)
   bool planned = false, planned_cold = false;  // the place in the proposal's count of decompositions that a speculative launch would
-  int planned_seq = 0;                         // have taken, kept for the ordinary one (icp_proposal::plan_eigen)
+                                               // have taken, kept for the ordinary one (icp_proposal::plan_eigen)
   uint64_t stamp = 0;
   DBuf<int> id, aux;
   DBuf<double> pt, nhat, e;
@@ -70,16 +70,30 @@ struct icp_proposal {
   int sampler = ICP_SAMPLER_EIGEN; // icp_proposal_set_sampler: what the "decomposition" of a posterior writes into V / S
   int* h_eig = nullptr;            // pinned: eigen status of every memo entry, written by the decomposition itself
   DBuf<int> eig_words;             // per memo entry: sequence number of its last finished decomposition (EigenRequest::done_word)
-  int eig_seq = 0;
+  EigenCount eig;                  // places in the cycle of 128 (cold starts) and completion-word numbers (icp_eigen_count.hpp)
   int* h_cancel = nullptr;         // pinned, 16 slots: the decomposition with sequence number q gives up once slot q%16 holds q
   int spec_seq = 0;
-  PosteriorEntry* spec_entry = nullptr;
+  // Decompositions started ahead and not yet resolved.  [0]: of the state the last step proposed — or, behind a twin pass whose
+  // lane 0 was rejected, of lane 1's (`lane1`: it moved here from [1]); [1]: of lane 1 of the twin pass just finished, launched
+  // together with lane 0's.  Each has a cancel slot of its own (`seq`).
+  struct PendingSpec { PosteriorEntry* e = nullptr; int seq = 0; bool lane1 = false; };
+  PendingSpec spec[2];
+  // (the caller has waited for the eigen stream, or dropped the entries; a pending lane 1 gives its place back as a cancelled one does)
+  void forget_speculation() {
+    if (spec[1].e) eig.give_back();
+    spec[0] = spec[1] = PendingSpec{};
+  }
   // fills the request of a speculative decomposition of `e` (the caller launches it, possibly together with another
   // proposal's, on the context's eigen stream and records e.eig_done behind it)
   void speculate_eigen(PosteriorEntry& e, const PosteriorEntry& cur, int splits, int half /* of Mpart: the step's partials */,
-                       const int* ready, int ready_seq, EigenSpec* spec_out, EigenRequest* rq_out);
-  void resolve_speculation(const double* theta_cur);
+                       const int* ready, int ready_seq, EigenSpec* spec_out, EigenRequest* rq_out, int lane = 0);
+  // lane1_step: the call is the step lane 1 of the last twin pass was made for (its decomposition stays pending)
+  // -> the basis kept was one started for a lane 1
+  bool resolve_speculation(const double* theta_cur, bool lane1_step = false);
   void withdraw_speculation();
+  // lane 1's pending decomposition is cancelled and its place given back; -> there was one
+  bool cancel_lane1_speculation();
+  void cancel_pending(PendingSpec& ps);
   DBuf<int> status;       // 3 ints per memo entry: {chol(M), chol(G+σ²M), eigen}
   // (pinned: the copy of `status` into it is a true asynchronous copy — into a pageable vector it was a synchronising one, 20-30 µs
   // per step of the per-stage paths)
@@ -122,6 +136,7 @@ struct icp_proposal {
   icp_evaluator* bound_eval = nullptr;
   int bound_index = -1;
   DBuf<double> work2;  // eig_stream2's (ranks above 64)
+  DBuf<double> work_twin;  // ranks <= 64: of lane 1's decomposition where it runs beside lane 0's in one launch (a twin pass)
   unsigned eig_flip = 0;
   void await_eigen(PosteriorEntry& e);   // make the context stream wait for it
   void check_status(PosteriorEntry& e);
@@ -173,6 +188,7 @@ struct TwinPending {
   StepFront F;
   StepFinishArgs f{};
   int seq = 0;
+  bool eigen_early = false;  // its decompositions went out with lane 0's (icp_proposal::spec[1])
 };
 }  // namespace
 
@@ -443,11 +459,12 @@ void icp_proposal::prepare_eigen(PosteriorEntry& e, EigenRequest* rq) {
   // first-order correction (<= 1e-11): every 128th starts cold, from the identity, which puts an end to the accumulation.
   if (e.planned) {  // (counted when its state was proposed: plan_eigen)
     e.planned = false;
-    e.done_value = e.planned_seq;
+    e.done_value = eig.issue();
     if (e.planned_cold) warm_valid = false;
   } else {
-    e.done_value = ++eig_seq;
-    if (((eig_seq + 1) & 127) == 0) warm_valid = false;
+    const EigenCount::Ticket t = eig.take_ordinary();
+    e.done_value = t.number;
+    if (t.cold) warm_valid = false;
   }
   *rq = EigenRequest{e.M.p, warm_valid ? warm_ptr : nullptr, e.V.p, e.Vt.p, e.S.p, work.p, status.p + e.status_off + 2, nullptr,
                      h_eig + e.status_off / 3, eig_words.p + e.status_off / 3, e.done_value, ctx->sqrt_lambda.p};
@@ -558,22 +575,24 @@ void icp_proposal::await_eigen(PosteriorEntry& e) {
 // decomposition waits for it on the device (an event between that launch and the next one on the context stream would
 // hold the latter back by several µs)
 void icp_proposal::speculate_eigen(PosteriorEntry& e, const PosteriorEntry& cur, int splits, int half, const int* ready, int ready_seq,
-                                   EigenSpec* spec_out, EigenRequest* rq_out) {
+                                   EigenSpec* spec_out, EigenRequest* rq_out, int lane) {
   e.eig_event_valid = false;
   e.planned = false;
   ++spec_seq;
   *spec_out = EigenSpec{splits, h_cancel + (spec_seq & 15), spec_seq, ready, ready_seq, ctx->profiling ? ctx->d_wait_ticks.p + 1 : nullptr};
   // warm start: the basis of the current state's posterior (complete, or ahead of this launch on the same stream)
-  const double* warm = (eig_seq & 127) == 127 ? nullptr : (cur.eig_valid ? cur.V.p : (warm_valid ? warm_ptr : nullptr));  // (see prepare_eigen)
+  const EigenCount::Ticket t = eig.take_ahead();
+  const double* warm = t.cold ? nullptr : (cur.eig_valid ? cur.V.p : (warm_valid ? warm_ptr : nullptr));  // (see prepare_eigen)
   h_eig[e.status_off / 3] = -1;  // in flight
-  e.done_value = ++eig_seq;
-  *rq_out = EigenRequest{Mpart.p + (size_t)half * mpart_half_doubles, warm, e.V.p, e.Vt.p, e.S.p, work.p, status.p + e.status_off + 2,
+  e.done_value = t.number;
+  // (lane 1 runs beside lane 0 in the same launch: a work area of its own)
+  *rq_out = EigenRequest{Mpart.p + (size_t)half * mpart_half_doubles, warm, e.V.p, e.Vt.p, e.S.p, lane ? work_twin.p : work.p, status.p + e.status_off + 2,
                          spec_out, h_eig + e.status_off / 3, eig_words.p + e.status_off / 3, e.done_value};
   rq_out->root = sampler == ICP_SAMPLER_CHOLESKY_ROOT;
   mpart_reader[half] = &e;
   e.eig_valid = true;
   e.eig_checked = false;
-  spec_entry = &e;
+  spec[lane] = PendingSpec{&e, spec_seq, lane != 0};
 }
 
 // Speculation switched off (ICP_NO_SPECULATION, ICP_SPECULATION=0) in a step that would otherwise have started the decomposition of
@@ -584,57 +603,82 @@ void icp_proposal::speculate_eigen(PosteriorEntry& e, const PosteriorEntry& cur,
 // a rejected state's place lapses, like a cancelled launch's (resolve_speculation).
 void icp_proposal::plan_eigen(PosteriorEntry& e) {
   e.planned = true;
-  e.planned_cold = (eig_seq & 127) == 127;  // (see speculate_eigen)
-  e.planned_seq = ++eig_seq;
+  e.planned_cold = eig.plan();  // (as speculate_eigen; the completion-word number is issued with the launch: prepare_eigen)
   plan_entry = &e;
 }
 
-// the caller's next current state decides the fate of the decomposition started for the last proposed state
-void icp_proposal::resolve_speculation(const double* theta_cur) {
+// a pending decomposition's state was not kept (or its entry was recycled meanwhile): its launch gives up at the next look at the word
+void icp_proposal::cancel_pending(PendingSpec& ps) {
+  PosteriorEntry& e = *ps.e;
+  __atomic_store_n(h_cancel + (ps.seq & 15), ps.seq, __ATOMIC_RELEASE);
+  e.eig_valid = false;
+  e.eig_checked = false;
+  ps = PendingSpec{};
+}
+
+bool icp_proposal::cancel_lane1_speculation() {
+  if (!spec[1].e) return false;
+  cancel_pending(spec[1]);
+  eig.give_back();  // (the place behind lane 0's: a lane 1 that is not used takes none)
+  return true;
+}
+
+// the caller's next current state decides the fate of the decompositions started for the last proposed states
+bool icp_proposal::resolve_speculation(const double* theta_cur, bool lane1_step) {
   if (plan_entry) {
     PosteriorEntry& pe = *plan_entry;
     plan_entry = nullptr;
     if (!(pe.valid && std::memcmp(pe.theta.data(), theta_cur, sizeof(double) * (10 + (size_t)ctx->r)) == 0)) pe.planned = false;
   }
-  if (!spec_entry) return;
-  PosteriorEntry& e = *spec_entry;
-  spec_entry = nullptr;
   // A decomposition that gave up waiting for its input (k_posterior_eigen_rr) has said so in its pinned status.  That
   // happens when the runtime puts its stream on a hardware queue ahead of the launch it waits for — many streams in one
   // process, or a tool that serialises kernels — and each occurrence stalls the step for the time-out: once is enough.
-  if (h_eig[e.status_off / 3] == kEigenGaveUp && !ctx->speculation_off) {
-    ctx->speculation_off = true;
-    ++ctx->stats.speculation_giveups; ++g_runtime_stats.speculation_giveups;
-  }
+  for (const PendingSpec& ps : spec)
+    if (ps.e && h_eig[ps.e->status_off / 3] == kEigenGaveUp && !ctx->speculation_off) {
+      ctx->speculation_off = true;
+      ++ctx->stats.speculation_giveups; ++g_runtime_stats.speculation_giveups;
+    }
   const size_t P = 10 + (size_t)ctx->r;
-  if (e.valid && e.eig_valid && std::memcmp(e.theta.data(), theta_cur, sizeof(double) * P) == 0) {
-    warm_ptr = e.V.p;  // accepted: this is the basis the next decompositions start from
-    warm_valid = true;
-    return;
+  bool kept = false, kept_lane1 = false;
+  if (spec[0].e) {
+    PosteriorEntry& e = *spec[0].e;
+    if (e.valid && e.eig_valid && std::memcmp(e.theta.data(), theta_cur, sizeof(double) * P) == 0) {
+      warm_ptr = e.V.p;  // accepted: this is the basis the next decompositions start from
+      warm_valid = true;
+      kept = true;
+      kept_lane1 = spec[0].lane1;
+      spec[0] = PendingSpec{};
+    } else {
+      cancel_pending(spec[0]);  // rejected (or the entry was recycled meanwhile)
+    }
   }
-  __atomic_store_n(h_cancel + (spec_seq & 15), spec_seq, __ATOMIC_RELEASE);  // rejected (or the entry was recycled meanwhile)
-  e.eig_valid = false;
-  e.eig_checked = false;
+  if (!spec[1].e) return kept_lane1;
+  // lane 1's: pending for one call more if this is the step it was made for — the call after this one resolves it as [0] —,
+  // cancelled otherwise (lane 0 was accepted, or the chain went elsewhere), and its place goes back
+  if (lane1_step && !kept) {
+    spec[0] = spec[1];
+    spec[1] = PendingSpec{};
+  } else {
+    (void)cancel_lane1_speculation();
+  }
+  return kept_lane1;
 }
 
 // The step that started (or planned) the decomposition of its proposed state is being repeated from scratch — its first launch
-// timed out on its word, nothing of it has been recorded.  The launch is cancelled, and the repeated step's decomposition takes
-// the same place in the cycle of 128, so that every 128th cold start stays on the step it falls on in an undisturbed chain.  A
-// planned place was never launched and is given back; a launched one is not given out again (a dropped launch still raises its
-// entry's completion word to its number): the count skips to the same place of the next cycle.
+// timed out on its word, nothing of it has been recorded.  The launches are cancelled and their places given back, so that the
+// repeated step's decompositions take the same places in the cycle of 128 and every 128th cold start stays on the step it falls
+// on in an undisturbed chain.  Their completion-word numbers are not given out again (a dropped launch still raises its entry's
+// word to its number): EigenCount.
 void icp_proposal::withdraw_speculation() {
   if (plan_entry) {
     plan_entry->planned = false;
     plan_entry = nullptr;
-    --eig_seq;
+    eig.give_back();
   }
-  if (!spec_entry) return;
-  PosteriorEntry& e = *spec_entry;
-  spec_entry = nullptr;
-  __atomic_store_n(h_cancel + (spec_seq & 15), spec_seq, __ATOMIC_RELEASE);
-  e.eig_valid = false;
-  e.eig_checked = false;
-  eig_seq += 127;
+  (void)cancel_lane1_speculation();
+  if (!spec[0].e) return;
+  cancel_pending(spec[0]);
+  eig.give_back();
 }
 
 // must be called after a synchronising copy of `status` into h_status

@@ -22,10 +22,20 @@ void drop_front(icp_evaluator* e) {
 }
 // Lane 1 of the twin pass whose lane 0 has been consumed, when the caller's next step is not the one it was made for (lane 0 was
 // accepted).  Its part of the finish launch may still be running — it writes the entries' M and alpha, reads their coefficients —
-// so the host sees its flag first (it trails lane 0's by a few µs at most); then the slots go back.
-void drop_twin(icp_evaluator* e) {
+// so the host sees its flag first (it trails lane 0's by a few µs at most); then the slots go back.  Its decomposition, if it was
+// started with lane 0's, is cancelled before anything else (the eigen stream is held until it has seen the word), and its place in
+// the proposal's count goes back.
+void drop_twin(icp_evaluator* e, bool lane0_accepted = false) {
   if (!e->twin.valid) return;
   icp_ctx& c = *e->ctx;
+  if (e->twin.eigen_early) {
+    bool any = false;
+    for (int i = 0; i < e->twin.F.n_props; ++i) {
+      icp_proposal* p = e->twin.F.props[i];
+      if (p->spec[1].e == e->twin.F.ep[i]) any = p->cancel_lane1_speculation() || any;
+    }
+    if (any && lane0_accepted) ++c.twin_eigen_stats[2];
+  }
   volatile int* flag = c.h_flag + 1;
   const auto t_start = std::chrono::steady_clock::now();
   long spins = 0;
@@ -583,6 +593,14 @@ int icp_ctx_twin_stats(icp_ctx* ctx, int64_t out[3]) {
   });
 }
 
+int icp_ctx_twin_eigen_stats(icp_ctx* ctx, int64_t out[4]) {
+  return guard([&] {
+    require(ctx && out, "null argument");
+    std::lock_guard<std::recursive_mutex> lk(ctx->mu);
+    for (int i = 0; i < 4; ++i) out[i] = ctx->twin_eigen_stats[i];
+  });
+}
+
 int icp_chain_step(icp_evaluator* e, int32_t n_props, icp_proposal* const* props, int32_t generator, const double* theta_cur,
                    const double* z, double* theta_prop, double* log_value_prop, double* fwd, double* bwd) {
   int status = ICP_OK;
@@ -606,7 +624,8 @@ int icp_chain_step(icp_evaluator* e, int32_t n_props, icp_proposal* const* props
     // lane 1 of the twin pass whose lane 0 the previous call consumed: this is the step it was made for (lane 0 was rejected), or
     // it is dropped — and with it the front launched behind it, for a state the chain has left
     const bool lane1 = n_props <= 2 && front_matches(e->twin.F, n_props, props, generator, theta_cur, key, r);
-    if (e->twin.valid && !lane1) drop_twin(e);
+    if (e->twin.valid && !lane1)  // (lane 0 accepted: the caller's current state is what the previous step proposed)
+      drop_twin(e, !e->last_prop.empty() && std::memcmp(e->last_prop.data(), theta_cur, sizeof(double) * (10 + (size_t)r)) == 0);
     const bool reuse = !lane1 && n_props <= 2 && front_matches(e->front, n_props, props, generator, theta_cur, key, r);
     if (e->front.valid && !reuse && !lane1) drop_front(e);  // pre-launched for another outcome: dropped
     per_stage = !reuse && !lane1 && !chain_step_covered(e, n_props, props, generator, theta_cur, theta_prop);
@@ -619,7 +638,9 @@ int icp_chain_step(icp_evaluator* e, int32_t n_props, icp_proposal* const* props
     Bound _b(&c, true);
     g_host_timing.start();
 
-    for (int i = 0; i < n_props; ++i) props[i]->resolve_speculation(theta_cur);
+    bool kept_lane1 = false;
+    for (int i = 0; i < n_props; ++i) kept_lane1 = props[i]->resolve_speculation(theta_cur, lane1) || kept_lane1;
+    if (kept_lane1) ++c.twin_eigen_stats[1];
     if (!e->last_prop.empty() && !e->acc_counted) {  // did the caller keep the state the previous step proposed?
       const bool accepted = std::memcmp(e->last_prop.data(), theta_cur, sizeof(double) * (10 + (size_t)r)) == 0;
       e->acc_ema = 0.9 * e->acc_ema + (accepted ? 0.1 : 0.0);
@@ -633,8 +654,9 @@ int icp_chain_step(icp_evaluator* e, int32_t n_props, icp_proposal* const* props
     FrontGuard front1_guard{&F1};
     StepFinishArgs f{};
     int step_seq = 0;
+    bool lane1_eigen_out = false;  // lane 1's decomposition went out with lane 0's: nothing to start for it
     if (lane1) {  // launches 1-5 are out (or done): the previous call issued them
-      F = e->twin.F; f = e->twin.f; step_seq = e->twin.seq;
+      F = e->twin.F; f = e->twin.f; step_seq = e->twin.seq; lane1_eigen_out = e->twin.eigen_early;
       e->twin = TwinPending{};
     } else if (reuse) {
       F = e->front; e->front = StepFront{};
@@ -710,19 +732,43 @@ int icp_chain_step(icp_evaluator* e, int32_t n_props, icp_proposal* const* props
       }
     }
     // (lane 1: nothing to launch on the step streams.  Lane 0 was rejected, its speculative decomposition has just been cancelled —
-    // resolve_speculation above —, and lane 1's own goes out below: its input is complete)
+    // resolve_speculation above —, and lane 1's own has been on the eigen stream since the twin pass was finished; under
+    // ICP_TWIN_LATE_EIGEN, or where that call did not start it, it goes out below: its input is complete)
     g_host_timing.mark(1);
     // the caller's outcome-independent host work runs beside the device — first of all the pre-launch of the next step's
     // first half, which the device can start as soon as the finish launch above has
     // KL bases of the proposed state's posteriors, in case it is accepted: they run on the eigen stream beside the
     // factorisations and the host's round trip; the next call keeps or cancels them (resolve_speculation).  One launch (both
     // directions side by side), issued BEFORE the caller's hook: the accepted path waits for nothing else.
-    if (speculate) {
-      EigenSpec specs[2];
-      EigenRequest rqs[2];
-      for (int i = 0; i < n_props; ++i) props[i]->speculate_eigen(*ep[i], *ec[i], F.splits[i], F.mpart_half[i], c.d_done.p + 2, step_seq + starve, &specs[i], &rqs[i]);
+    if (lane1_eigen_out) {
+      // nothing: lane 1's decompositions are pending (icp_proposal::spec[0] now), the call after this one keeps or cancels them
+    } else if (speculate) {
+      EigenSpec specs[kEigenPairMax];
+      EigenRequest rqs[kEigenPairMax];
+      int nq = 0;
+      for (int i = 0; i < n_props; ++i, ++nq) props[i]->speculate_eigen(*ep[i], *ec[i], F.splits[i], F.mpart_half[i], c.d_done.p + 2, step_seq + starve, &specs[nq], &rqs[nq]);
+      // A twin pass: lane 1's as well, in the same launch — its normal matrix is as complete as lane 0's (the finish launch raises
+      // the one `ready` word behind both lanes' regressions), and a pass that ends "lane 0 rejected, lane 1 accepted" finds the
+      // basis a finish launch and a host turn-around earlier.  Lane 1 is used only behind a rejected lane 0: started here exactly
+      // where its own call would have started it (the acceptance estimate after that rejection), so that the places in the
+      // proposals' counts fall as they do one call at a time.  The Cholesky-root sampler keeps the late order.
+      bool early = twin && !lane1 && !c.twin_late_eigen && (spec_mode == 1 || 0.9 * e->acc_ema + 0.0 >= 0.1);
+      for (int i = 0; i < n_props; ++i) early = early && props[i]->sampler != ICP_SAMPLER_CHOLESKY_ROOT;
+      if (early) {
+        const StepFront& L1 = e->twin.F;
+        bool cold = false;
+        for (int i = 0; i < n_props; ++i, ++nq) {
+          const bool cold_place = props[i]->eig.ahead_cold();
+          props[i]->speculate_eigen(*L1.ep[i], *L1.ec[i], L1.splits[i], L1.mpart_half[i], c.d_done.p + 2, step_seq + starve, &specs[nq], &rqs[nq], 1);
+          cold = cold || cold_place;
+        }
+        e->twin.eigen_early = true;
+        ++c.twin_eigen_stats[0];
+        if (cold) ++c.twin_eigen_stats[3];
+      }
       const hipStream_t es = eigen_stream_for(c, c.eig_stream.get());
-      launch_posterior_eigen_pair(es, r, c.sqrt_lambda.p, n_props, rqs);  // (no event: completion words, see start_decompositions)
+      // (no event: completion words, see start_decompositions)
+      if (!launch_posterior_eigen_pair(es, r, c.sqrt_lambda.p, nq, rqs)) fail(ICP_ERR_DEVICE, "internal: no decomposition kernel for a speculative launch");
     } else if (plan_only) {
       for (int i = 0; i < n_props; ++i) props[i]->plan_eigen(*ep[i]);
     }

@@ -19,6 +19,7 @@
 #include <vector>
 
 #include "icp_kernels.hpp"
+#include "icp_eigen_count.hpp"
 
 using namespace icp;
 
@@ -472,6 +473,11 @@ struct icp_ctx {
   int* h_twin_status = nullptr;
   // icp_ctx_twin_stats: twin passes issued, lane-1 results used, lane-1 results dropped
   int64_t twin_stats[3] = {0, 0, 0};
+  // ICP_TWIN_LATE_EIGEN=1: lane 1's speculative decomposition goes out at its own call, not with lane 0's (A/B, tests)
+  bool twin_late_eigen = [] { const char* v = std::getenv("ICP_TWIN_LATE_EIGEN"); return v && v[0] && std::strcmp(v, "0") != 0; }();
+  // icp_ctx_twin_eigen_stats: lane-1 decompositions started with lane 0's, kept (lane 1 accepted), cancelled because lane 0 was
+  // accepted, started cold
+  int64_t twin_eigen_stats[4] = {0, 0, 0, 0};
   int step_seq = 0;
   std::vector<struct icp_evaluator*> evaluators;  // live evaluators (a proposal being destroyed drops their pending half steps)
   std::vector<struct icp_proposal*> proposals;    // live proposals (icp_ctx_set_rotation forgets what they memoised under a triple)

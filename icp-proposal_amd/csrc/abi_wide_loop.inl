@@ -276,7 +276,8 @@ void wide_loop_chain_records(const LoopRun& a, WideLoopChain& ch, WideLoopGroup&
     fw.out = gr.res.p + (size_t)k * 32 + 8 + 2 * i; fw.status = gr.stat.p + (size_t)k * 16 + 2 * i;
     bw.out = gr.res.p + (size_t)k * 32 + 9 + 2 * i; bw.status = gr.stat.p + (size_t)k * 16 + 2 * i + 1;
     mw.chol[i] = cap.factors[(size_t)k * n_props + i].status;
-    m.eig_seq[i] = p->eig_seq;
+    m.eig_seq[i] = p->eig.place;
+    p->eig.foreign_words_up_to(p->eig.place + a.n_steps);  // (as the merged loop: the words it may raise stay below the host's numbers)
   }
   m.wide = gr.wide.p + k;
   m.eig_live = gr.eig_rec.p + (size_t)k * n_props;
@@ -487,7 +488,7 @@ void wide_loop_forget(const LoopRun& a, WideLoopChain& ch, WideItem& w) {
     for (PosteriorEntry* en : {w.ec[i], w.ep[i]})
       if (en) en->off_record();
     ch.props[i]->warm_valid = false;
-    ch.props[i]->spec_entry = nullptr;
+    ch.props[i]->forget_speculation();
   }
   if (w.s) w.s->valid = false;
 }
@@ -526,8 +527,8 @@ void wide_loop_book(const LoopRun& a, std::vector<WideLoopChain>& chains, WideLo
       icp_proposal* p = ch.props[i];
       p->on_record(*w.ec[i], a.theta[b], a.P);
       w.ep[i]->off_record();
-      if (a.jacobi) p->eig_seq = hm[k].eig_seq[i];
-      p->spec_entry = nullptr;
+      p->forget_speculation();
+      if (a.jacobi) p->eig.place = hm[k].eig_seq[i];
     }
     w.s->valid = false;
     loop_count_steps(ch.e, a.n_steps);

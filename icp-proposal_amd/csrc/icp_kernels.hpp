@@ -269,7 +269,8 @@ constexpr int kEigenGaveUp = 3;  // pinned status of a speculative decomposition
 struct EigenSpec { int splits; const int* cancel; int seq; const int* ready; int ready_seq;
                    long long* wait_ticks = nullptr; /* profiling: 100 MHz ticks spent waiting for `ready` are added here */ };
 bool eigen_speculation_supported(int r);
-// up to two decompositions of the same rank in ONE launch (they run side by side); false: not available for this rank
+// up to two decompositions of the same rank in ONE launch (they run side by side) — up to kEigenPairMax = four for the two lanes of
+// a twin pass (not with `root`); false: not available for this rank / count (nothing launched)
 // done_word (optional): set to done_value (release, agent scope) when THIS decomposition's outputs are complete — or when it
 // gave up — so that a consumer on another stream can wait for one of the two without waiting for the whole launch
 struct EigenRequest { const double* M; const double* Vwarm; double* V; double* Vt; double* S; double* work; int* status;
@@ -277,6 +278,7 @@ struct EigenRequest { const double* M; const double* Vwarm; double* V; double* V
                       const double* sqrt_lambda = nullptr; /* of the request's own model; launch_posterior_eigen_many needs it */
                       bool root = false; /* write V := D·L⁻ᵀ (M = L·Lᵀ), S := 1 instead of the eigen-decomposition: the opt-in
                       Cholesky-root sampler (kernels_eigen.hip: k_posterior_root; ranks <= 64) */ };
+constexpr int kEigenPairMax = 4;
 bool launch_posterior_eigen_pair(hipStream_t st, int r, const double* sqrt_lambda, int n, const EigenRequest* rq);
 // one decomposition as the rank <= 64 kernels see it (EigenRequest resolved into the kernel's own pointers)
 struct EigenProblem {

@@ -581,8 +581,8 @@ constexpr int kRrPollWave = 13;           // … nor this one: a speculative dec
 constexpr int kRrLogLag = 8;              // the progress word trails the log wave's write-through stores by this many rounds
 template <int N> struct IntC { static constexpr int value = N; };
 
-// One launch decomposes up to two posteriors side by side (the two ICP directions of a chain step): problem p owns the
-// workgroups [p·per, (p+1)·per), the first of which iterates while the others replay.
+// One launch decomposes up to four posteriors side by side (the two ICP directions of a chain step; of both lanes of a twin pass:
+// EigenBatch<4>): problem p owns the workgroups [p·per, (p+1)·per), the first of which iterates while the others replay.
 // (struct EigenProblem: icp_kernels.hpp — the on-device chain loop patches these records in device memory)
 // The batch record.  EigenBatch<2>: the two directions of one chain step, by value in the kernel arguments.  EigenBatchMem: the
 // decompositions of a batch of chains (icp_chain_step_batched) — any number of them in ONE launch, the records read in place from
@@ -603,7 +603,7 @@ struct EigenBatchMem {
   }
   __device__ __forceinline__ bool skipped(int which) const { return skip != nullptr && skip[which] != 0; }
 };
-static_assert(sizeof(EigenBatch<2>) + 64 <= 4096, "the batch record must fit the kernel argument segment");
+static_assert(sizeof(EigenBatch<kEigenPairMax>) + 64 <= 4096, "the batch record must fit the kernel argument segment");
 
 template <class Batch>
 __global__ void __launch_bounds__(1024) k_posterior_eigen_rr(int r, const double* __restrict__ sqrt_lambda_launch, int ldk, int max_sweeps,
@@ -1708,15 +1708,18 @@ void launch_root_batch(hipStream_t st, int r, int n, const Batch& batch) {
 
 bool launch_posterior_eigen_pair(hipStream_t st, int r, const double* sqrt_lambda, int n, const EigenRequest* rq) {
   static const bool force_generic = dev_env("ICP_EIGEN_GENERIC") != nullptr;
-  if (!(r >= 3 && r <= 64 && !force_generic) || n < 1 || n > 2) return false;
+  if (!(r >= 3 && r <= 64 && !force_generic) || n < 1 || n > kEigenPairMax) return false;
   if (rq[0].root) {  // the Cholesky-root sampler (icp_proposal_set_sampler): no decomposition at all
+    if (n > 2) return false;  // (its lanes are decomposed one call after the other)
     RootBatch2 b{};
     b.n = n;
     for (int i = 0; i < n; ++i) b.p[i] = eigen_rr_problem(r, rq[i]);
     launch_root_batch(st, r, n, b);
     return true;
   }
-  launch_eigen_rr<2>(st, r, sqrt_lambda, n, rq);  // (the warm-started iteration; a direct route at these ranks was measured and lost: DESIGN.md §11)
+  // (the warm-started iteration; a direct route at these ranks was measured and lost: DESIGN.md §11)
+  if (n <= 2) launch_eigen_rr<2>(st, r, sqrt_lambda, n, rq);
+  else launch_eigen_rr<kEigenPairMax>(st, r, sqrt_lambda, n, rq);  // both lanes of a twin pass: the same bodies, a longer record
   return true;
 }
 

@@ -463,6 +463,10 @@ ICP_API int icp_chain_step_prelaunch2(icp_evaluator *e, int32_t n_props, icp_pro
                                       const double *z_or_theta_prop2, int32_t *lanes_issued);
 /* out: twin passes issued, second-lane results used, second-lane results dropped (icp_chain_step_prelaunch2) */
 ICP_API int icp_ctx_twin_stats(icp_ctx *ctx, int64_t out[3]);
+/* The speculative decompositions of a twin pass's second lane go out with the first lane's, in one launch (ranks <= 64, the eigen
+ * sampler; ICP_TWIN_LATE_EIGEN=1 in the environment — any value but empty or 0 —: at the second lane's own call, as before).  out: second-lane decompositions
+ * started early, kept (the second lane's proposal was accepted), cancelled because the first lane's was accepted, started cold. */
+ICP_API int icp_ctx_twin_eigen_stats(icp_ctx *ctx, int64_t out[4]);
 
 /* B chains per launch (SURVEY.md §8b "*_batched variants", §8e "within a GPU, batch B chains per launch"; the
  * reference runs its chains from a ForkJoin pool, apps/femur/RunMHRandomInitComparison.scala:66): icp_chain_step for

@@ -7,9 +7,13 @@ finish launches (a step's first launch is the last one that started before its f
 step have no finish launch and are left out).  With one finish launch per step (no twin passes) the records of the same command
 (bench.py --dump-outputs, column 1: accepted) tell rejected from accepted steps: the interval behind step k is a rejected step's
 if step k was rejected.  With twin passes a finish launch serves one or two steps: the intervals are tabulated by the kind of the
-launch they start at (twin or one-lane) instead.
+launch they start at (twin or one-lane) instead — and, given the records of EVERY step of the process (warm-up included) and the
+lengths of its runs, by the step that was served LAST from the launch: the steps are laid along the finish launches from the first
+one on (a twin launch serves lane 0 alone where lane 0 was accepted, lanes 0 and 1 where lane 0 was rejected: the lone chain's
+harness always asks for the step lane 1 was made for), which tells the intervals behind "lane 1 used and accepted" — the pass whose
+next first launch waits for lane 1's KL basis — from the others.
 
-usage: step_trace_gaps.py <kernel_trace.csv> [records.npy] [label]   (markdown on stdout)"""
+usage: step_trace_gaps.py <kernel_trace.csv> [records.npy] [label] [runs=<steps>,<steps>…]   (markdown on stdout)"""
 import bisect
 import csv
 import statistics
@@ -17,7 +21,8 @@ import sys
 
 rows = list(csv.DictReader(open(sys.argv[1])))
 records = sys.argv[2] if len(sys.argv) > 2 and sys.argv[2].endswith(".npy") else None
-label = sys.argv[-1] if len(sys.argv) > 2 and not sys.argv[-1].endswith(".npy") else "trace"
+labels = [a for a in sys.argv[2:] if not a.endswith(".npy") and not a.startswith("runs=")]
+label = labels[0] if labels else "trace"
 
 
 def spans(word):
@@ -68,6 +73,46 @@ for r in rows:
     if "k_step_" in nm:
         k = nm.split("k_step_")[1].split("(")[0].split("<")[0]
         names.setdefault(k, []).append((int(r["End_Timestamp"]) - int(r["Start_Timestamp"])) / 1e3)
+
+
+def lay_steps(acc, runs):
+    """-> {finish index: kind of the step served last from it}, or None where steps and launches do not come out even.  Forwards
+    from the first launch: a twin launch serves lane 0 alone where lane 0 was accepted (or was the last step of its run: what is
+    launched ahead is dropped there), lanes 0 and 1 where lane 0 was rejected."""
+    ends, e = set(), 0
+    for r in runs:
+        e += r
+        ends.add(e - 1)
+    served, k = {}, 0
+    for j, f in enumerate(finish):
+        if k >= len(acc):
+            return None
+        if not f[2]:
+            served[j] = "one-lane, " + ("accepted" if acc[k] else "rejected")
+        elif acc[k] or k in ends:
+            served[j] = "twin, lane 0 " + ("accepted" if acc[k] else "rejected (end of a run)")
+        else:
+            k += 1
+            served[j] = "twin, lane 1 used and " + ("accepted" if acc[k] else "rejected")
+        k += 1
+    return served if k == len(acc) else None
+
+
+runs = [a for a in sys.argv[3:] if a.startswith("runs=")]
+if len(sys.argv) > 2 and sys.argv[2].endswith(".npy") and runs and any(f[2] for f in finish):
+    import numpy as np
+    served = lay_steps(list(np.load(sys.argv[2])[:, 1] != 0), [int(v) for v in runs[0][5:].split(",")])
+    if served is None:
+        print("\n(the records do not fit the finish launches: no table by the step served last)")
+    else:
+        by = {}
+        for j, what in served.items():
+            if j + 1 < n:
+                by.setdefault(what, []).append((finish[j + 1][0] - finish[j][0]) / 1e3)
+        print("\n| finish start -> next finish start (us), by the step served last from the launch | count | median | p10 | p90 | mean |")
+        print("|---|---:|---:|---:|---:|---:|")
+        for key in sorted(by):
+            print(line(key, by[key]))
 print("\n| launch | calls | avg us | median us |")
 print("|---|---:|---:|---:|")
 for k in sorted(names):
