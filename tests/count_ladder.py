@@ -11,7 +11,7 @@ compares: a change of the dispatch code that moves an edge has to move the resta
 
 Out of scope: what belongs to the `*_many` entry points alone (metrics, registration maps, projection slabs, gp models, batched fits:
 met_cand / eval_cand, filter_grid_blocks over many items, regression_fold and regression_macro, which fold only when a launch carries
-many posteriors).
+many posteriors).  tests/batched_count_ladder.py ladders that family.
 
 Readings of the code that differ from the obvious one:
  * the stride of a candidate list does NOT depend on a context's history.  query_scratch only grows the scratch, but it grows it to

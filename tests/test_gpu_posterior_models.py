@@ -76,6 +76,7 @@ def check_against_long_form(model, res, ids, y, sigma2, cov, tag):
     assert np.all(np.diff(res["variance"]) <= 0), tag
     for k, (err, tol) in figures.items():
         assert err <= tol, (tag, k, err)
+    return figures
 
 
 # ---------------------------------------------------------------- 1. the long form

@@ -18,6 +18,7 @@ CHUNK_DOUBLES = 8 << 20
 SAMPLE_RECORD_BYTES = 144   # sizeof(InstanceItem): coefficient pointer, Pose (16 doubles), mesh pointer
 GROUP_RECORD_BYTES = 48     # sizeof(InstanceGroup); kInstGroup = 8 samples a group
 SIZES = (2, 3, 25, 41, 12)  # samples per map of the mixed batches
+ORACLE_REL = 1e-12          # of the map's maximum: the bound tests/test_gpu_fit.py holds the one-map entry to
 
 
 def sample_set(model, seed, n, scale=0.3):
@@ -64,8 +65,8 @@ def test_bits_against_one_map_entry_and_oracle(pkg, oracle, femur50, femur50_ora
         assert np.array_equal(g, one_map(pkg, ctx, th, mode, ref))
         want = oracle.posterior_variability(om, th, mode=mode, theta_ref=ref)
         err = np.abs(g - want).max()
-        print(f"mode {mode} S {th.shape[0]}: |map - oracle| = {err:.3e}, bound {1e-12 * np.abs(want).max():.3e}")
-        assert err <= 1e-12 * np.abs(want).max()
+        print(f"mode {mode} S {th.shape[0]}: |map - oracle| = {err:.3e}, bound {ORACLE_REL * np.abs(want).max():.3e}")
+        assert err <= ORACLE_REL * np.abs(want).max()
         x = np.stack([ctx.transformedMesh(t) for t in th])
         assert np.abs(mu - x.mean(axis=0)).max() <= 1e-12 * np.abs(x).max()
     ctx.close()
