@@ -3,6 +3,14 @@
 // icp_proposal_basis_state
 extern "C" {
 
+// B chains per launch.  Every chain takes the merged step of icp_chain_step with its own context's buffers; the five
+// launches are recorded per chain (StepCapture) and issued ONCE for all of them on the first chain's stream, the
+// decompositions of chains that moved run on their own contexts' eigen streams beside it (launch 1 waits for each on the
+// device, as in the single-chain step).  Chains this does not cover (another device or rank than the first chain's, a
+// context that already has a chain in the batch, a configuration the merged launches do not cover) take icp_chain_step
+// one after the other, behind the batch.
+// The work is split in two so that a caller can keep two batches in flight (the decompositions of one run beside the
+// launches of the other): _issue ends when everything is on the device, _collect waits and records.
 int icp_chain_step_batched_issue(int32_t n_chains, icp_evaluator* const* evaluators, int32_t n_props, icp_proposal* const* props,
                                  const int32_t* generator, const double* const* theta_cur_in, const double* const* z_in,
                                  double* const* theta_prop_in, double* log_value_prop, double* fwd, double* bwd, int32_t* status,
@@ -35,16 +43,8 @@ int icp_chain_step_batched_issue(int32_t n_chains, icp_evaluator* const* evaluat
       it.props = t.props.data() + (size_t)b * n_props;
       it.generator = generator[b];
       require(it.e && theta_cur[b] && theta_prop[b], "null argument");
-      require(it.generator < n_props, "generator index out of range");
-      require(it.generator < 0 || (z && z[b]), "z is null");
-      icp_ctx& c = *it.e->ctx;
-      for (int i = 0; i < n_props; ++i) require(it.props[i] && it.props[i]->ctx == &c, "proposal belongs to another context");
-      check_theta_finite(&c, theta_cur[b]);
-      if (it.generator < 0) check_theta_finite(&c, theta_prop[b]);
-      else
-        for (int j = 0; j < c.r; ++j)
-          if (!std::isfinite(z[b][j])) fail(ICP_ERR_NOT_FINITE, "z contains a non-finite value");
-      it.key = it.generator >= 0 ? z[b] : theta_prop[b];
+      it.key = it.generator < 0 ? theta_prop[b] : z ? z[b] : nullptr;
+      check_step_args(*it.e->ctx, n_props, it.props, it.generator, theta_cur[b], it.key);
       status[b] = ICP_OK;
     }
     // `lead` carries the launches (its stream, its argument buffers); the decompositions go to the first chain's eigen stream
@@ -159,7 +159,6 @@ int icp_chain_step_batched_issue(int32_t n_chains, icp_evaluator* const* evaluat
       Item& it = items[b];
       if (!it.batched) continue;
       icp_ctx& c = *it.e->ctx;
-      const int r = c.r;
       Bound _b(&c, true);
       for (int i = 0; i < n_props; ++i) it.props[i]->resolve_speculation(theta_cur[b]);
       bool other_work = c.stream_used_elsewhere;  // another entry point may still be busy on `stream` …
@@ -176,19 +175,7 @@ int icp_chain_step_batched_issue(int32_t n_chains, icp_evaluator* const* evaluat
       for (int i = 0; i < 16; ++i) c.h_res[i] = 0.0;
       for (int i = 0; i < 16; ++i) c.h_status[i] = 0;
       const int step_seq = ++c.step_seq;
-      StepFinishArgs& f = it.f;
-      f.n = n_props; f.r = r; f.Ginv = c.Ginv.p; f.sigma2 = kSigma2;
-      for (int i = 0; i < n_props; ++i) {
-        icp_proposal* p = it.props[i];
-        f.Mpart[i] = F.mpart[i]; f.splits[i] = F.splits[i];
-        f.M[i] = F.ep[i]->M.p; f.alpha[i] = F.ep[i]->alpha.p;
-        f.status[i] = p->status.p + F.ep[i]->status_off;
-        f.host_status[i] = c.h_status + 8 + i;
-        f.fwd[i] = TransitionTailIO{F.ec[i]->alpha.p, F.ec[i]->M.p, F.ec[i]->coeffs.p, F.ep[i]->coeffs.p, p->prm.step_length,
-                                    c.h_res + 8 + 2 * i, c.h_status + 2 * i};
-        f.bwd[i] = TransitionTailIO{F.ep[i]->alpha.p, F.ep[i]->M.p, F.ep[i]->coeffs.p, F.ec[i]->coeffs.p, p->prm.step_length,
-                                    c.h_res + 9 + 2 * i, c.h_status + 2 * i + 1};
-      }
+      StepFinishArgs f = step_finish_args(c, n_props, it.props, F, c.h_res, c.h_status);
       f.done_counter = c.d_done.p; f.host_flag = c.h_flag; f.seq = step_seq;
       f.ready_flag = c.d_done.p + 2;
       c.last_back_seq = step_seq;
@@ -263,13 +250,7 @@ int icp_chain_step_batched_collect(icp_step_ticket* tk) {
       icp_ctx& c = *it.e->ctx;
       it.lk = std::unique_lock<std::recursive_mutex>(c.mu);
       Bound _b(&c, true, true);
-      volatile int* flag = c.h_flag;
-      const auto t_start = std::chrono::steady_clock::now();
-      long spins = 0;
-      while (*flag != it.f.seq) {
-        if ((++spins & 0xFFFF) == 0 && std::chrono::steady_clock::now() - t_start > std::chrono::seconds(2)) break;
-      }
-      if (*flag != it.f.seq) {
+      if (!await_host_flag(c.h_flag, it.f.seq, std::chrono::seconds(2))) {
         HIP_OK(hipStreamSynchronize(lead.stream));
         if (t.finish_stream) HIP_OK(hipStreamSynchronize(t.finish_stream));
       }
@@ -310,16 +291,10 @@ int icp_chain_step_batched_collect(icp_step_ticket* tk) {
       icp_ctx& c = *it.e->ctx;
       it.lk = std::unique_lock<std::recursive_mutex>(c.mu);
       Bound _b(&c, true, true);
-      volatile int* flag = c.h_flag;
-      const auto t_start = std::chrono::steady_clock::now();
-      long spins = 0;
-      while (*flag != it.W.seq) {
-        if ((++spins & 0xFFFF) == 0 && std::chrono::steady_clock::now() - t_start > std::chrono::seconds(5)) break;
-      }
-      if (*flag != it.W.seq) {
+      if (!await_host_flag(c.h_flag, it.W.seq, std::chrono::seconds(5))) {
         for (hipStream_t ws : t.wide_streams)
           if (ws) HIP_OK(hipStreamSynchronize(ws));
-        if (*flag != it.W.seq) fail(ICP_ERR_DEVICE, "internal: a wide step's completion flag did not arrive");
+        if (*(volatile int*)c.h_flag != it.W.seq) fail(ICP_ERR_DEVICE, "internal: a wide step's completion flag did not arrive");
       }
       c.stage_used = 0;
       int st = ICP_OK;

@@ -118,30 +118,13 @@ void merged_loop_chain_records(const LoopRun& a, MergedLoopChain& ch, MergedLoop
     {
       struct CaptureScope { CaptureScope(StepCapture* cp) { step_capture(cp); } ~CaptureScope() { step_capture(nullptr); } } scope(&cap);
       front_launches(ch.e, n_props, ch.props, -1, zero_key.data(), F, true, false);
-      StepFinishArgs f{};
-      f.n = n_props; f.r = r; f.Ginv = c.Ginv.p; f.sigma2 = kSigma2;
-      for (int i = 0; i < n_props; ++i) {
-        icp_proposal* p = ch.props[i];
-        f.Mpart[i] = F.mpart[i]; f.splits[i] = F.splits[i];
-        f.M[i] = F.ep[i]->M.p; f.alpha[i] = F.ep[i]->alpha.p;
-        f.status[i] = p->status.p + F.ep[i]->status_off;
-        f.host_status[i] = gr.stat.p + (size_t)k * 16 + 8 + i;
-        f.fwd[i] = TransitionTailIO{F.ec[i]->alpha.p, F.ec[i]->M.p, F.ec[i]->coeffs.p, F.ep[i]->coeffs.p, p->prm.step_length,
-                                    gr.res.p + (size_t)k * 32 + 8 + 2 * i, gr.stat.p + (size_t)k * 16 + 2 * i};
-        f.bwd[i] = TransitionTailIO{F.ep[i]->alpha.p, F.ep[i]->M.p, F.ep[i]->coeffs.p, F.ec[i]->coeffs.p, p->prm.step_length,
-                                    gr.res.p + (size_t)k * 32 + 9 + 2 * i, gr.stat.p + (size_t)k * 16 + 2 * i + 1};
-      }
-      f.done_counter = c.d_done.p; f.host_flag = c.h_flag; f.seq = 0;
-      f.ready_flag = nullptr;
+      StepFinishArgs f = step_finish_args(c, n_props, ch.props, F, gr.res.p + (size_t)k * 32, gr.stat.p + (size_t)k * 16);
+      f.done_counter = c.d_done.p; f.host_flag = c.h_flag;  // (seq 0, no ready word: nobody waits for a step of the loop)
       launch_step_finish(c.stream, f);  // (captured; finalised by the launcher)
     }
     cap.begin.wait_flag = nullptr; cap.begin.wait2_flag = nullptr; cap.begin.wait_ticks = nullptr; cap.begin.hold_regs = 0;
     cap.regression.red_out = gr.res.p + (size_t)k * 32;  // (device memory instead of the context's pinned area)
-    {  // (launch 1's matvec layout: set by enqueue_front only when it knows the generator)
-      int t = 0;
-      while (t < 6 && (r << (t + 1)) <= 256 && (r >> (t + 1)) >= 8) ++t;
-      cap.begin.tpr_log2 = t;
-    }
+    cap.begin.tpr_log2 = matvec_tpr_log2(r, 256);  // (launch 1's matvec layout: front_launches sets it only when it knows the generator)
     const size_t row = (size_t)sel * B + k;
     hb[row] = cap.begin; hs[row] = cap.search; hr[row] = cap.regression; hf[row] = cap.finish;
     for (int q = 0; q < 5; ++q) gr.grid[q] = std::max(gr.grid[q], cap.grid[q]);
@@ -177,7 +160,7 @@ void merged_loop_chain_records(const LoopRun& a, MergedLoopChain& ch, MergedLoop
   m.eval_kind = ch.e->prm.kind == ICP_EVAL_INDEPENDENT_POINT_DISTANCE ? 0 : 2;
   m.coeff_prop = ch.slot->coeffs.p;
   m.red = gr.res.p + (size_t)k * 32;
-  m.chol_status = gr.stat.p + (size_t)k * 16 + 8;
+  m.chol_status = gr.stat.p + (size_t)k * 16 + kStatFactor;
   // (the loop counts on from the place and raises the completion words of the set's entries to the places it takes, at most one per
   // step: the host's numbers stay above them whatever becomes of the loop — booked, forgotten or failed)
   for (int i = 0; i < n_props; ++i) {

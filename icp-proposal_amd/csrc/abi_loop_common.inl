@@ -1,11 +1,27 @@
 // abi_loop_common.inl — part of icp_abi.hip (one translation unit; included there, in order).
 // What the two on-device MH loops (abi_wide_loop.inl: the wide step's; abi_device_loop.inl: the merged step's) share: a run's arguments
-// and their checks, the loop-independent part of an MhChain, a group's buffers, the feed of standard normals, the drain with its error
-// mapping and the hand-out of results.  Plain functions and small structs; what the loops do differently on purpose stays at their call
-// sites.  (A posterior entry that leaves or re-enters the record: PosteriorEntry::off_record, icp_proposal::on_record.)
+// and their checks, the loop-independent part of an MhChain, a group's buffers, the harness' standard normals and their feed, the drain with
+// its error mapping and the hand-out of results.  Plain functions and small structs; what the loops do differently on purpose stays at
+// their call sites.  (A posterior entry that leaves or re-enters the record: PosteriorEntry::off_record, icp_proposal::on_record.)
 namespace {
 
 constexpr int kLoopChunk = 64;  // steps per block of standard normals
+
+// StepRandom::normal of the C++ harness (host/icp_host.hpp; = orc_rng_normal of the oracle): Box–Muller over the counter-based uniforms
+inline uint64_t harness_splitmix64(uint64_t x) {
+  x += 0x9E3779B97F4A7C15ull;
+  x = (x ^ (x >> 30)) * 0xBF58476D1CE4E5B9ull;
+  x = (x ^ (x >> 27)) * 0x94D049BB133111EBull;
+  return x ^ (x >> 31);
+}
+inline double harness_uniform(uint64_t seed, uint64_t step, uint64_t lane) {
+  const uint64_t h = harness_splitmix64(harness_splitmix64(harness_splitmix64(seed) ^ (step * 0xD1342543DE82EF95ull)) ^ (lane * 0x2545F4914F6CDD1Dull));
+  return ((double)(h >> 11) + 0.5) * (1.0 / 9007199254740992.0);
+}
+inline double harness_normal(uint64_t seed, uint64_t step, uint64_t lane) {
+  const double u1 = harness_uniform(seed, step, 2 * lane + 1000), u2 = harness_uniform(seed, step, 2 * lane + 1001);
+  return std::sqrt(-2.0 * std::log(u1)) * std::cos(2.0 * M_PI * u2);
+}
 
 // the arguments of icp_chains_run_on_device and the constants both loops derive from them (loop_check_args)
 struct LoopRun {
@@ -121,8 +137,8 @@ void loop_fill_chain(MhChain& m, const LoopRun& a, const LoopGroup& gr, int k, c
   m.gauss_mean = ep.gauss_mean; m.gauss_sigma = ep.gauss_sigma;
   m.gauss_logn = std::log(std::sqrt(2.0 * M_PI)) + std::log(ep.gauss_sigma);
   m.exp_rate = ep.exp_rate; m.exp_lograte = std::log(ep.exp_rate);
-  m.tails = gr.res.p + (size_t)k * 32 + 8;
-  m.tail_status = gr.stat.p + (size_t)k * 16;
+  m.tails = gr.res.p + (size_t)k * 32 + kResTails;
+  m.tail_status = gr.stat.p + (size_t)k * 16 + kStatTails;
   // (normals: the two buffers are addressed through MhChain::normals / normals_first, re-pointed per block of steps: loop_feed_normals)
   m.normals = nullptr; m.normals_first = 0; m.normals_rows = 0;
   m.records = a.records && a.records[b] ? gr.rec.p + (size_t)k * a.n_steps * (4 + a.P) : nullptr;

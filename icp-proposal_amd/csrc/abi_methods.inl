@@ -598,6 +598,19 @@ int speculation_mode() {
   }();
   return mode;
 }
+// … and what it says at an acceptance estimate (the adaptive mode speculates unless next to nothing is being accepted)
+bool speculation_wanted(double acc_ema) {
+  const int mode = speculation_mode();
+  return mode == 1 || (mode == 2 && acc_ema >= 0.1);
+}
+// did the caller keep the state the previous step proposed (theta_cur is that state, bit for bit)?
+bool kept_last_proposal(const icp_evaluator* e, const double* theta_cur, int r) {
+  return !e->last_prop.empty() && std::memcmp(e->last_prop.data(), theta_cur, sizeof(double) * (10 + (size_t)r)) == 0;
+}
+// the chain's acceptance estimate, one step on (nothing before the chain's first step)
+void note_outcome(icp_evaluator* e, const double* theta_cur, int r) {
+  if (!e->last_prop.empty()) e->acc_ema = 0.9 * e->acc_ema + (kept_last_proposal(e, theta_cur, r) ? 0.1 : 0.0);
+}
 }  // namespace
 extern "C" {
 int icp_chain_eval_step(icp_evaluator* e, int32_t n_props, icp_proposal* const* props, const double* theta_cur,
@@ -620,13 +633,8 @@ int icp_chain_eval_step(icp_evaluator* e, int32_t n_props, icp_proposal* const* 
     // the posteriors go first and the proposed state's decomposition starts at once on the eigen stream, BESIDE the evaluator's
     // searches on this one — if the state is accepted, the next proposal finds its basis done or under way; if not, the work
     // was done on CUs nobody needed.  (Acceptance tracked as in the merged step; not worth it when next to nothing is accepted.)
-    if (!e->last_prop.empty()) {
-      const bool accepted = std::memcmp(e->last_prop.data(), theta_cur, sizeof(double) * (10 + (size_t)r)) == 0;
-      e->acc_ema = 0.9 * e->acc_ema + (accepted ? 0.1 : 0.0);
-    }
-    const int spec_mode = speculation_mode();
-    const bool spec_ok = r > 64 && n_props == 1 && need_eval && !c.speculation_off &&
-                         (spec_mode == 1 || (spec_mode == 2 && e->acc_ema >= 0.1));
+    note_outcome(e, theta_cur, r);
+    const bool spec_ok = r > 64 && n_props == 1 && need_eval && !c.speculation_off && speculation_wanted(e->acc_ema);
     const bool spec_big = spec_ok && shape_only;
     // a pose move changes the state too: if it is kept, the next ICP proposal draws from the posterior at the NEW state — which
     // nothing on this path computes (the transition probabilities across a pose change are zero).  Started here, ahead, it is

@@ -181,6 +181,12 @@ struct StepFront {
 constexpr int kCoeffArea = 512;  // doubles per half of that area (>= kMaxRank)
 constexpr int kReduceArea = 16 + 2 * kCoeffArea;  // pinned result of launch 4's likelihood reduction: 8 doubles per parity
 static_assert(icp_ctx::kTwinDoubles == kReduceArea + 16 + 8, "lane 1's pinned areas have the layout of lane 0's");
+// A step's result block (doubles) and status block (ints) — the context's pinned h_res / h_status, lane 1's h_twin / h_twin_status, a
+// loop chain's 32 doubles / 16 ints of device memory — as launch 5 fills them (step_finish_args) and chain_step_record and the decide
+// kernel read them: the evaluator's reductions in res[0..7], then per proposal i
+constexpr int kResTails = 8;    // res[kResTails + 2i] the forward, res[kResTails + 2i + 1] the backward transition tail
+constexpr int kStatTails = 0;   // st[kStatTails + 2i] / st[kStatTails + 2i + 1]: the tails' status
+constexpr int kStatFactor = 8;  // st[kStatFactor + i]: the factorisation's status
 // lane 1 of a twin pass whose lane 0 has been consumed: its finish launch is on the device (or done), its results are lane 1's
 // pinned areas; the next icp_chain_step takes them if it is the step they were made for, or drops them
 struct TwinPending {

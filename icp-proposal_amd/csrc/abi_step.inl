@@ -1,14 +1,75 @@
 // abi_step.inl — part of icp_abi.hip (one translation unit; included there, in order).
-// the merged step (five launches): fronts, speculative decompositions, icp_chain_step / _prelaunch
+// the merged step (five launches): what its entry points share (the poll of a pinned flag, the argument checks, launch 5's arguments over
+// a result block), fronts and speculative decompositions, icp_chain_step_prelaunch / _prelaunch2, and icp_chain_step as a sequence of
+// phases over one ChainStep
 namespace {
+
+// (the wide step: abi_wide.inl)
+bool wide_chain_covered(icp_evaluator* e, int n_props, icp_proposal* const* props, int generator, const double* theta_cur,
+                        const double* theta_prop_in);
 
 // posteriors the regression launch being prepared will carry over all its chains (set by the batched issuers around their per-chain
 // preparation; 1 for a lone chain): decides regression_fold
 thread_local int tl_regression_posteriors = 1;
 
+// Results and their completion flag are written into pinned memory by the kernels: the host polls the flag (≈ 4 µs less than a stream
+// synchronisation), looking at the clock once in 65,536 spins.  -> false: the flag has not shown `seq` within `limit` — the caller
+// synchronises its streams and lets them report what went wrong.
+bool await_host_flag(volatile int* flag, int seq, std::chrono::seconds limit) {
+  const auto t_start = std::chrono::steady_clock::now();
+  long spins = 0;
+  while (*flag != seq) {
+    if ((++spins & 0xFFFF) == 0 && std::chrono::steady_clock::now() - t_start > limit) return *flag == seq;
+  }
+  return true;
+}
+
+// The argument checks of a step, shared by icp_chain_step, the pre-launch (either key) and every chain of icp_chain_step_batched_issue.
+// key: z (generator >= 0) or the proposed state.  The order decides which status a list with several faults gets; the null checks and
+// the bound on n_props are the entry points' own, ahead of this.
+void check_step_args(const icp_ctx& c, int n_props, icp_proposal* const* props, int generator, const double* theta_cur, const double* key) {
+  require(generator < n_props, "generator index out of range");
+  require(generator < 0 || key, "z is null");
+  for (int i = 0; i < n_props; ++i) require(props[i] && props[i]->ctx == &c, "proposal belongs to another context");
+  check_theta_finite(&c, theta_cur);
+  if (generator < 0) check_theta_finite(&c, key);
+  else
+    for (int j = 0; j < c.r; ++j)
+      if (!std::isfinite(key[j])) fail(ICP_ERR_NOT_FINITE, "z contains a non-finite value");
+}
+
+// 5: factorisations + tails of front `F` over the result block `res` and the status block `st` (kResTails / kStatTails / kStatFactor: the
+// context's pinned areas, lane 1's, a loop chain's device memory).  The caller adds what is its own: done_counter, host_flag,
+// ready_flag, seq.
+StepFinishArgs step_finish_args(const icp_ctx& c, int n_props, icp_proposal* const* props, const StepFront& F, double* res, int* st) {
+  StepFinishArgs a{};
+  a.n = n_props; a.r = c.r; a.Ginv = c.Ginv.p; a.sigma2 = kSigma2;
+  for (int i = 0; i < n_props; ++i) {
+    icp_proposal* p = props[i];
+    PosteriorEntry* lc = F.ec[i];
+    PosteriorEntry* lp = F.ep[i];
+    a.Mpart[i] = F.mpart[i]; a.splits[i] = F.splits[i];
+    a.M[i] = lp->M.p; a.alpha[i] = lp->alpha.p;
+    a.status[i] = p->status.p + lp->status_off;
+    a.host_status[i] = st + kStatFactor + i;
+    a.fwd[i] = TransitionTailIO{lc->alpha.p, lc->M.p, lc->coeffs.p, lp->coeffs.p, p->prm.step_length, res + kResTails + 2 * i,
+                                st + kStatTails + 2 * i};
+    a.bwd[i] = TransitionTailIO{lp->alpha.p, lp->M.p, lp->coeffs.p, lc->coeffs.p, p->prm.step_length, res + kResTails + 2 * i + 1,
+                                st + kStatTails + 2 * i + 1};
+  }
+  return a;
+}
+
 // give back what a front holds without recording anything (its launches, if any, are harmless: they wrote to a state
 // slot and memo entries that nobody refers to, to the search scratch and to the hints, which may be stale by design)
-void release_front(StepFront& F);
+void release_front(StepFront& F) {
+  if (F.mate) { StepFront* m = F.mate; F.mate = nullptr; if (m->valid || m->s) release_front(*m); }
+  if (F.s) F.s->reserved = false;
+  for (int i = 0; i < F.n_props; ++i)
+    if (F.ep[i]) F.ep[i]->reserved = false;
+  if (F.valid && F.eigen_first_use && F.generator >= 0 && F.ec[F.generator]) F.ec[F.generator]->eig_checked = false;
+  F = StepFront{};
+}
 // A half step launched ahead for an outcome that did not happen.  Its launches may still be running — they write the search
 // scratch, the hints, a state slot and memo entries that the replacement is about to be given — so the step that replaces it
 // must be ordered behind it: it takes the dropped front's own stream (enqueue_front toggles the parity back), where stream
@@ -36,13 +97,7 @@ void drop_twin(icp_evaluator* e, bool lane0_accepted = false) {
     }
     if (any && lane0_accepted) ++c.twin_eigen_stats[2];
   }
-  volatile int* flag = c.h_flag + 1;
-  const auto t_start = std::chrono::steady_clock::now();
-  long spins = 0;
-  while (*flag != e->twin.seq) {
-    if ((++spins & 0xFFFF) == 0 && std::chrono::steady_clock::now() - t_start > std::chrono::seconds(2)) break;
-  }
-  if (*flag != e->twin.seq) (void)hipStreamSynchronize(e->twin.F.stream);
+  if (!await_host_flag(c.h_flag + 1, e->twin.seq, std::chrono::seconds(2))) (void)hipStreamSynchronize(e->twin.F.stream);
   release_front(e->twin.F);
   e->twin = TwinPending{};
   ++c.twin_stats[2];
@@ -55,14 +110,6 @@ void release_fronts(icp_evaluator* e) {
 bool fronts_use(const icp_evaluator* e, const icp_proposal* p) {
   return (e->front.valid && (e->front.props[0] == p || e->front.props[1] == p)) ||
          (e->twin.valid && (e->twin.F.props[0] == p || e->twin.F.props[1] == p));
-}
-void release_front(StepFront& F) {
-  if (F.mate) { StepFront* m = F.mate; F.mate = nullptr; if (m->valid || m->s) release_front(*m); }
-  if (F.s) F.s->reserved = false;
-  for (int i = 0; i < F.n_props; ++i)
-    if (F.ep[i]) F.ep[i]->reserved = false;
-  if (F.valid && F.eigen_first_use && F.generator >= 0 && F.ec[F.generator]) F.ec[F.generator]->eig_checked = false;
-  F = StepFront{};
 }
 
 // KL bases of a state's posteriors `ec` that are not on record yet: all of them are started now, in ONE launch on the eigen
@@ -148,94 +195,6 @@ void start_decompositions(icp_ctx& c, int n_props, icp_proposal* const* props, P
   for (int i = 0; i < nn; ++i) need[i]->eig_event_valid = true;
 }
 
-void front_launches(icp_evaluator* e, int n_props, icp_proposal* const* props, int generator, const double* key, StepFront& F, bool batched,
-                    bool two_streams);
-
-// launches 1-3 of the step (theta_cur --generator/key--> proposal); `key` = z or the proposed state (see StepFront)
-// (batched: the launches are being captured for icp_chain_step_batched — one stream, nothing to wait for on the device
-// but the decomposition)
-// F2 (with generator2 / key2): the step after it as well, from the same theta_cur, as lane 1 of a twin pass — ONE set of launches
-void enqueue_front(icp_evaluator* e, int n_props, icp_proposal* const* props, int generator, const double* theta_cur,
-                   const double* key, StepFront& F, bool batched = false, StepFront* F2 = nullptr, int generator2 = -1,
-                   const double* key2 = nullptr) {
-  icp_ctx& c = *e->ctx;
-  const int r = c.r;
-  F = StepFront{};
-  F.n_props = n_props; F.generator = generator;
-  for (int i = 0; i < n_props; ++i) F.props[i] = props[i];
-  F.theta_cur.assign(theta_cur, theta_cur + 10 + r);
-  F.key.assign(key, key + (generator >= 0 ? r : 10 + r));
-  F.parity = (e->front_parity ^= 1);
-  F.h_coeffs = c.h_res + 16 + F.parity * kCoeffArea;
-  F.h_reduce = c.h_res + kReduceArea + F.parity * 8;  // (its own half: the host may still be reading the previous step's)
-  if (F2) {
-    *F2 = F;
-    F2->lane = 1; F2->generator = generator2;
-    F2->key.assign(key2, key2 + (generator2 >= 0 ? r : 10 + r));
-    F2->h_coeffs = c.h_twin + 16 + F.parity * kCoeffArea;
-    F2->h_reduce = c.h_twin + kReduceArea + F.parity * 8;
-    F.mate = F2;  // (from here on lane 1 is released with lane 0)
-  }
-  // ---- cached side: posterior of the current state for every proposal (+ its KL basis for the generating one)
-  PosteriorEntry** ec = F.ec;
-  bool missing = false;
-  for (int i = 0; i < n_props; ++i) missing = missing || !props[i]->find_entry(theta_cur);
-  if (missing && c.front_stream_used) {  // the posteriors are computed on `stream` with the scratch a step in flight may still use
-    c.front_stream.sync();
-    c.front_stream_used = false;
-  }
-  for (int i = 0; i < n_props; ++i) ec[i] = &props[i]->posterior(theta_cur, false);  // NonRigidIcpProposal.scala:54,76
-  if (missing) c.stream_used_elsewhere = true;  // … and this step reads them
-  const bool m_in_flight = c.stream_used_elsewhere;  // `stream` may still be writing what the decompositions below read
-  const bool two_streams = !c.pipeline_off && !batched && device_side_waits_allowed();
-  F.stream = (F.parity && two_streams) ? c.front_stream.get() : c.stream;
-  if (F.stream == c.front_stream.peek()) {
-    if (c.stream_used_elsewhere) {  // another entry point has work on `stream` that this step may depend on: join once
-      HIP_OK(hipEventRecord(c.ev_join, c.stream));
-      HIP_OK(hipStreamWaitEvent(c.front_stream.get(), c.ev_join, 0));
-    }
-    c.front_stream_used = true;
-  }
-  c.stream_used_elsewhere = false;
-  start_decompositions(c, n_props, props, ec, m_in_flight);
-  if (F2) { F2->stream = F.stream; for (int i = 0; i < n_props; ++i) F2->ec[i] = ec[i]; }
-  // (per lane; two lanes that draw from the same basis: the first one fetches its status)
-  for (StepFront* L : {&F, F2}) {
-    if (!L || L->generator < 0) continue;
-    PosteriorEntry* g = ec[L->generator];
-    // (await_eigen on the front's stream: through the decomposition's own completion word when it has one — see launch 1)
-    if (g->done_value == 0 && g->eigen_event()) HIP_OK(hipStreamWaitEvent(F.stream, g->eigen_event(), 0));
-    L->eigen_first_use = !g->eig_checked;  // (possibly of an earlier prefetch or speculation): fetch its status
-    g->eig_checked = true;
-  }
-
-  // ---- new side: one state slot, one memo entry per proposal (and lane)
-  for (StepFront* L : {&F, F2}) {
-    if (!L) continue;
-    StateSlot& s = c.fresh_state();
-    s.reserved = true;
-    L->s = &s;
-    s.pose = c.pose_of(L->generator >= 0 ? theta_cur : L->key.data());
-    for (int i = 0; i < n_props; ++i) { L->ep[i] = &props[i]->fresh_entry(); L->ep[i]->reserved = true; }
-  }
-  if (!F2) {
-    front_launches(e, n_props, props, generator, key, F, batched, two_streams);
-  } else {
-    // both lanes' launches are captured (arguments finalised, grids known) and issued as one set
-    StepCapture caps[2];
-    struct CaptureGuard { ~CaptureGuard() { step_capture(nullptr); } } capture_guard;
-    step_capture(&caps[0]);
-    front_launches(e, n_props, props, generator, key, F, batched, two_streams);
-    step_capture(&caps[1]);
-    front_launches(e, n_props, props, generator2, key2, *F2, batched, two_streams);
-    step_capture(nullptr);
-    launch_step_twin_front(F.stream, caps[0], caps[1]);
-    F2->valid = true;
-    ++c.twin_stats[0];
-  }
-  F.valid = true;
-}
-
 // launches 1-4 of a merged step with every choice made: F.ec / F.ep (the posterior entries of the current and of the proposed state),
 // F.s (the proposed state's slot, its pose set), F.parity, F.stream.  enqueue_front above makes those choices from the memo; the
 // on-device chain loop (icp_chains_run_on_device) fixes them once per chain and captures the arguments.
@@ -300,9 +259,7 @@ void front_launches(icp_evaluator* e, int n_props, icp_proposal* const* props, i
     PosteriorEntry& g = *ec[generator];
     b.prop = ProposeIn{g.alpha.p, g.V.p, g.S.p, c.inv_sqrt_lambda.p, c.P.p, g.coeffs.p, nullptr, kSigma2,
                        props[generator]->prm.step_length, props[generator]->sampler == ICP_SAMPLER_CHOLESKY_ROOT};
-    int t = 0;
-    while (t < 6 && (r << (t + 1)) <= 256 && (r >> (t + 1)) >= 8) ++t;  // = matvec_tpr_log2(r, 256) of k_propose
-    b.tpr_log2 = t;
+    b.tpr_log2 = matvec_tpr_log2(r, 256);  // (as k_propose's)
   }
   b.n_out = 0;
   b.out[b.n_out++] = s.coeffs.p;
@@ -401,6 +358,91 @@ void front_launches(icp_evaluator* e, int n_props, icp_proposal* const* props, i
   }
 }
 
+// launches 1-3 of the step (theta_cur --generator/key--> proposal); `key` = z or the proposed state (see StepFront)
+// (batched: the launches are being captured for icp_chain_step_batched — one stream, nothing to wait for on the device
+// but the decomposition)
+// F2 (with generator2 / key2): the step after it as well, from the same theta_cur, as lane 1 of a twin pass — ONE set of launches
+void enqueue_front(icp_evaluator* e, int n_props, icp_proposal* const* props, int generator, const double* theta_cur,
+                   const double* key, StepFront& F, bool batched = false, StepFront* F2 = nullptr, int generator2 = -1,
+                   const double* key2 = nullptr) {
+  icp_ctx& c = *e->ctx;
+  const int r = c.r;
+  F = StepFront{};
+  F.n_props = n_props; F.generator = generator;
+  for (int i = 0; i < n_props; ++i) F.props[i] = props[i];
+  F.theta_cur.assign(theta_cur, theta_cur + 10 + r);
+  F.key.assign(key, key + (generator >= 0 ? r : 10 + r));
+  F.parity = (e->front_parity ^= 1);
+  F.h_coeffs = c.h_res + 16 + F.parity * kCoeffArea;
+  F.h_reduce = c.h_res + kReduceArea + F.parity * 8;  // (its own half: the host may still be reading the previous step's)
+  if (F2) {
+    *F2 = F;
+    F2->lane = 1; F2->generator = generator2;
+    F2->key.assign(key2, key2 + (generator2 >= 0 ? r : 10 + r));
+    F2->h_coeffs = c.h_twin + 16 + F.parity * kCoeffArea;
+    F2->h_reduce = c.h_twin + kReduceArea + F.parity * 8;
+    F.mate = F2;  // (from here on lane 1 is released with lane 0)
+  }
+  // ---- cached side: posterior of the current state for every proposal (+ its KL basis for the generating one)
+  PosteriorEntry** ec = F.ec;
+  bool missing = false;
+  for (int i = 0; i < n_props; ++i) missing = missing || !props[i]->find_entry(theta_cur);
+  if (missing && c.front_stream_used) {  // the posteriors are computed on `stream` with the scratch a step in flight may still use
+    c.front_stream.sync();
+    c.front_stream_used = false;
+  }
+  for (int i = 0; i < n_props; ++i) ec[i] = &props[i]->posterior(theta_cur, false);  // NonRigidIcpProposal.scala:54,76
+  if (missing) c.stream_used_elsewhere = true;  // … and this step reads them
+  const bool m_in_flight = c.stream_used_elsewhere;  // `stream` may still be writing what the decompositions below read
+  const bool two_streams = !c.pipeline_off && !batched && device_side_waits_allowed();
+  F.stream = (F.parity && two_streams) ? c.front_stream.get() : c.stream;
+  if (F.stream == c.front_stream.peek()) {
+    if (c.stream_used_elsewhere) {  // another entry point has work on `stream` that this step may depend on: join once
+      HIP_OK(hipEventRecord(c.ev_join, c.stream));
+      HIP_OK(hipStreamWaitEvent(c.front_stream.get(), c.ev_join, 0));
+    }
+    c.front_stream_used = true;
+  }
+  c.stream_used_elsewhere = false;
+  start_decompositions(c, n_props, props, ec, m_in_flight);
+  if (F2) { F2->stream = F.stream; for (int i = 0; i < n_props; ++i) F2->ec[i] = ec[i]; }
+  // (per lane; two lanes that draw from the same basis: the first one fetches its status)
+  for (StepFront* L : {&F, F2}) {
+    if (!L || L->generator < 0) continue;
+    PosteriorEntry* g = ec[L->generator];
+    // (await_eigen on the front's stream: through the decomposition's own completion word when it has one — see launch 1)
+    if (g->done_value == 0 && g->eigen_event()) HIP_OK(hipStreamWaitEvent(F.stream, g->eigen_event(), 0));
+    L->eigen_first_use = !g->eig_checked;  // (possibly of an earlier prefetch or speculation): fetch its status
+    g->eig_checked = true;
+  }
+
+  // ---- new side: one state slot, one memo entry per proposal (and lane)
+  for (StepFront* L : {&F, F2}) {
+    if (!L) continue;
+    StateSlot& s = c.fresh_state();
+    s.reserved = true;
+    L->s = &s;
+    s.pose = c.pose_of(L->generator >= 0 ? theta_cur : L->key.data());
+    for (int i = 0; i < n_props; ++i) { L->ep[i] = &props[i]->fresh_entry(); L->ep[i]->reserved = true; }
+  }
+  if (!F2) {
+    front_launches(e, n_props, props, generator, key, F, batched, two_streams);
+  } else {
+    // both lanes' launches are captured (arguments finalised, grids known) and issued as one set
+    StepCapture caps[2];
+    struct CaptureGuard { ~CaptureGuard() { step_capture(nullptr); } } capture_guard;
+    step_capture(&caps[0]);
+    front_launches(e, n_props, props, generator, key, F, batched, two_streams);
+    step_capture(&caps[1]);
+    front_launches(e, n_props, props, generator2, key2, *F2, batched, two_streams);
+    step_capture(nullptr);
+    launch_step_twin_front(F.stream, caps[0], caps[1]);
+    F2->valid = true;
+    ++c.twin_stats[0];
+  }
+  F.valid = true;
+}
+
 // Host side of a merged step whose results have arrived in the context's pinned memory: status of the decomposition it
 // drew from, the proposed state, the memo entries, the rare direct transition tail, likelihood and densities.
 // -> false: the step has to be done again (nothing of it has been recorded)
@@ -445,14 +487,14 @@ bool chain_step_record(icp_evaluator* e, int n_props, icp_proposal* const* props
     ep[i]->theta.assign(theta_prop, theta_prop + P);
     ep[i]->valid = true;
     ep[i]->stamp = ++p->clock;
-    p->h_status[ep[i]->status_off] = c.h_status[8 + i];
+    p->h_status[ep[i]->status_off] = c.h_status[kStatFactor + i];
     p->h_status[ep[i]->status_off + 1] = 0;
     p->h_status[ep[i]->status_off + 2] = 0;
     p->check_status(*ec[i]);
     p->check_status(*ep[i]);
   }
   for (int t = 0; t < 2 * n_props; ++t)
-    if (c.h_status[t] != 0) {  // rare: the fixed-point tail did not contract -> direct kernel
+    if (c.h_status[kStatTails + t] != 0) {  // rare: the fixed-point tail did not contract -> direct kernel
       std::vector<double> saved(c.h_res, c.h_res + 16);
       icp_proposal* p = props[t / 2];
       TransitionTailIO io = (t % 2 == 0) ? f.fwd[t / 2] : f.bwd[t / 2];
@@ -462,7 +504,7 @@ bool chain_step_record(icp_evaluator* e, int n_props, icp_proposal* const* props
       launch_transition_tail_direct(c.stream, r, io, c.G.p, kSigma2, p->work.p);
       c.finish(1, 64);
       if (c.h_status[32] != 0) fail(ICP_ERR_NOT_SPD, "G + sigma^2 M is not positive definite");
-      saved[8 + t] = c.h_res[0];
+      saved[kResTails + t] = c.h_res[0];
       std::memcpy(c.h_res, saved.data(), sizeof(double) * saved.size());
     }
   for (int i = 0; i < 8; ++i) c.h_res[i] = F.h_reduce[i];  // launch 4's reductions, where finish_eval looks
@@ -471,15 +513,12 @@ bool chain_step_record(icp_evaluator* e, int n_props, icp_proposal* const* props
   *log_value_prop = m->value;
   *status = m->status;
   for (int i = 0; i < n_props; ++i) {
-    fwd[i] = c.h_res[8 + 2 * i];
-    bwd[i] = c.h_res[9 + 2 * i];
+    fwd[i] = c.h_res[kResTails + 2 * i];
+    bwd[i] = c.h_res[kResTails + 2 * i + 1];
     if (std::isnan(fwd[i]) || std::isnan(bwd[i])) fail(ICP_ERR_NOT_FINITE, "NaN transition probability");
   }
   return true;
 }
-
-// ICP_SPECULATION: 0 never, 1 always, unset = adaptive (2): while the chain's running acceptance rate is high
-
 bool front_matches(const StepFront& F, int n_props, icp_proposal* const* props, int generator, const double* theta_cur,
                    const double* key, int r) {
   if (!F.valid || F.n_props != n_props || F.generator != generator) return false;
@@ -489,10 +528,7 @@ bool front_matches(const StepFront& F, int n_props, icp_proposal* const* props, 
          std::memcmp(F.key.data(), key, sizeof(double) * F.key.size()) == 0;
 }
 
-bool wide_chain_covered(icp_evaluator* e, int n_props, icp_proposal* const* props, int generator, const double* theta_cur,
-                        const double* theta_prop_in);  // (the wide step: further down)
-
-// shared argument checks of icp_chain_step and icp_chain_step_prelaunch; -> the merged launches cover this call
+// -> the merged launches cover this call (icp_chain_step, icp_chain_step_prelaunch and the batch ask before they issue anything)
 bool chain_step_covered(icp_evaluator* e, int n_props, icp_proposal* const* props, int generator, const double* theta_cur,
                         const double* theta_prop_in) {
   icp_ctx& c = *e->ctx;
@@ -526,18 +562,10 @@ int chain_step_prelaunch(icp_evaluator* e, int32_t n_props, icp_proposal* const*
   }
   require(theta_cur && key, "null argument");
   require(n_props >= 1 && n_props <= 2 && props, "bad proposal list");
-  require(generator < n_props && generator2 < n_props, "generator index out of range");
+  require(generator2 < n_props, "generator index out of range");  // (both generators ahead of everything else)
   icp_ctx& c = *e->ctx;
-  for (int i = 0; i < n_props; ++i) require(props[i] && props[i]->ctx == &c, "proposal belongs to another context");
-  check_theta_finite(&c, theta_cur);
-  auto check_key = [&](int g, const double* k) {
-    if (g < 0) check_theta_finite(&c, k);
-    else
-      for (int j = 0; j < c.r; ++j)
-        if (!std::isfinite(k[j])) fail(ICP_ERR_NOT_FINITE, "z contains a non-finite value");
-  };
-  check_key(generator, key);
-  if (key2) check_key(generator2, key2);
+  check_step_args(c, n_props, props, generator, theta_cur, key);
+  if (key2) check_step_args(c, n_props, props, generator2, theta_cur, key2);
   std::lock_guard<std::recursive_mutex> lk(c.mu);
   drop_front(e);
   if (c.pipeline_off) return 0;
@@ -565,6 +593,207 @@ int chain_step_prelaunch(icp_evaluator* e, int32_t n_props, icp_proposal* const*
     throw;
   }
   return twin ? 2 : 1;
+}
+
+// ---- icp_chain_step on the merged launches: phases over one ChainStep, called in order by the entry point below.  A step that is
+// lane 1 of the twin pass the previous call finished skips the finish launch and the speculation: both went out with lane 0's.
+struct ChainStep {
+  icp_evaluator* e; int n_props; icp_proposal* const* props; int generator; const double* theta_cur; const double* key;
+  double* theta_prop; double* log_value_prop; double* fwd; double* bwd;
+  icp_ctx& c;
+  const int r;
+  ChainStep(icp_evaluator* e_, int n_props_, icp_proposal* const* props_, int generator_, const double* theta_cur_, const double* key_,
+            double* theta_prop_, double* log_value_prop_, double* fwd_, double* bwd_)
+      : e(e_), n_props(n_props_), props(props_), generator(generator_), theta_cur(theta_cur_), key(key_), theta_prop(theta_prop_),
+        log_value_prop(log_value_prop_), fwd(fwd_), bwd(bwd_), c(*e_->ctx), r(c.r) {}
+  bool lane1 = false;  // the step is lane 1 of the pending twin pass: launches 1-5 are out (or done), the previous call issued them
+  bool reuse = false;  // the pre-launched front is this step's (asked by step_take_front only)
+  struct FrontGuard {  // whatever happens, the slots of this step are not left reserved
+    StepFront* f;
+    ~FrontGuard() { if (f) release_front(*f); }
+  };
+  StepFront F;
+  FrontGuard front_guard{&F};
+  StepFront F1;  // lane 1 of a twin front, until its finish launch is out
+  FrontGuard front1_guard{&F1};
+  StepFinishArgs f{};
+  int step_seq = 0;
+  bool lane1_eigen_out = false;  // lane 1's decomposition went out with lane 0's: nothing to start for it
+};
+
+// 1: where the step's front comes from.  Lane 1 of the twin pass whose lane 0 the previous call consumed: this is the step it was made
+// for (lane 0 was rejected), or it is dropped — and with it the front launched behind it, for a state the chain has left.
+// -> false: the merged launches do not cover the call (nothing launched ahead matches it either)
+bool step_classify(ChainStep& s) {
+  icp_evaluator* e = s.e;
+  s.lane1 = s.n_props <= 2 && front_matches(e->twin.F, s.n_props, s.props, s.generator, s.theta_cur, s.key, s.r);
+  if (e->twin.valid && !s.lane1)  // (lane 0 accepted: the caller's current state is what the previous step proposed)
+    drop_twin(e, kept_last_proposal(e, s.theta_cur, s.r));
+  s.reuse = !s.lane1 && s.n_props <= 2 && front_matches(e->front, s.n_props, s.props, s.generator, s.theta_cur, s.key, s.r);
+  if (e->front.valid && !s.reuse && !s.lane1) drop_front(e);  // pre-launched for another outcome: dropped
+  return s.reuse || s.lane1 || chain_step_covered(e, s.n_props, s.props, s.generator, s.theta_cur, s.theta_prop);
+}
+
+// 2: what the previous step left open — its speculative decompositions are kept or cancelled, its outcome enters the acceptance
+// estimate — and the front: lane 1's with its finish arguments, the pre-launched one (a twin front's lane 1 goes to F1), or issued now
+void step_take_front(ChainStep& s) {
+  icp_evaluator* e = s.e;
+  bool kept_lane1 = false;
+  for (int i = 0; i < s.n_props; ++i) kept_lane1 = s.props[i]->resolve_speculation(s.theta_cur, s.lane1) || kept_lane1;
+  if (kept_lane1) ++s.c.twin_eigen_stats[1];
+  if (!e->acc_counted) note_outcome(e, s.theta_cur, s.r);
+  if (s.lane1) {
+    s.F = std::move(e->twin.F); s.f = e->twin.f; s.step_seq = e->twin.seq; s.lane1_eigen_out = e->twin.eigen_early;
+    e->twin = TwinPending{};
+  } else if (s.reuse) {
+    s.F = std::move(e->front); e->front = StepFront{};
+    if (s.F.mate) { s.F1 = std::move(*s.F.mate); *s.F.mate = StepFront{}; s.F.mate = nullptr; }
+  } else {
+    enqueue_front(e, s.n_props, s.props, s.generator, s.theta_cur, s.key, s.F);
+  }
+}
+
+// 3 (not for a lane-1 step): the finish launch, results straight to pinned host memory.  A twin front: one launch for both lanes; lane 1
+// has result areas, a completion counter and a host flag of its own, so that this step's results are not held back by it, and stays
+// with the evaluator: the next call takes it, or drops it.
+void step_finish_launch(ChainStep& s) {
+  icp_ctx& c = s.c;
+  for (int i = 0; i < 16; ++i) c.h_res[i] = 0.0;
+  for (int i = 0; i < 16; ++i) c.h_status[i] = 0;
+  s.step_seq = ++c.step_seq;
+  s.f = step_finish_args(c, s.n_props, s.props, s.F, c.h_res, c.h_status);
+  s.f.seq = s.step_seq; s.f.done_counter = c.d_done.p; s.f.host_flag = c.h_flag;
+  s.f.ready_flag = c.d_done.p + 2;  // (speculative decompositions and the next step's first launches wait for it)
+  c.last_back_seq = s.step_seq;
+  if (!s.F1.valid) {
+    launch_step_finish(s.F.stream, s.f);
+    return;
+  }
+  for (int i = 0; i < 16; ++i) c.h_twin[i] = 0.0;
+  for (int i = 0; i < 16; ++i) c.h_twin_status[i] = 0;
+  StepFinishArgs f1 = step_finish_args(c, s.n_props, s.props, s.F1, c.h_twin, c.h_twin_status);
+  f1.seq = s.step_seq; f1.done_counter = c.d_done.p + 3; f1.host_flag = c.h_flag + 1;
+  launch_step_twin_finish(s.F.stream, s.f, f1);
+  TwinPending& tw = s.e->twin;
+  tw.F = std::move(s.F1); tw.f = f1; tw.seq = s.step_seq; tw.valid = true;
+  s.F1 = StepFront{};  // (its slots belong to the evaluator now)
+}
+
+// 4 (not where lane 1's decompositions went out with lane 0's: they are pending — icp_proposal::spec[0] now —, the call after this one
+// keeps or cancels them): KL bases of the proposed state's posteriors, in case it is accepted.  They run on the eigen stream beside the
+// factorisations and the host's round trip; the next call keeps or cancels them (resolve_speculation).  One launch (both directions
+// side by side), issued BEFORE the caller's hook: the accepted path waits for nothing else.
+// Adaptive (speculation_mode): an accepted step finds its basis ≈ 50 µs earlier; a rejected one has paid one launch for
+// nothing: ≈ 3 µs of host time, a few CUs — and the eigen stream, which the next decomposition shares, until the launch has
+// seen its cancel word.  The kernel looks at the word before it starts and every eight rounds (≈ 3 µs) of the iteration:
+// the launch behind a rejected step then starts 0-8 µs after its input (median; 13-25 µs when the word was looked at once
+// per sweep: profiles/spec_cancel_lag.md).  Worth it unless next to nothing is accepted (measured then: 8.3k against 7.4k
+// it/s over a chain's first 20 steps).
+// (A lane-1 step whose decomposition did not go out early — ICP_TWIN_LATE_EIGEN, or that call did not start it — starts it here: lane 0
+// was rejected, its own has just been cancelled, and lane 1's input is complete.)
+void step_speculate(ChainStep& s) {
+  icp_ctx& c = s.c;
+  icp_evaluator* e = s.e;
+  const int n_props = s.n_props, r = s.r;
+  // test hook: the speculative decompositions wait for a word that never comes, time out and are repeated
+  static const int starve = dev_env("ICP_TEST_STARVE_SPECULATION") ? (1 << 24) : 0;
+  if (c.speculation_off || g_live_contexts.load(std::memory_order_relaxed) > 2 || n_props <= 0 || !eigen_speculation_supported(r)) return;
+  if (!speculation_wanted(e->acc_ema)) {
+    // switched off where the default would speculate: the decompositions keep their places in the count (plan_eigen)
+    if (speculation_mode() == 0 && e->acc_ema >= 0.1)
+      for (int i = 0; i < n_props; ++i) s.props[i]->plan_eigen(*s.F.ep[i]);
+    return;
+  }
+  EigenSpec specs[kEigenPairMax];
+  EigenRequest rqs[kEigenPairMax];
+  int nq = 0;
+  for (int i = 0; i < n_props; ++i, ++nq)
+    s.props[i]->speculate_eigen(*s.F.ep[i], *s.F.ec[i], s.F.splits[i], s.F.mpart_half[i], c.d_done.p + 2, s.step_seq + starve, &specs[nq], &rqs[nq]);
+  // A twin pass just finished (lane 1 is with the evaluator): lane 1's as well, in the same launch — its normal matrix is as complete as
+  // lane 0's (the finish launch raises the one `ready` word behind both lanes' regressions), and a pass that ends "lane 0 rejected,
+  // lane 1 accepted" finds the basis a finish launch and a host turn-around earlier.  Lane 1 is used only behind a rejected lane 0:
+  // started here exactly where its own call would have started it (the acceptance estimate after that rejection), so that the places
+  // in the proposals' counts fall as they do one call at a time.  The Cholesky-root sampler keeps the late order.
+  bool early = e->twin.valid && !c.twin_late_eigen && speculation_wanted(0.9 * e->acc_ema + 0.0);
+  for (int i = 0; i < n_props; ++i) early = early && s.props[i]->sampler != ICP_SAMPLER_CHOLESKY_ROOT;
+  if (early) {
+    const StepFront& L1 = e->twin.F;
+    bool cold = false;
+    for (int i = 0; i < n_props; ++i, ++nq) {
+      const bool cold_place = s.props[i]->eig.ahead_cold();
+      s.props[i]->speculate_eigen(*L1.ep[i], *L1.ec[i], L1.splits[i], L1.mpart_half[i], c.d_done.p + 2, s.step_seq + starve, &specs[nq], &rqs[nq], 1);
+      cold = cold || cold_place;
+    }
+    e->twin.eigen_early = true;
+    ++c.twin_eigen_stats[0];
+    if (cold) ++c.twin_eigen_stats[3];
+  }
+  const hipStream_t es = eigen_stream_for(c, c.eig_stream.get());
+  // (no event: completion words, see start_decompositions)
+  if (!launch_posterior_eigen_pair(es, r, c.sqrt_lambda.p, nq, rqs)) fail(ICP_ERR_DEVICE, "internal: no decomposition kernel for a speculative launch");
+}
+
+// 5: the results.  The finish launch's flag in pinned memory (give up after 2 s and let the synchronisation report what went wrong), or,
+// where the decomposition the step drew from leaves its status in device memory only (ranks > 64), a synchronisation and a copy.  A
+// lane-1 step's results then go where lane 0's are looked for.
+void step_wait(ChainStep& s) {
+  icp_ctx& c = s.c;
+  const StepFront& F = s.F;
+  if (F.eigen_first_use && !eigen_speculation_supported(s.r)) {
+    if (F.stream != c.stream) HIP_OK(hipStreamSynchronize(F.stream));
+    sync_proposal_status_if(s.props[s.generator], true);
+    c.finish(0, 0);
+  } else {
+    if (!await_host_flag(s.f.host_flag, s.f.seq, std::chrono::seconds(2))) {
+      if (F.stream != c.stream) HIP_OK(hipStreamSynchronize(F.stream));
+      c.finish(0, 0);
+    }
+    c.stage_used = 0;
+  }
+  if (s.lane1) {
+    for (int i = 0; i < 16; ++i) c.h_res[i] = c.h_twin[i];
+    for (int i = 0; i < 16; ++i) c.h_status[i] = c.h_twin_status[i];
+  }
+}
+
+// 6 (c.h_wait_error: this path's only reader): a first launch did not see the word it waits for within 50 ms and went ahead unordered.
+// That is what a tool does that lets one kernel run at a time in an order of its own (rocprofv3 --pmc): drain everything, switch the
+// pipelining off for this context, and have the step done again — nothing of it has been recorded.  (The decomposition started or
+// planned for its proposed state is withdrawn first: the repeated step starts it again, in the same place of the count.)
+void step_first_launch_timed_out(ChainStep& s) {
+  icp_ctx& c = s.c;
+  for (int i = 0; i < s.n_props; ++i) s.props[i]->withdraw_speculation();
+  s.e->acc_counted = true;
+  HIP_OK(hipStreamSynchronize(c.stream));
+  c.front_stream.sync();  // (a half step launched ahead may time out here, too)
+  sync_eigen(c);
+  c.h_wait_error[0] = 0;
+  ++c.stats.wait_timeouts; ++g_runtime_stats.wait_timeouts;
+  if (c.pipeline_off) fail(ICP_ERR_DEVICE, "internal: a step's first launch timed out on its word");
+  c.pipeline_off = true;
+  ++c.stats.pipeline_fallbacks; ++g_runtime_stats.pipeline_fallbacks;
+  ++c.stats.step_redos; ++g_runtime_stats.step_redos;
+  release_fronts(s.e);  // (lane 1 of a twin pass included: nothing of either lane has been recorded)
+}
+
+// 7: bookkeeping with the results in hand (chain_step_record), the step's slots given back, counters.  -> false: the step has to be
+// done again
+bool step_record(ChainStep& s, int* status) {
+  icp_ctx& c = s.c;
+  icp_evaluator* e = s.e;
+  if (!chain_step_record(e, s.n_props, s.props, s.generator, s.theta_cur, s.F, s.f, s.theta_prop, s.log_value_prop, s.fwd, s.bwd, status)) {
+    ++c.stats.step_redos; ++g_runtime_stats.step_redos;
+    drop_twin(e);  // (lane 1 may have drawn from the same basis)
+    return false;
+  }
+  if (s.lane1) ++c.twin_stats[1];
+  s.F.s->reserved = false;
+  for (int i = 0; i < s.n_props; ++i) s.F.ep[i]->reserved = false;
+  s.front_guard.f = nullptr;
+  ++c.paths.n[0]; ++g_step_paths.n[0];
+  e->last_prop.assign(s.theta_prop, s.theta_prop + 10 + s.r);
+  e->acc_counted = false;
+  return true;
 }
 
 }  // namespace
@@ -609,232 +838,38 @@ int icp_chain_step(icp_evaluator* e, int32_t n_props, icp_proposal* const* props
   int rc = guard([&] {
     require(e && theta_cur && theta_prop && log_value_prop, "null argument");
     require(n_props >= 0 && n_props <= 8 && (n_props == 0 || (props && fwd && bwd)), "bad proposal list");
-    require(generator < n_props, "generator index out of range");
-    require(generator < 0 || z, "z is null");
     icp_ctx& c = *e->ctx;
-    for (int i = 0; i < n_props; ++i) require(props[i] && props[i]->ctx == &c, "proposal belongs to another context");
-    check_theta_finite(&c, theta_cur);
-    if (generator < 0) check_theta_finite(&c, theta_prop);
-    else
-      for (int j = 0; j < c.r; ++j)
-        if (!std::isfinite(z[j])) fail(ICP_ERR_NOT_FINITE, "z contains a non-finite value");
-    std::lock_guard<std::recursive_mutex> lk(c.mu);
-    const int r = c.r;
     const double* key = generator >= 0 ? z : theta_prop;
-    // lane 1 of the twin pass whose lane 0 the previous call consumed: this is the step it was made for (lane 0 was rejected), or
-    // it is dropped — and with it the front launched behind it, for a state the chain has left
-    const bool lane1 = n_props <= 2 && front_matches(e->twin.F, n_props, props, generator, theta_cur, key, r);
-    if (e->twin.valid && !lane1)  // (lane 0 accepted: the caller's current state is what the previous step proposed)
-      drop_twin(e, !e->last_prop.empty() && std::memcmp(e->last_prop.data(), theta_cur, sizeof(double) * (10 + (size_t)r)) == 0);
-    const bool reuse = !lane1 && n_props <= 2 && front_matches(e->front, n_props, props, generator, theta_cur, key, r);
-    if (e->front.valid && !reuse && !lane1) drop_front(e);  // pre-launched for another outcome: dropped
-    per_stage = !reuse && !lane1 && !chain_step_covered(e, n_props, props, generator, theta_cur, theta_prop);
-    if (per_stage) {
+    check_step_args(c, n_props, props, generator, theta_cur, key);
+    std::lock_guard<std::recursive_mutex> lk(c.mu);
+    ChainStep s{e, n_props, props, generator, theta_cur, key, theta_prop, log_value_prop, fwd, bwd};
+    if (!step_classify(s)) {
       // what the five merged launches do not cover as a configuration takes the wide step (a batch of one chain)
+      per_stage = true;
       wide = wide_depth < 2 && n_props >= 1 && n_props <= 2 && !step_pipeline_covers(e, n_props, props) &&
              wide_chain_covered(e, n_props, props, generator, theta_cur, theta_prop);
       return;
     }
     Bound _b(&c, true);
     g_host_timing.start();
-
-    bool kept_lane1 = false;
-    for (int i = 0; i < n_props; ++i) kept_lane1 = props[i]->resolve_speculation(theta_cur, lane1) || kept_lane1;
-    if (kept_lane1) ++c.twin_eigen_stats[1];
-    if (!e->last_prop.empty() && !e->acc_counted) {  // did the caller keep the state the previous step proposed?
-      const bool accepted = std::memcmp(e->last_prop.data(), theta_cur, sizeof(double) * (10 + (size_t)r)) == 0;
-      e->acc_ema = 0.9 * e->acc_ema + (accepted ? 0.1 : 0.0);
-    }
-    StepFront F;
-    struct FrontGuard {  // whatever happens below, the slots of this step are not left reserved
-      StepFront* f;
-      ~FrontGuard() { if (f) release_front(*f); }
-    } front_guard{&F};
-    StepFront F1;  // lane 1 of a twin front, until its finish launch is out
-    FrontGuard front1_guard{&F1};
-    StepFinishArgs f{};
-    int step_seq = 0;
-    bool lane1_eigen_out = false;  // lane 1's decomposition went out with lane 0's: nothing to start for it
-    if (lane1) {  // launches 1-5 are out (or done): the previous call issued them
-      F = e->twin.F; f = e->twin.f; step_seq = e->twin.seq; lane1_eigen_out = e->twin.eigen_early;
-      e->twin = TwinPending{};
-    } else if (reuse) {
-      F = e->front; e->front = StepFront{};
-      if (F.mate) { F1 = *F.mate; *F.mate = StepFront{}; F.mate = nullptr; }
-    } else {
-      enqueue_front(e, n_props, props, generator, theta_cur, key, F);
-    }
-    const bool twin = F1.valid;
+    step_take_front(s);
     g_host_timing.mark(0);
-    PosteriorEntry** ec = F.ec;
-    PosteriorEntry** ep = F.ep;
-    StateSlot& s = *F.s;
-    const bool eigen_first_use = F.eigen_first_use;
-    // the decompositions of ranks <= 64 leave their status in pinned memory themselves; the others need a copy
-    const bool eigen_status_pinned = eigen_speculation_supported(r);
-    const bool eigen_enqueued = eigen_first_use && !eigen_status_pinned;
-    if (!lane1) {
-      for (int i = 0; i < 16; ++i) c.h_res[i] = 0.0;
-      for (int i = 0; i < 16; ++i) c.h_status[i] = 0;
-    }
-
-    // Adaptive (speculation_mode): an accepted step finds its basis ≈ 50 µs earlier; a rejected one has paid one launch for
-    // nothing: ≈ 3 µs of host time, a few CUs — and the eigen stream, which the next decomposition shares, until the launch has
-    // seen its cancel word.  The kernel looks at the word before it starts and every eight rounds (≈ 3 µs) of the iteration:
-    // the launch behind a rejected step then starts 0-8 µs after its input (median; 13-25 µs when the word was looked at once
-    // per sweep: profiles/spec_cancel_lag.md).  Worth it unless next to nothing is accepted (measured then: 8.3k against 7.4k
-    // it/s over a chain's first 20 steps).
-    const int spec_mode = speculation_mode();
-    const bool spec_possible = !c.speculation_off && g_live_contexts.load(std::memory_order_relaxed) <= 2 && n_props > 0 &&
-                               eigen_speculation_supported(r);
-    const bool speculate = (spec_mode == 1 || (spec_mode == 2 && e->acc_ema >= 0.1)) && spec_possible;
-    // switched off where the default would speculate: the decompositions keep their places in the count (plan_eigen)
-    const bool plan_only = spec_mode == 0 && e->acc_ema >= 0.1 && spec_possible;
-    // test hook: the speculative decompositions wait for a word that never comes, time out and are repeated
-    static const int starve = dev_env("ICP_TEST_STARVE_SPECULATION") ? (1 << 24) : 0;
-
-    // 5: factorisations + tails (results go straight to pinned host memory: `res` / `st`, lane 1's into areas of its own)
-    auto finish_args = [&](const StepFront& L, double* res, int* st) {
-      StepFinishArgs a{};
-      a.n = n_props; a.r = r; a.Ginv = c.Ginv.p; a.sigma2 = kSigma2;
-      for (int i = 0; i < n_props; ++i) {
-        icp_proposal* p = props[i];
-        PosteriorEntry* lc = L.ec[i];
-        PosteriorEntry* lp = L.ep[i];
-        a.Mpart[i] = L.mpart[i]; a.splits[i] = L.splits[i];
-        a.M[i] = lp->M.p; a.alpha[i] = lp->alpha.p;
-        a.status[i] = p->status.p + lp->status_off;
-        a.host_status[i] = st + 8 + i;
-        a.fwd[i] = TransitionTailIO{lc->alpha.p, lc->M.p, lc->coeffs.p, lp->coeffs.p, p->prm.step_length, res + 8 + 2 * i, st + 2 * i};
-        a.bwd[i] = TransitionTailIO{lp->alpha.p, lp->M.p, lp->coeffs.p, lc->coeffs.p, p->prm.step_length, res + 9 + 2 * i, st + 2 * i + 1};
-      }
-      a.seq = step_seq;
-      return a;
-    };
-    if (!lane1) {
-      step_seq = ++c.step_seq;
-      f = finish_args(F, c.h_res, c.h_status);
-      f.done_counter = c.d_done.p; f.host_flag = c.h_flag;
-      f.ready_flag = c.d_done.p + 2;  // (speculative decompositions and the next step's first launches wait for it)
-      c.last_back_seq = step_seq;
-      if (twin) {
-        // one finish launch for both lanes; lane 1 has a completion counter and a host flag of its own, so that this step's
-        // results are not held back by it.  Lane 1 stays with the evaluator: the next call takes it, or drops it.
-        for (int i = 0; i < 16; ++i) c.h_twin[i] = 0.0;
-        for (int i = 0; i < 16; ++i) c.h_twin_status[i] = 0;
-        StepFinishArgs f1 = finish_args(F1, c.h_twin, c.h_twin_status);
-        f1.done_counter = c.d_done.p + 3; f1.host_flag = c.h_flag + 1;
-        launch_step_twin_finish(F.stream, f, f1);
-        e->twin.F = F1; e->twin.f = f1; e->twin.seq = step_seq; e->twin.valid = true;
-        F1 = StepFront{};  // (its slots belong to e->twin now)
-      } else {
-        launch_step_finish(F.stream, f);
-      }
-    }
-    // (lane 1: nothing to launch on the step streams.  Lane 0 was rejected, its speculative decomposition has just been cancelled —
-    // resolve_speculation above —, and lane 1's own has been on the eigen stream since the twin pass was finished; under
-    // ICP_TWIN_LATE_EIGEN, or where that call did not start it, it goes out below: its input is complete)
+    if (!s.lane1) step_finish_launch(s);
     g_host_timing.mark(1);
-    // the caller's outcome-independent host work runs beside the device — first of all the pre-launch of the next step's
-    // first half, which the device can start as soon as the finish launch above has
-    // KL bases of the proposed state's posteriors, in case it is accepted: they run on the eigen stream beside the
-    // factorisations and the host's round trip; the next call keeps or cancels them (resolve_speculation).  One launch (both
-    // directions side by side), issued BEFORE the caller's hook: the accepted path waits for nothing else.
-    if (lane1_eigen_out) {
-      // nothing: lane 1's decompositions are pending (icp_proposal::spec[0] now), the call after this one keeps or cancels them
-    } else if (speculate) {
-      EigenSpec specs[kEigenPairMax];
-      EigenRequest rqs[kEigenPairMax];
-      int nq = 0;
-      for (int i = 0; i < n_props; ++i, ++nq) props[i]->speculate_eigen(*ep[i], *ec[i], F.splits[i], F.mpart_half[i], c.d_done.p + 2, step_seq + starve, &specs[nq], &rqs[nq]);
-      // A twin pass: lane 1's as well, in the same launch — its normal matrix is as complete as lane 0's (the finish launch raises
-      // the one `ready` word behind both lanes' regressions), and a pass that ends "lane 0 rejected, lane 1 accepted" finds the
-      // basis a finish launch and a host turn-around earlier.  Lane 1 is used only behind a rejected lane 0: started here exactly
-      // where its own call would have started it (the acceptance estimate after that rejection), so that the places in the
-      // proposals' counts fall as they do one call at a time.  The Cholesky-root sampler keeps the late order.
-      bool early = twin && !lane1 && !c.twin_late_eigen && (spec_mode == 1 || 0.9 * e->acc_ema + 0.0 >= 0.1);
-      for (int i = 0; i < n_props; ++i) early = early && props[i]->sampler != ICP_SAMPLER_CHOLESKY_ROOT;
-      if (early) {
-        const StepFront& L1 = e->twin.F;
-        bool cold = false;
-        for (int i = 0; i < n_props; ++i, ++nq) {
-          const bool cold_place = props[i]->eig.ahead_cold();
-          props[i]->speculate_eigen(*L1.ep[i], *L1.ec[i], L1.splits[i], L1.mpart_half[i], c.d_done.p + 2, step_seq + starve, &specs[nq], &rqs[nq], 1);
-          cold = cold || cold_place;
-        }
-        e->twin.eigen_early = true;
-        ++c.twin_eigen_stats[0];
-        if (cold) ++c.twin_eigen_stats[3];
-      }
-      const hipStream_t es = eigen_stream_for(c, c.eig_stream.get());
-      // (no event: completion words, see start_decompositions)
-      if (!launch_posterior_eigen_pair(es, r, c.sqrt_lambda.p, nq, rqs)) fail(ICP_ERR_DEVICE, "internal: no decomposition kernel for a speculative launch");
-    } else if (plan_only) {
-      for (int i = 0; i < n_props; ++i) props[i]->plan_eigen(*ep[i]);
-    }
+    if (!s.lane1_eigen_out) step_speculate(s);
     // the caller's outcome-independent host work runs beside the device — first of all the pre-launch of the next step's
     // first half (under the rejection assumption), which the device can start as soon as the finish launch above has
     if (c.idle_fn) c.idle_fn(c.idle_arg);
     g_host_timing.mark(2);
-    if (eigen_enqueued) {
-      if (F.stream != c.stream) HIP_OK(hipStreamSynchronize(F.stream));
-      sync_proposal_status_if(props[generator], true);
-      c.finish(0, 0);
-    } else {
-      // results and flag are written into pinned memory by the kernels: poll the flag (≈ 4 µs less than a stream
-      // synchronisation); give up after 2 s and let the synchronisation report what went wrong
-      volatile int* flag = f.host_flag;
-      const auto t_start = std::chrono::steady_clock::now();
-      long spins = 0;
-      while (*flag != f.seq) {
-        if ((++spins & 0xFFFF) == 0 && std::chrono::steady_clock::now() - t_start > std::chrono::seconds(2)) break;
-      }
-      if (*flag != f.seq) {
-        if (F.stream != c.stream) HIP_OK(hipStreamSynchronize(F.stream));
-        c.finish(0, 0);
-      }
-      c.stage_used = 0;
-    }
-    if (lane1) {
-      for (int i = 0; i < 16; ++i) c.h_res[i] = c.h_twin[i];
-      for (int i = 0; i < 16; ++i) c.h_status[i] = c.h_twin_status[i];
-    }
-
-    // ---- bookkeeping with the results in hand
-    g_host_timing.mark_wait(eigen_first_use);
+    step_wait(s);
+    g_host_timing.mark_wait(s.F.eigen_first_use);
     if (c.h_wait_error[0]) {
-      // A first launch did not see the word it waits for within 50 ms and went ahead unordered.  That is what a tool does
-      // that lets one kernel run at a time in an order of its own (rocprofv3 --pmc): drain everything, switch the pipelining
-      // off for this context, and do the step again — nothing of it has been recorded.  (The decomposition started or planned
-      // for its proposed state is withdrawn first: the repeated step starts it again, in the same place of the count.)
-      for (int i = 0; i < n_props; ++i) props[i]->withdraw_speculation();
-      e->acc_counted = true;
-      HIP_OK(hipStreamSynchronize(c.stream));
-      c.front_stream.sync();  // (a half step launched ahead may time out here, too)
-      sync_eigen(c);
-      c.h_wait_error[0] = 0;
-      ++c.stats.wait_timeouts; ++g_runtime_stats.wait_timeouts;
-      if (c.pipeline_off) fail(ICP_ERR_DEVICE, "internal: a step's first launch timed out on its word");
-      c.pipeline_off = true;
-      ++c.stats.pipeline_fallbacks; ++g_runtime_stats.pipeline_fallbacks;
-      ++c.stats.step_redos; ++g_runtime_stats.step_redos;
-      release_fronts(e);  // (lane 1 of a twin pass included: nothing of either lane has been recorded)
+      step_first_launch_timed_out(s);
       redo = true;
       return;
     }
-    if (!chain_step_record(e, n_props, props, generator, theta_cur, F, f, theta_prop, log_value_prop, fwd, bwd, &status)) {
-      ++c.stats.step_redos; ++g_runtime_stats.step_redos;
-      drop_twin(e);  // (lane 1 may have drawn from the same basis)
-      redo = true;
-      return;
-    }
-    if (lane1) ++c.twin_stats[1];
-    s.reserved = false;
-    for (int i = 0; i < n_props; ++i) ep[i]->reserved = false;
-    front_guard.f = nullptr;
-    ++c.paths.n[0]; ++g_step_paths.n[0];
-    e->last_prop.assign(theta_prop, theta_prop + 10 + r);
-    e->acc_counted = false;
+    redo = !step_record(s, &status);
+    if (redo) return;
     g_host_timing.mark(4);
     g_host_timing.end();
   });
@@ -861,28 +896,4 @@ int icp_chain_step(icp_evaluator* e, int32_t n_props, icp_proposal* const* props
   return status;
 }
 
-// B chains per launch.  Every chain takes the merged step of icp_chain_step with its own context's buffers; the five
-// launches are recorded per chain (StepCapture) and issued ONCE for all of them on the first chain's stream, the
-// decompositions of chains that moved run on their own contexts' eigen streams beside it (launch 1 waits for each on the
-// device, as in the single-chain step).  Chains this does not cover (another device or rank than the first chain's, a
-// context that already has a chain in the batch, a configuration the merged launches do not cover) take icp_chain_step
-// one after the other, behind the batch.
-// The work is split in two so that a caller can keep two batches in flight (the decompositions of one run beside the
-// launches of the other): _issue ends when everything is on the device, _collect waits and records.
-} // extern "C" (helpers)
-
-// StepRandom::normal of the C++ harness (host/icp_host.hpp; = orc_rng_normal of the oracle): Box–Muller over the counter-based uniforms
-static inline uint64_t harness_splitmix64(uint64_t x) {
-  x += 0x9E3779B97F4A7C15ull;
-  x = (x ^ (x >> 30)) * 0xBF58476D1CE4E5B9ull;
-  x = (x ^ (x >> 27)) * 0x94D049BB133111EBull;
-  return x ^ (x >> 31);
-}
-static inline double harness_uniform(uint64_t seed, uint64_t step, uint64_t lane) {
-  const uint64_t h = harness_splitmix64(harness_splitmix64(harness_splitmix64(seed) ^ (step * 0xD1342543DE82EF95ull)) ^ (lane * 0x2545F4914F6CDD1Dull));
-  return ((double)(h >> 11) + 0.5) * (1.0 / 9007199254740992.0);
-}
-static inline double harness_normal(uint64_t seed, uint64_t step, uint64_t lane) {
-  const double u1 = harness_uniform(seed, step, 2 * lane + 1000), u2 = harness_uniform(seed, step, 2 * lane + 1001);
-  return std::sqrt(-2.0 * std::log(u1)) * std::cos(2.0 * M_PI * u2);
-}
+}  // extern "C"

@@ -233,7 +233,6 @@ void wide_issue(icp_step_ticket& t, icp_ctx& lead, icp_ctx& elead, WideCapture* 
   bool any_split = false;
   int inst_head_points = 0;  // (INT_MAX: some chain's main sequence reads the whole instance)
   const bool concurrent = t.items[idx[0]].e->prm.kind == ICP_EVAL_HAUSDORFF;  // (how a split step's two sequences are scheduled: below)
-  const int spec_mode = speculation_mode();
 
   for (int k = 0; k < nW; ++k) {
     BatchItem& it = t.items[idx[k]];
@@ -246,13 +245,10 @@ void wide_issue(icp_step_ticket& t, icp_ctx& lead, icp_ctx& elead, WideCapture* 
     Bound _b(&c, true, capture != nullptr);  // (a captured step belongs to a run that has claimed its contexts already)
     w = WideItem{};
     w.on = true;
-    if (!e->last_prop.empty() && !capture) {  // did the caller keep the state the previous step proposed?
-      const bool accepted = std::memcmp(e->last_prop.data(), theta_cur, sizeof(double) * (10 + (size_t)r)) == 0;
-      e->acc_ema = 0.9 * e->acc_ema + (accepted ? 0.1 : 0.0);
-    }
+    if (!capture) note_outcome(e, theta_cur, r);
     for (int i = 0; i < n_props; ++i) it.props[i]->resolve_speculation(theta_cur);  // (a merged step's speculation, if the chain changed paths)
     w.shape_only = generator >= 0 || pose_equal(theta_cur, theta_prop);
-    const bool spec = !capture && (spec_mode == 1 || (spec_mode == 2 && e->acc_ema >= 0.1)) && !c.speculation_off;
+    const bool spec = !capture && speculation_wanted(e->acc_ema) && !c.speculation_off;
     // a pose move changes the state too: if it is kept, the next ICP proposal draws from the posterior at the NEW state, which
     // nothing else on this path would compute (the transition densities across a pose change are −∞): started here, ahead
     w.do_post = w.shape_only || spec;

@@ -23,9 +23,9 @@
 #include "abi_registration_maps.inl"  // C ABI: icp_registration_maps_many / icp_distance_summaries_many (per-vertex registration maps and chain summaries, kernels_maps.hip)
 #include "abi_posterior_models.inl"  // C ABI: icp_posterior_models_many (posterior shape models of given correspondences, kernels_posterior_model.hip)
 #include "abi_gp_models.inl"  // C ABI: icp_gp_models_many (Gaussian-process shape models from analytic kernels by pivoted Cholesky, kernels_gp_model.hip)
-#include "abi_step.inl"  // the merged step (five launches): fronts, speculative decompositions, icp_chain_step / _prelaunch
+#include "abi_step.inl"  // the merged step (five launches): flag poll, argument checks and finish arguments its entry points share; fronts, speculative decompositions, icp_chain_step_prelaunch; icp_chain_step in phases
 #include "abi_wide.inl"  // the wide step's host side (kernels_wide.hip)
 #include "abi_batched.inl"  // C ABI: icp_chain_step_batched (_issue / _collect / _abandon), icp_chain_step_path, icp_proposal_basis_state
-#include "abi_loop_common.inl"  // what the two on-device MH loops below share: arguments and checks, the MhChain fill, a group's buffers, normals feed, drain and hand-out
+#include "abi_loop_common.inl"  // what the two on-device MH loops below share: arguments and checks, the MhChain fill, a group's buffers, the harness' normals and their feed, drain and hand-out
 #include "abi_wide_loop.inl"  // the whole MH loop on the device for chains whose step is the wide one
 #include "abi_device_loop.inl"  // C ABI: icp_chains_run_on_device (the whole MH loop on the device: the merged step's loop, dispatch to the wide one)

@@ -567,12 +567,7 @@ static inline __device__ void block_matvec_lds(int r, int offA, int lda, const d
   __syncthreads();
 }
 
-// threads per row for block_matvec: enough rows in flight to occupy the block, at least ~8 terms per thread
-static inline int matvec_tpr_log2(int r, int block) {
-  int t = 0;
-  while (t < 6 && (r << (t + 1)) <= block && (r >> (t + 1)) >= 8) ++t;
-  return t;
-}
+// (threads per row: matvec_tpr_log2, icp_kernels.hpp — the host chooses it, for the launch arguments too)
 
 // copy a row-major r×r matrix into LDS with leading dimension ld
 static inline __device__ void stage_matrix(int r, const double* __restrict__ src, double* dst, int ld) {

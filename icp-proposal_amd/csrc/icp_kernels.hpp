@@ -352,6 +352,13 @@ constexpr int kStepBeginPoints = 128;  // model points per workgroup of the firs
 constexpr int kStepInlineZ = 128;  // ranks up to this pass the r host-drawn numbers inside the kernel arguments
 constexpr int kStepMaxOut = 6;
 
+// threads per row for block_matvec (icp_dense.hpp): enough rows in flight to occupy the block, at least ~8 terms per thread
+static inline int matvec_tpr_log2(int r, int block) {
+  int t = 0;
+  while (t < 6 && (r << (t + 1)) <= block && (r >> (t + 1)) >= 8) ++t;
+  return t;
+}
+
 struct StepBeginArgs {  // launch 1: [propose] -> coefficients -> instance -> search initialisation
   int N, r, inst_blocks, tpr_log2;
   // Consecutive steps alternate between two streams, so the first four launches of a step run beside the last launch of

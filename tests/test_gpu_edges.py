@@ -15,7 +15,7 @@ from conftest import make_theta, open_patch_target
 pytestmark = pytest.mark.gpu
 
 REL = 1e-9
-ICP_ERR_EMPTY = -5  # include/icp_proposal.h
+ICP_ERR_INVALID_ARG, ICP_ERR_NOT_FINITE, ICP_ERR_EMPTY = -1, -3, -5  # include/icp_proposal.h
 
 
 def rel_err(a, b):
@@ -30,6 +30,121 @@ def check_posterior(post, po):
     assert rel_err(post.M, po.M) < REL
     assert rel_err(post.alpha, po.alpha) < REL
     assert rel_err(post.S, po.S) < REL
+
+
+
+def _step_objects(pkg, ctx, target, r):
+    tp = pkg.data.decimated_point_subset(target, 2 * r)
+    props = [pkg.NonRigidIcpProposal(ctx, 0.1, 10.0, 5.0, 2 * r, pkg.TargetSampling, True, decimatedTargetPoints=tp),
+             pkg.NonRigidIcpProposal(ctx, 0.1, 10.0, 5.0, 2 * r, pkg.ModelSampling, True, decimatedTargetPoints=tp)]
+    ev = pkg.IndependentPointDistanceEvaluator(ctx, 0.0, 2.0, pkg.ModelToTargetEvaluation, 4 * r, decimatedTargetPoints=tp)
+    return ev, props
+
+
+def _step_draws(r, cur, k):
+    """Step k of the test's chain: generator (every fifth step a shape random walk, given as a state), its key, and whether the
+    proposal is kept (four in ten, whatever its value: accepted and rejected steps in a fixed pattern)."""
+    rng = np.random.default_rng([77, k])
+    g = -1 if k % 5 == 4 else k % 2
+    noise, keep = rng.normal(size=r), bool(rng.uniform() < 0.4)
+    if g >= 0:
+        return g, noise, keep
+    key = cur.copy()
+    key[10:] += 0.05 * noise
+    return g, key, keep
+
+
+def _advance(pkg, chain, n_steps):
+    """n_steps more steps through icp_chain_step, the next two proposals launched ahead before every step that has no
+    second-lane result waiting -> records [n_steps, 4 + P + 4]: step, accepted, generator, log value, proposed state, fwd, bwd."""
+    ev, props, r = chain["ev"], chain["props"], chain["r"]
+    records = []
+    for k in range(chain["k"], chain["k"] + n_steps):
+        cur = chain["cur"]
+        g, key, accepted = _step_draws(r, cur, k)
+        lanes = 0
+        if not chain["lane1_waiting"]:
+            g2, key2, _ = _step_draws(r, cur, k + 1)
+            lanes = pkg.chain_step_prelaunch2(ev, props, cur, g, key, g2, key2)
+        prop, lv, fwd, bwd = pkg.chain_step(ev, props, cur, g, z=key) if g >= 0 else pkg.chain_step(ev, props, cur, -1, theta_prop=key)
+        records.append(np.concatenate([[k, accepted, g, lv], prop, fwd, bwd]))
+        chain["lane1_waiting"] = lanes == 2 and not accepted
+        if accepted:
+            chain["cur"] = np.array(prop, dtype=np.float64)
+    chain["k"] += n_steps
+    return np.array(records)
+
+
+def _refused(pkg, call):
+    with pytest.raises(pkg._native.IcpNativeError) as e:
+        call()
+    return e.value.status
+
+
+def test_step_entry_points_refuse_bad_arguments(pkg, femur50):
+    """(First in this file: steps are launched ahead only while the process has one live context, before the fixtures below make theirs.)
+    icp_chain_step, icp_chain_step_prelaunch, icp_chain_step_prelaunch2 (the fault in its second key) and icp_chain_step_batched (the
+    fault in its second chain) refuse NaN in z, in theta_cur and in a given proposed state with ICP_ERR_NOT_FINITE, a generator index
+    equal to the proposal count and a proposal of another context with ICP_ERR_INVALID_ARG; a refused pre-launch issues no lane; and the
+    chain stepped on through the same objects has the records of a chain that never saw such a call, bit for bit."""
+    import ctypes as C
+    nat = pkg._native
+    model, target = femur50
+    r = model.rank
+
+    def new_chain():
+        ctx = pkg.IcpContext(model, target, device=0)
+        ev, props = _step_objects(pkg, ctx, target, r)
+        cur = make_theta(model, 77, shape_scale=0.2, pose=False)
+        return dict(ctx=ctx, ev=ev, props=props, r=r, cur=cur, k=0, lane1_waiting=False)
+
+    def close(chain):
+        print("twin passes", chain["ctx"].twin_stats())
+        chain["ev"].close(); [p.close() for p in chain["props"]]
+        chain["ctx"].close()
+
+    undisturbed = new_chain()
+    want = _advance(pkg, undisturbed, 36)
+    close(undisturbed)
+    print("accepted", int(want[:, 1].sum()), "of", len(want), "given states", int((want[:, 2] < 0).sum()))
+
+    chain = new_chain()
+    got_head = _advance(pkg, chain, 6)
+    ev, props, cur = chain["ev"], chain["props"], chain["cur"]
+    other = pkg.IcpContext(model, target, device=0)
+    ev2, props2 = _step_objects(pkg, other, target, r)
+    rng = np.random.default_rng(5)
+    z_good, z_bad = rng.normal(size=r), rng.normal(size=r)
+    z_bad[r // 2] = np.nan
+    cur_bad, prop_bad = cur.copy(), cur.copy()
+    cur_bad[12] = np.nan
+    prop_bad[10:] += 0.05 * z_good
+    prop_bad[10 + r - 1] = np.nan
+    # (name, this context's proposal list, the second context's, generator, theta_cur, key, status)
+    lists = [("NaN in z", props, props2, 0, cur, z_bad, ICP_ERR_NOT_FINITE),
+             ("NaN in theta_cur", props, props2, 0, cur_bad, z_good, ICP_ERR_NOT_FINITE),
+             ("NaN in a given theta_prop", props, props2, -1, cur, prop_bad, ICP_ERR_NOT_FINITE),
+             ("generator == n_props", props, props2, 2, cur, z_good, ICP_ERR_INVALID_ARG),
+             ("a proposal of another context", [props[0], props2[1]], [props2[0], props[1]], 0, cur, z_good, ICP_ERR_INVALID_ARG)]
+    for name, plist, plist2, g, tc, key, status in lists:
+        got = {}
+        got["icp_chain_step"] = _refused(pkg, lambda: pkg.chain_step(ev, plist, tc, g, z=key, theta_prop=key))
+        got["icp_chain_step_prelaunch"] = _refused(pkg, lambda: pkg.chain_step_prelaunch(ev, plist, tc, g, z=key, theta_prop=key))
+        arr = (C.c_void_p * 2)(*[p.h for p in plist])
+        lanes = C.c_int32(7)
+        d = lambda a: a.ctypes.data_as(nat.c_double_p)  # noqa: E731
+        got["icp_chain_step_prelaunch2"] = nat.lib().icp_chain_step_prelaunch2(ev.h, 2, arr, 0, d(tc), d(z_good), g, d(key), C.byref(lanes))
+        assert lanes.value == 0, (name, lanes.value)
+        got["icp_chain_step_batched"] = _refused(pkg, lambda: pkg.chain_step_batched([ev, ev2], [props, plist2], [cur, tc], [0, g],
+                                                                                z=[z_good, key], theta_prop=[None, key]))
+        print(name, got)
+        assert all(v == status for v in got.values()), (name, status, got)
+    ev2.close(); [p.close() for p in props2]
+    other.close()
+    got_tail = _advance(pkg, chain, 30)
+    close(chain)
+    assert np.array_equal(got_head, want[:6])
+    assert np.array_equal(got_tail, want[6:]), "records differing: %s" % np.nonzero((got_tail != want[6:]).any(axis=1))[0][:3]
 
 
 @pytest.fixture(scope="module")
