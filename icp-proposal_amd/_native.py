@@ -76,6 +76,11 @@ class KernelTermGeneral(C.Structure):
                 ("mirror_axis", C.c_int32), ("mirror_gain", C.c_double), ("A", C.c_double * 9), ("weights", c_double_p)]
 
 
+class ScanTransform(C.Structure):
+    _fields_ = [("struct_size", C.c_uint64), ("pre_scale", C.c_double), ("rotation", C.c_double * 9), ("centre", C.c_double * 3),
+                ("translation", C.c_double * 3)]
+
+
 # every symbol include/icp_proposal.h declares: name -> (restype, argtypes)
 SIGNATURES = {
     "icp_ctx_create": (C.c_int, [C.POINTER(ModelDesc), C.POINTER(MeshDesc), C.c_int, C.POINTER(C.c_void_p)]),
@@ -145,6 +150,11 @@ SIGNATURES = {
                                              C.POINTER(c_double_p), C.POINTER(c_int_p), C.POINTER(c_double_p), C.POINTER(c_double_p), c_int_p]),
     "icp_region_weights_many": (C.c_int, [C.c_int32, C.c_int, c_int_p, C.POINTER(c_double_p), c_int_p, C.POINTER(c_double_p), c_double_p,
                                           C.POINTER(c_double_p), c_int_p]),
+    "icp_scans_prepare_many": (C.c_int, [C.c_int32, C.c_int, c_int_p, C.POINTER(c_double_p), c_int_p, C.POINTER(c_int_p),
+                                         C.POINTER(ScanTransform), c_int_p, C.POINTER(c_double_p), c_int_p, C.POINTER(c_int_p),
+                                         C.POINTER(c_int_p), c_int_p, C.POINTER(c_int_p), C.POINTER(c_double_p), C.POINTER(c_double_p),
+                                         C.POINTER(c_ubyte_p), C.POINTER(c_double_p), C.POINTER(c_int_p), C.POINTER(c_int_p), c_int_p,
+                                         c_int_p]),
     "icp_chain_step":(C.c_int, [C.c_void_p, C.c_int32, C.POINTER(C.c_void_p), C.c_int32, c_double_p, c_double_p, c_double_p,
                                  c_double_p, c_double_p, c_double_p]),
     "icp_chain_step_batched_issue": (C.c_int, [C.c_int32, C.POINTER(C.c_void_p), C.c_int32, C.POINTER(C.c_void_p), C.POINTER(C.c_int32),

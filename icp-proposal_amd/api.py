@@ -1342,3 +1342,117 @@ def face_kernel(mesh, mask=None, device=0):
         regions = [mask.region(mesh, level) for level, _ in levels]
         weights = region_weights([mesh.points] * len(levels), regions, 40.0, device)
     return [_data.BSplineKernelTerm(scale, level, np.eye(3), w, _data.FACE_KERNEL_MIRROR_GAIN, 0) for (level, scale), w in zip(levels, weights)]
+
+
+_SCAN_WANT = ("aligned", "partial", "kept_ids", "landmarks", "cut_flags")
+_SCAN_MAX_POINTS, _SCAN_MAX_CUTS, _SCAN_MAX_MAGNITUDE = 1 << 26, 7, 2.0 ** 400
+
+
+def _is_int_like(v):
+    return isinstance(v, (int, np.integer)) and not isinstance(v, bool)
+
+
+def _is_cut_list(v):
+    """one item's cuts: a list or tuple of (landmark index, count) pairs, possibly empty"""
+    return isinstance(v, (list, tuple)) and all(isinstance(q, (list, tuple)) and len(q) == 2 and all(_is_int_like(x) for x in q) for q in v)
+
+
+def _scan_per_item(value, n, is_single, name):
+    """`value` for every item: one value (is_single) is repeated, a list or tuple has one entry per item"""
+    if value is None or is_single(value):
+        return [value] * n
+    if not isinstance(value, (list, tuple)) or len(value) != n:
+        raise ValueError(f"{name}: one for all items, or one per item")
+    return list(value)
+
+
+def prepare_scans(scans, transforms, landmarks=None, cuts=None, mask_ids=None, device=0, want=_SCAN_WANT) -> list:
+    """Aligned and partial targets of many raw scans in one call (icp_scans_prepare_many; apps/femur/AlignShapes.scala:30-55,
+    apps/bfm/AlignShapes.scala:33-101).  Per item: `scans[b]` (a data.TriangleMesh) under `transforms[b]` (a
+    data.ScanTransform: A(x) = R·(s·x − c) + c + t), its `landmarks[b]` [L, 3] under the same transform, `cuts[b]` — up to seven
+    pairs (landmark index, count): the count vertices nearest the aligned landmark, equal distances going to the lowest ids — and
+    `mask_ids[b]`, vertex ids to cut away besides (repeats are fine, ids >= the vertex count match nothing).  What no cut took is
+    compacted as maskPoints(...).transformedMesh does: triangles without a cut vertex, and the vertices they use.
+    One transform, landmark array, cut list or id list serves every item; a list or tuple holds one per item.
+    -> one dict per item with the keys of `want`: "aligned" (TriangleMesh, all vertices), "partial" (TriangleMesh), "kept_ids" [n_kept]
+    (kept_ids[new] = old), "landmarks" [L, 3], "cut_flags" [M] uint8 (bit j: cut j; bit 7: the id list)."""
+    want = _want(want, _SCAN_WANT)
+    scans = [scans] if isinstance(scans, _data.TriangleMesh) else list(scans)
+    n = len(scans)
+    if n == 0 or n > 65535:
+        raise ValueError("at least one scan, at most 65,535 a call")
+    tfs = _scan_per_item(transforms, n, lambda v: isinstance(v, _data.ScanTransform), "transforms")
+    lms = _scan_per_item(landmarks, n, lambda v: isinstance(v, np.ndarray), "landmarks")
+    cts = _scan_per_item(cuts, n, _is_cut_list, "cuts")
+    mks = _scan_per_item(mask_ids, n, lambda v: isinstance(v, np.ndarray) or (isinstance(v, (list, tuple)) and all(_is_int_like(x) for x in v)),
+                         "mask_ids")
+    pts, cells, tf_arr, lm_arr, cl_arr, cc_arr, mk_arr = [], [], (nat.ScanTransform * n)(), [], [], [], []
+    for b in range(n):
+        mesh, tf = scans[b], tfs[b]
+        if not isinstance(mesh, _data.TriangleMesh) or not isinstance(tf, _data.ScanTransform):
+            raise ValueError(f"item {b}: a data.TriangleMesh and a data.ScanTransform")
+        p, c = mesh.points, mesh.cells.reshape(-1, 3)
+        M = p.shape[0]
+        if p.ndim != 2 or p.shape[1] != 3 or M < 1 or M > _SCAN_MAX_POINTS or c.shape[0] > _SCAN_MAX_POINTS:
+            raise ValueError(f"item {b}: points are [1 .. 2^26, 3], at most 2^26 triangles")
+        if c.size and (c.min() < 0 or c.max() >= M):
+            raise ValueError(f"item {b}: a triangle's vertex id is out of range")
+        s = tf.pre_scale
+        if not (math.isfinite(s) and s > 0.0):
+            raise ValueError(f"item {b}: pre_scale must be finite and positive")
+        lm = np.zeros((0, 3)) if lms[b] is None else _f64(lms[b]).reshape(-1, 3)
+        with np.errstate(over="ignore", invalid="ignore"):
+            small = all(np.all(np.abs(a) <= _SCAN_MAX_MAGNITUDE) for a in (tf.rotation, tf.centre, tf.translation, p, lm, s * p, s * lm))
+        if not small:
+            raise ValueError(f"item {b}: every value is finite, and |s·x|, |c|, |t| and |R_ij| are at most 2^400")
+        ct = [] if cts[b] is None else list(cts[b])
+        if len(ct) > _SCAN_MAX_CUTS:
+            raise ValueError(f"item {b}: at most {_SCAN_MAX_CUTS} cuts")
+        for pair in ct:
+            if len(pair) != 2 or not all(_is_int_like(x) for x in pair) or not (0 <= pair[0] < lm.shape[0]) or not (0 <= pair[1] <= 2 ** 31 - 1):
+                raise ValueError(f"item {b}: a cut is (landmark index in [0, {lm.shape[0]}), count >= 0)")
+        mk = np.zeros(0, dtype=np.int64) if mks[b] is None else np.asarray(mks[b])
+        if mk.size and (mk.ndim != 1 or mk.dtype.kind not in "iu" or mk.min() < 0 or mk.max() > 2 ** 31 - 1):
+            raise ValueError(f"item {b}: mask ids are int32 values >= 0")
+        pts.append(p); cells.append(np.ascontiguousarray(c, dtype=np.int32)); lm_arr.append(lm)
+        cl_arr.append(np.array([q[0] for q in ct], dtype=np.int32)); cc_arr.append(np.array([q[1] for q in ct], dtype=np.int32))
+        mk_arr.append(np.ascontiguousarray(mk.reshape(-1), dtype=np.int32))
+        tf_arr[b].struct_size, tf_arr[b].pre_scale = C.sizeof(nat.ScanTransform), s
+        tf_arr[b].rotation[:] = tf.rotation.reshape(-1).tolist()
+        tf_arr[b].centre[:] = tf.centre.tolist()
+        tf_arr[b].translation[:] = tf.translation.tolist()
+    counts = lambda arrays, width=1: np.array([a.shape[0] // width if a.ndim == 1 else a.shape[0] for a in arrays], dtype=np.int32)  # noqa: E731
+    n_pts, n_tri, n_lm, n_ct, n_mk = counts(pts), counts(cells), counts(lm_arr), counts(cl_arr), counts(mk_arr)
+    partial = "partial" in want
+    aligned = [np.zeros((p.shape[0], 3)) for p in pts] if "aligned" in want else None
+    lm_out = [np.zeros((a.shape[0], 3)) for a in lm_arr] if "landmarks" in want else None
+    flags = [np.zeros(p.shape[0], dtype=np.uint8) for p in pts] if "cut_flags" in want else None
+    ppts = [np.zeros((p.shape[0], 3)) for p in pts] if partial else None
+    ptris = [np.zeros((c.shape[0], 3), dtype=np.int32) for c in cells] if partial else None
+    kept = [np.zeros(p.shape[0], dtype=np.int32) for p in pts] if (partial or "kept_ids" in want) else None
+    cnt = np.zeros(2 * n, dtype=np.int32)
+    status = np.zeros(n, dtype=np.int32)
+    out_d = lambda a: None if a is None else _ptr_array(a)  # noqa: E731
+    out_i = lambda a: None if a is None else _ptr_array(a, nat.c_int_p, _i)  # noqa: E731
+    rc = nat.lib().icp_scans_prepare_many(n, int(device), _i(n_pts), _ptr_array(pts), _i(n_tri), _ptr_array(cells, nat.c_int_p, _i), tf_arr,
+                                          _i(n_lm), _ptr_array(lm_arr), _i(n_ct), _ptr_array(cl_arr, nat.c_int_p, _i),
+                                          _ptr_array(cc_arr, nat.c_int_p, _i), _i(n_mk), _ptr_array(mk_arr, nat.c_int_p, _i), out_d(aligned),
+                                          out_d(lm_out), None if flags is None else _ptr_array(flags, nat.c_ubyte_p, _ubyte_p), out_d(ppts),
+                                          out_i(ptris), out_i(kept), _i(cnt), _i(status))
+    nat.check(rc, "icp_scans_prepare_many")
+    out = []
+    for b in range(n):
+        nk, tk = int(cnt[2 * b]), int(cnt[2 * b + 1])
+        item = {}
+        if "aligned" in want:
+            item["aligned"] = _data.TriangleMesh(aligned[b], cells[b])
+        if partial:
+            item["partial"] = _data.TriangleMesh(ppts[b][:nk].copy(), ptris[b][:tk].copy())
+        if "kept_ids" in want:
+            item["kept_ids"] = kept[b][:nk].copy()
+        if "landmarks" in want:
+            item["landmarks"] = lm_out[b]
+        if "cut_flags" in want:
+            item["cut_flags"] = flags[b]
+        out.append(item)
+    return out

@@ -972,5 +972,40 @@ void launch_gpm_refine(hipStream_t st, int n, int me_max, const GpmSpace* items)
 void launch_gpm_operand(hipStream_t st, int n, int mp_max, int ldb_max, const GpmSpace* items);
 void launch_gpm_gemm(hipStream_t st, int n_pieces, int rows_max, int col_tiles_max, const GpmPiece* pieces);
 
+// ---- aligned and partial targets from raw scans (kernels_scan_prep.hip; icp_scans_prepare_many)
+constexpr int kScanMaxCuts = 7;     // cuts per item: bits 0..6 of a vertex's flag byte; bit 7 is the mask list's
+constexpr int kScanTile = 2048;     // elements of one workgroup of the block scan: an item's block totals are a function of its size alone
+struct ScanItem {       // one item's record (device), the same for every launch of its round
+  int M, T, L, n_cuts, n_mask;
+  int cut_landmark[kScanMaxCuts];
+  int cut_count[kScanMaxCuts];   // min(cut_count, M)
+  double s, R[9], c[3], o[3];    // pre-scale, rotation (row-major), centre, o = c + t rounded once on the host
+  const double* pts;    // [3M] the scan's points
+  const double* lms;    // [3L] landmarks in scan coordinates
+  const int* tris;      // [3T]
+  const int* mask;      // [n_mask] ids of the mask list (>= 0; ids >= M match nothing)
+  double* aligned;      // [3M] A(P)
+  double* lm_out;       // [3L] A(Λ)
+  unsigned long long* keys;  // [n_cuts][M] bit patterns of d²
+  unsigned long long* thr;   // [n_cuts][2] the threshold of the composite key: (d² bits, id as a signed 64-bit word)
+  unsigned char* flags; // [M] zeroed in front of the round
+  unsigned char* used;  // [M] zeroed in front of the round: 1 = some kept triangle uses the vertex
+  unsigned char* keep;  // [T]
+  int* vpre;            // [M] exclusive prefix of used[] within its tile; + vblk[tile] = the new id
+  int* tpre;            // [T] likewise of keep[]
+  int* vblk;            // [cdiv(M, kScanTile)] tile totals, then their exclusive prefix
+  int* tblk;            // [cdiv(T, kScanTile)]
+  int* counts;          // [2] n_kept, t_kept
+  double* ppts;         // [3M] rows 0 .. n_kept-1
+  int* ptris;           // [3T] rows 0 .. t_kept-1, renumbered
+  int* kept;            // [M] kept[new] = old
+};
+void launch_scan_transform(hipStream_t st, int n_items, long long work_max, const ScanItem* items);  // work_max = max (M + L + n_mask)
+void launch_scan_select(hipStream_t st, int n_items, const ScanItem* items);
+void launch_scan_flags(hipStream_t st, int n_items, int m_max, const ScanItem* items);
+void launch_scan_triangles(hipStream_t st, int n_items, int t_max, const ScanItem* items);
+void launch_scan_prefix(hipStream_t st, int n_items, int n_max, const ScanItem* items);  // block scan, scan of the block totals
+void launch_scan_scatter(hipStream_t st, int n_items, int n_max, const ScanItem* items);
+
 
 }  // namespace icp

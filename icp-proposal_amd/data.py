@@ -407,3 +407,70 @@ def synthetic_partial_target(model: StatisticalMeshModel, seed: int = 7, n_remov
     remap[used] = np.arange(int(used.sum()))
     return TriangleMesh(pts[used], remap[keep_cells].astype(np.int32))
 
+
+
+# ---------------------------------------------------------------------------------------------------------------
+# Target preparation: what apps/femur/AlignShapes.scala:30-55 and apps/bfm/AlignShapes.scala:33-101 do to a raw scan in front of
+# either study — scale, landmark alignment, the cut around a landmark plus an id list, compaction.  The arithmetic runs on the device
+# (api.prepare_scans, icp_scans_prepare_many); Kabsch on a handful of landmark pairs stays here.
+
+@dataclasses.dataclass
+class ScanTransform:
+    """A(x) = R·(s·x − c) + c + t: Scalismo's translation ∘ rotation-about-c behind Scaling(s) (AlignmentTransforms.scala:25-30,
+    apps/bfm/AlignShapes.scala:66,77-83)."""
+    pre_scale: float = 1.0
+    rotation: np.ndarray = dataclasses.field(default_factory=lambda: np.eye(3))   # [3,3]
+    centre: np.ndarray = dataclasses.field(default_factory=lambda: np.zeros(3))
+    translation: np.ndarray = dataclasses.field(default_factory=lambda: np.zeros(3))
+
+    def __post_init__(self):
+        self.pre_scale = float(self.pre_scale)
+        self.rotation = np.ascontiguousarray(self.rotation, dtype=np.float64).reshape(3, 3)
+        self.centre = np.ascontiguousarray(self.centre, dtype=np.float64).reshape(3)
+        self.translation = np.ascontiguousarray(self.translation, dtype=np.float64).reshape(3)
+
+
+def landmark_alignment(scan_landmarks, model_landmarks, centre=(0.0, 0.0, 0.0), pre_scale: float = 1.0) -> ScanTransform:
+    """AlignmentTransforms.computeTransform (apps/util/AlignmentTransforms.scala:25-30) behind Scaling(pre_scale): both arguments map
+    landmark names to points; the pairs are the names common to both, in the scan's order (`lm1.map(_.id) intersect lm2.map(_.id)`);
+    Kabsch (rigid_landmark_transform) takes the pre-scaled scan landmarks onto the model's, rotating about `centre`."""
+    names = [k for k in scan_landmarks if k in model_landmarks]
+    if len(names) < 3:
+        raise ValueError("a rigid alignment needs at least three landmark names common to scan and model")
+    c = np.ascontiguousarray(centre, dtype=np.float64).reshape(3)
+    s = float(pre_scale)
+    src = np.asarray([np.asarray(scan_landmarks[k], dtype=np.float64).reshape(3) for k in names]) * s - c
+    dst = np.asarray([np.asarray(model_landmarks[k], dtype=np.float64).reshape(3) for k in names]) - c
+    if not (np.isfinite(s) and s > 0.0 and np.all(np.isfinite(src)) and np.all(np.isfinite(dst))):
+        raise ValueError("pre_scale must be positive and the landmarks finite")
+    rot, t = rigid_landmark_transform(src, dst)
+    return ScanTransform(s, rot, c, t)
+
+
+def aligned_and_partial_targets(scans, scan_landmarks, model_landmarks, pre_scale: float = 1.0, cut_landmark=None, cut_count: int = 0,
+                                mask_ids=(), drop_landmarks=(), device: int = 0):
+    """The two AlignShapes.main loops in one call (apps/femur/AlignShapes.scala:30-55: alignment alone; apps/bfm/AlignShapes.scala:
+    71-100: scale, alignment, the `cut_count` vertices nearest the aligned landmark `cut_landmark` plus `mask_ids` cut away, the rest
+    compacted).  scans: TriangleMesh per scan; scan_landmarks: a name -> point mapping per scan; model_landmarks: one mapping.
+    -> (aligned meshes, partial meshes, aligned landmark dicts, partial landmark dicts: without the names in drop_landmarks, :93).
+    The mouth id list of the reference is part of its program text: the caller passes its own ids."""
+    from . import api
+    scans, scan_landmarks = list(scans), list(scan_landmarks)
+    if len(scans) != len(scan_landmarks) or not scans:
+        raise ValueError("one landmark mapping per scan, at least one scan")
+    transforms, points, cuts = [], [], []
+    for lms in scan_landmarks:
+        transforms.append(landmark_alignment(lms, model_landmarks, pre_scale=pre_scale))
+        points.append(np.asarray([np.asarray(lms[k], dtype=np.float64).reshape(3) for k in lms]).reshape(-1, 3))
+        if cut_landmark is None:
+            cuts.append([])
+        else:
+            if cut_landmark not in lms:
+                raise ValueError(f"a scan has no landmark {cut_landmark!r} to cut around")
+            cuts.append([(list(lms).index(cut_landmark), int(cut_count))])
+    got = api.prepare_scans(scans, transforms, points, cuts, [np.asarray(mask_ids, dtype=np.int64).reshape(-1)] * len(scans), device=device,
+                            want=("aligned", "partial", "landmarks"))
+    aligned_lms = [{k: g["landmarks"][i].copy() for i, k in enumerate(lms)} for g, lms in zip(got, scan_landmarks)]
+    dropped = set(drop_landmarks)
+    partial_lms = [{k: v for k, v in d.items() if k not in dropped} for d in aligned_lms]
+    return [g["aligned"] for g in got], [g["partial"] for g in got], aligned_lms, partial_lms

@@ -652,6 +652,50 @@ ICP_API int icp_region_weights_many(int32_t n_items, int device, const int32_t *
                                     const int32_t *n_region, const double *const *region_points, const double *stddev,
                                     double *const *weights_out, int32_t *status);
 
+/* ---- aligned and partial targets from raw scans, many in one call.
+ * The step both studies of the reference start with (apps/femur/AlignShapes.scala:30-55, apps/bfm/AlignShapes.scala:33-101): a raw
+ * scan is scaled, landmark-aligned, cut around landmarks and by an id list, and what is left is compacted.  Kabsch on a handful of
+ * landmark pairs stays with the caller; the device gets the transform.  Per item b, all floating point f64 with every operation
+ * rounded separately, all ids int32:
+ *   transform   A(x): q = s*x per coordinate, u = q - c, y_i = ((R_i0*u_0 + R_i1*u_1) + R_i2*u_2) + o_i with o = c + t rounded once on
+ *               the host: Scalismo's translation o rotation-about-c behind Scaling(s) (AlignmentTransforms.scala:25-30,
+ *               apps/bfm/AlignShapes.scala:66,77-83).  aligned_out[b] [3 * M] = A(points[b]), landmarks_out[b] [3 * L] = A(landmarks[b]):
+ *               vertices and landmarks go through one device function, so a cut's centre has the bits the caller gets back.
+ *   cut j       (findNClosestPoints, :90) z = landmarks_out[cut_landmark[b][j]], d2(v) = (dx*dx + dy*dy) + dz*dz with dx = aligned[v].x -
+ *               z.x ...; the cut set is the min(cut_count[b][j], M) vertices smallest in (d2, v), ordered lexicographically: EQUAL
+ *               DISTANCES GO TO THE LOWEST IDS (a rule of this library; the reference's KD-tree leaves it open).
+ *   flags       cut_flags_out[b][v] [M] has bit j if v is in cut set j and bit 7 if v occurs in mask_ids[b] (duplicates allowed, ids
+ *               >= M match nothing); a vertex is dropped iff its flags are not zero.
+ *   compaction  (operations.maskPoints(...).transformedMesh, :92 [SCALISMO-UNVERIFIED]) a triangle is kept iff none of its vertices
+ *               is dropped, kept triangles stay in their order; a vertex is kept iff a kept triangle uses it, kept vertices stay in
+ *               ascending old id order — a vertex no triangle references leaves the partial mesh even when it is not cut.
+ *               partial_points_out[b] (caller: [3 * M]), partial_triangles_out[b] (caller: [3 * T], renumbered), kept_ids_out[b]
+ *               (caller: [M], kept_ids[new] = old): the rows counts_out[2b] = n_kept / counts_out[2b + 1] = t_kept are written, the
+ *               rows behind them are left untouched.  An empty result (everything cut, T = 0) is ICP_OK with counts (0, 0).
+ * Any output array, or any entry of one, may be NULL, and so may counts_out; status may not.  Limits, checked for every item before
+ * the device is touched (status[b] = ICP_ERR_INVALID_ARG, nothing written for that item): 1 <= M <= 2^26, 0 <= T <= 2^26, triangle
+ * ids in [0, M), struct_size, pre_scale > 0, every double finite and |s*x|, |c|, |t|, |R_ij| <= 2^400 (no result is NaN),
+ * 0 <= n_cuts <= ICP_SCAN_MAX_CUTS, 0 <= cut_landmark < L, cut_count >= 0, mask ids >= 0; n_items in [1, 65535].  The items go
+ * through the device in rounds of at most ICP_SCAN_PREP_ROUND_BYTES (an item above that has a round of its own), one
+ * synchronisation per round; an item's bits depend on the item alone. */
+#define ICP_SCAN_MAX_CUTS 7
+#define ICP_SCAN_PREP_ROUND_BYTES (64u << 20)
+typedef struct {
+  uint64_t struct_size;   /* sizeof(icp_scan_transform) */
+  double pre_scale;       /* s > 0 */
+  double rotation[9];     /* R, row-major */
+  double centre[3];       /* c */
+  double translation[3];  /* t */
+} icp_scan_transform;
+ICP_API int icp_scans_prepare_many(int32_t n_items, int device, const int32_t *n_points, const double *const *points,
+                                   const int32_t *n_triangles, const int32_t *const *triangles, const icp_scan_transform *transforms,
+                                   const int32_t *n_landmarks, const double *const *landmarks, const int32_t *n_cuts,
+                                   const int32_t *const *cut_landmark, const int32_t *const *cut_count, const int32_t *n_mask_ids,
+                                   const int32_t *const *mask_ids, double *const *aligned_out, double *const *landmarks_out,
+                                   uint8_t *const *cut_flags_out, double *const *partial_points_out,
+                                   int32_t *const *partial_triangles_out, int32_t *const *kept_ids_out,
+                                   int32_t *counts_out /* [n_items * 2] */, int32_t *status);
+
 /* ---------------------------------------------------------------- the per-method entry points as ONE submission per step (round 6)
  * The drop-in contract is "Scalismo's chain, unchanged": MetropolisHastings.next (constructed at
  * api/sampling/SamplingRegistration.scala:52-58) calls  logValue(current) [memoised] → propose(current) → logValue(proposal) →
