@@ -1300,6 +1300,131 @@ def gp_model(mesh, kernel, n_pivots, rank=None, rel_tolerance=0.0, device=0, wan
     return gp_models([mesh], [list(kernel)], n_pivots, rank, rel_tolerance, device, want)[0]
 
 
+_PCA_WANT = ("variance", "mean", "transforms")
+PCA_MAX_MESHES, PCA_MAX_ROUNDS = 256, 32
+PCA_NOT_FINITE = -3  # ICP_ERR_NOT_FINITE: an item whose meshes are all equal (no component is left)
+
+
+def pca_models(mesh_sets, rank=None, gpa_iterations=3, halt_distance=1e-5, reference=None, cells=None, device=0, want=_PCA_WANT):
+    """PCA shape models of meshes in correspondence, with generalised Procrustes alignment, many in one call (icp_pca_models_many;
+    Scalismo's DataCollection.gpa followed by StatisticalMeshModel.createUsingPCA).  `mesh_sets`: a list of items, each
+    a list of 2..256 [N, 3] arrays or data.TriangleMesh of one N; arrays that are the same object go into the call's pool once.  Item b:
+    at most gpa_iterations[b] <= 32 rounds of rigid alignment to the mean shape, stopped behind the round that moves the mean shape by
+    less than halt_distance[b] (RMS); then the leading rank[b] <= n − 1 (None: n − 1) eigenpairs of the covariance of the aligned
+    meshes.  rank, gpa_iterations, halt_distance: one for all, or one per item.  reference: None, one [N, 3] array or mesh for all, or a
+    list of one (or None) per item: the model's reference points, its mean deformation being mean shape − reference; None: the mean
+    shape is the reference.  cells: the triangles, one array for all or one per item (None: those of the item's first data.TriangleMesh,
+    else none).  Returns one (model, info) per item: a data.StatisticalMeshModel of the effective rank with columns of squared norm N
+    (None for an item that failed), and a dict with "n_meshes", "rank" (effective), "total_variance" trace(G)/N, "approximated_variance"
+    Σ variance, "rounds", "rms" (the last round's RMS displacement of the mean shape), "status" (0, or -3 with NaN arrays for an item
+    whose meshes are all equal, beside which the others are computed) and the wanted ones of "variance" [rank], "mean" [N, 3],
+    "transforms" [n, 12] (each mesh's composite rotation by rows, then its translation)."""
+    want = tuple(want)
+    for w in want:
+        if w not in _PCA_WANT:
+            raise ValueError(f"unknown output {w!r}: one of {_PCA_WANT}")
+    sets = [list(s) for s in mesh_sets]
+    n = len(sets)
+    if n == 0 or n > 65535:
+        raise ValueError("at least one item, at most 65,535 a call")
+
+    def per_item(v, name, single):
+        v = [v] * n if single(v) else list(v)
+        if len(v) != n:
+            raise ValueError(f"{name}: one for all items, or one per item")
+        return v
+    scalar = lambda v: v is None or not isinstance(v, (list, tuple, np.ndarray))  # noqa: E731
+    array = lambda v: v is None or isinstance(v, (np.ndarray, _data.TriangleMesh))  # noqa: E731
+    rk = per_item(rank, "rank", scalar)
+    it = [int(v) for v in per_item(gpa_iterations, "gpa_iterations", scalar)]
+    hd = [float(v) for v in per_item(halt_distance, "halt_distance", scalar)]
+    refs = per_item(reference, "reference", array)
+    cls = per_item(cells, "cells", lambda v: v is None or isinstance(v, np.ndarray))
+    pool, pool_index, ids = [], {}, []
+    for b, ms in enumerate(sets):
+        if not (2 <= len(ms) <= PCA_MAX_MESHES):
+            raise ValueError(f"item {b}: 2 to {PCA_MAX_MESHES} meshes")
+        row = []
+        for m in ms:
+            src = m.points if isinstance(m, _data.TriangleMesh) else m
+            if id(src) not in pool_index:
+                p = _f64(src)
+                if p.ndim != 2 or p.shape[1] != 3 or p.shape[0] < 1:
+                    raise ValueError(f"item {b}: a mesh has points [N, 3]")
+                if not np.all(np.isfinite(p)):
+                    raise ValueError(f"item {b}: points contain a non-finite value")
+                pool_index[id(src)] = len(pool)
+                pool.append((src, p))  # (src: kept alive, so that its id stays its own)
+            row.append(pool_index[id(src)])
+        N = pool[row[0]][1].shape[0]
+        if any(pool[k][1].shape[0] != N for k in row):
+            raise ValueError(f"item {b}: the meshes of an item have one N")
+        rk[b] = len(ms) - 1 if rk[b] is None else int(rk[b])
+        if not (1 <= rk[b] <= len(ms) - 1):
+            raise ValueError(f"item {b}: 1 <= rank <= n - 1")
+        if not (0 <= it[b] <= PCA_MAX_ROUNDS):
+            raise ValueError(f"item {b}: 0 <= gpa_iterations <= {PCA_MAX_ROUNDS}")
+        if not (math.isfinite(hd[b]) and hd[b] >= 0.0):
+            raise ValueError(f"item {b}: halt_distance must be finite and >= 0")
+        if refs[b] is not None:
+            r = _f64(refs[b].points if isinstance(refs[b], _data.TriangleMesh) else refs[b])
+            if r.shape != (N, 3) or not np.all(np.isfinite(r)):
+                raise ValueError(f"item {b}: the reference is [N, 3] and finite")
+            refs[b] = r
+        if cls[b] is None:
+            first = next((m for m in ms if isinstance(m, _data.TriangleMesh)), None)
+            cls[b] = first.cells if first is not None else np.zeros((0, 3), dtype=np.int32)
+        ids.append(np.array(row, dtype=np.int32))
+    n_pts = [pool[row[0]][1].shape[0] for row in ids]
+    var = [np.zeros(rk[b]) for b in range(n)]
+    basis = [np.zeros((3 * n_pts[b], rk[b])) for b in range(n)]
+    mean = [np.zeros((n_pts[b], 3)) for b in range(n)]
+    tfs = [np.zeros((len(sets[b]), 12)) for b in range(n)] if "transforms" in want else None
+    info = np.zeros((n, 8))
+    status = np.zeros(n, dtype=np.int32)
+    pool_pts = np.array([p.shape[0] for _, p in pool], dtype=np.int32)
+    n_meshes = np.array([len(s) for s in sets], dtype=np.int32)
+    a_rk, a_it, a_hd = np.array(rk, dtype=np.int32), np.array(it, dtype=np.int32), np.array(hd, dtype=np.float64)
+    rc = nat.lib().icp_pca_models_many(n, int(device), len(pool), _i(pool_pts), _ptr_array([p for _, p in pool]), _i(n_meshes),
+                                       _ptr_array(ids, nat.c_int_p, _i), _ptr_array(refs), _i(a_rk), _i(a_it), _d(a_hd), _ptr_array(var),
+                                       _ptr_array(basis), _ptr_array(mean), None if tfs is None else _ptr_array(tfs),
+                                       _ptr_array(list(info)), _i(status))
+    if rc != 0 and (not status.any() or not np.all((status == 0) | (status == PCA_NOT_FINITE))):
+        nat.check(rc, "icp_pca_models_many")  # a whole-call error, or an item the checks above should have refused
+    res = []
+    for b in range(n):
+        ok = status[b] == 0
+        re = int(info[b, 1]) if ok else 0
+        d = {"n_meshes": len(sets[b]), "rank": re, "total_variance": float(info[b, 2]), "approximated_variance": float(info[b, 3]),
+             "rounds": int(info[b, 4]) if ok else 0, "rms": float(info[b, 5]), "status": int(status[b])}
+        if "variance" in want:
+            d["variance"] = var[b][:re].copy() if ok else var[b]
+        if "mean" in want:
+            d["mean"] = mean[b]
+        if "transforms" in want:
+            d["transforms"] = tfs[b]
+        model = None
+        if ok:
+            ref = mean[b] if refs[b] is None else refs[b]
+            model = _data.StatisticalMeshModel(ref, cls[b], mean[b] - ref, basis[b][:, :re], var[b][:re].copy())
+        res.append((model, d))
+    return res
+
+
+def pca_model(meshes, rank=None, gpa_iterations=3, halt_distance=1e-5, reference=None, cells=None, device=0, want=_PCA_WANT):
+    """One item of pca_models: (model, info) of the meshes in correspondence `meshes`."""
+    return pca_models([list(meshes)], rank, gpa_iterations, halt_distance, reference, cells, device, want)[0]
+
+
+def leave_one_out_pca_models(meshes, rank=None, gpa_iterations=3, halt_distance=1e-5, reference=None, cells=None, device=0, want=_PCA_WANT):
+    """The n leave-one-out models of n >= 3 meshes in ONE pca_models call over one pool (n uploads, not n·(n−1)): item i is the model
+    of all meshes but mesh i — what generalisation and specificity of a learned model are measured on."""
+    ms = list(meshes)
+    if len(ms) < 3:
+        raise ValueError("leave-one-out models need at least three meshes")
+    return pca_models([ms[:i] + ms[i + 1:] for i in range(len(ms))], rank, gpa_iterations, halt_distance, reference, cells, device, want)
+
+
 def region_weights(points, region_points, stddev=40.0, device=0):
     """Smoothed region weights (icp_region_weights_many; apps/bfm/FaceMask.scala computeSmoothedRegions): w[i] = exp(−d²/stddev²), d the
     distance from points[i] to the nearest of region_points; exactly 1 at a region point.  One item — points [N, 3], region_points

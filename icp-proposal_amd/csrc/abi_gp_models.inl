@@ -5,7 +5,8 @@
 //
 // Item b: the pivoted Cholesky factor L of its kernel matrix, up to n_pivots columns (one launch per pivot step carries every item
 // of the call), then LᵀL = W·Θ·Wᵀ and the model (Θ/N, √N·L·W·Θ^-1/2).  The host synchronises ONCE behind the pivot loop, to read how
-// many columns every item made: that is the rank of its decomposition.  The m-space work then goes through kGpmGroup slots of scratch,
+// many columns every item made: that is the rank of its decomposition.  The m-space work (gpm_mspace_run, which icp_pca_models_many
+// calls with its centred data matrices as the factors) then goes through kGpmGroup slots of scratch,
 // a group at a time: the Gram matrices in one launch, the decompositions rank by rank (launch_posterior_eigen_many up to rank 64,
 // launch_posterior_eigen_tridiag_many up to 256, launch_posterior_eigen for ranks 1 and 2 and for a spectrum the side-by-side route
 // could not separate), one refinement step of the eigenvectors and the operands in a launch each, and the group's rows of L·Op through ONE chunk buffer, round by round, one
@@ -76,6 +77,23 @@ bool gpm_term_good(const icp_kernel_term_general& k, long long N, double lattice
   }
   return true;
 }
+
+// one item of the m-space half: a column-major factor L ([me][R]) whose L·Lᵀ is the item's covariance
+struct GpmFactor {
+  int b;             // the caller's item: the index into the output arrays and item_status
+  const double* L;   // device
+  int R, me, rank;   // rows 3N; columns; eigenpairs asked for
+  double trace;      // trace(LᵀL) > 0: the Gram matrix is multiplied by the power of two that brings it into [1, 2)
+  double n_points;   // N
+  double tau;        // rank_rule: eigenvalues θ <= tau do not count (k_pca_rank); unused otherwise
+};
+
+// the m-space half of icp_gp_models_many, icp_gp_models_general_many and icp_pca_models_many: LᵀL = W·Θ·Wᵀ and the model (Θ/N,
+// √N·L·W·Θ^-1/2) of every factor, a group of kGpmGroup at a time; variance_out / basis_out / info_out[..][0..3] and the statuses of
+// the items that fail.  rank_rule: the effective rank is decided on the device between the refinement and the operand
+// (launch_pca_rank), and an item that keeps no component fails.
+void gpm_mspace_run(hipStream_t st, const std::vector<GpmFactor>& f, bool rank_rule, double* const* variance_out, double* const* basis_out,
+                    double* const* info_out, std::vector<int>& item_status);
 
 // the body of both entry points, inside their guard.  general_entry: an item whose pivot loop leaves no column is that item's failure
 // (icp_gp_models_general_many) instead of the call's.
@@ -231,196 +249,210 @@ void gpm_models_run(int32_t n_items, int device, const int32_t* n_points, const 
       if (n_live == 0) return;
     }
 
-    // ---- m-space: kGpmGroup slots of scratch sized for the call's largest decomposition; the chunk
-    int me_max = 1, rank_max = 1, slabs_max = 1;
-    std::vector<GpmSpace> h_sp(n_live);
+    // ---- m-space (gpm_mspace_run, shared with icp_pca_models_many)
+    std::vector<GpmFactor> factors(n_live);
     for (int q = 0; q < n_live; ++q) {
       const int b = live[q];
-      GpmSpace& s = h_sp[q];
-      s.R = 3 * n_points[b]; s.me = h_meff[q]; s.mp = (s.me + 15) / 16 * 16;
-      s.slab_rows = gpm_slab_rows(s.R); s.slabs = cdiv(s.R, s.slab_rows);
-      s.rank = rank[b]; s.re = std::min(s.rank, s.me); s.ldb = (s.rank + 15) / 16 * 16;
-      s.scale = std::ldexp(1.0, -std::ilogb(h_start[2 * (size_t)q + 1]));
-      s.n_points = (double)n_points[b];
-      s.L = d_L.p + off_L[q];
-      me_max = std::max(me_max, s.me); rank_max = std::max(rank_max, s.rank); slabs_max = std::max(slabs_max, s.slabs);
+      factors[q] = GpmFactor{b, d_L.p + off_L[q], 3 * n_points[b], h_meff[q], rank[b], h_start[2 * (size_t)q + 1], (double)n_points[b], 0.0};
     }
-    const int slots = std::min(kGpmGroup, n_live);
-    const int mp_max = (me_max + 15) / 16 * 16, ldb_max = (rank_max + 15) / 16 * 16;
-    const size_t mm = (size_t)me_max * me_max;
-    size_t work_max = 1;
-    for (int q = 0; q < n_live; ++q) work_max = std::max(work_max, eigen_work_doubles(h_sp[q].me));
-    size_t cap = test_chunk_doubles("ICP_TEST_GP_MODELS_CHUNK_DOUBLES", kGpmChunkDoubles);
-    cap = std::max(cap, (size_t)kGpmRowQuantum * rank_max);  // (a piece always fits)
-    DBuf<double> Gpart, G, V, Vt, S, T, Sm, Rm, E, lam, Op, work, ones, d_var, chunk;
-    DBuf<int> d_status, d_order;
-    DBuf<GpmSpace> d_sp;
-    {
-      NullStreamBatch _nb;
-      Gpart.alloc((size_t)slots * slabs_max * mp_max * mp_max);
-      G.alloc(slots * mm); V.alloc(slots * mm); Vt.alloc(slots * mm);
-      S.alloc((size_t)slots * me_max); lam.alloc((size_t)slots * me_max); d_order.alloc((size_t)slots * me_max);
-      T.alloc(slots * mm); Sm.alloc(slots * mm); Rm.alloc(slots * mm); E.alloc(slots * mm);
-      Op.alloc((size_t)slots * mp_max * ldb_max);
-      work.alloc(slots * work_max);
-      d_var.alloc((size_t)n_live * rank_max);
-      chunk.alloc(cap);
-      std::vector<double> h_ones(kGpmMaxPivots, 1.0);
-      ones.upload(h_ones.data(), h_ones.size());
-      d_status.alloc(4 * (size_t)n_live);  // per item {-, sweeps, decomposition, -}
-      d_status.fill_bytes(0);
-      for (int q = 0; q < n_live; ++q) {
-        const int s = q % slots;
-        GpmSpace& sp = h_sp[q];
-        sp.Gpart = Gpart.p + (size_t)s * slabs_max * mp_max * mp_max;
-        sp.G = G.p + s * mm; sp.V = V.p + s * mm;
-        sp.T = T.p + s * mm; sp.Sm = Sm.p + s * mm; sp.Rm = Rm.p + s * mm; sp.E = E.p + s * mm;
-        sp.lam = lam.p + (size_t)s * me_max; sp.order = d_order.p + (size_t)s * me_max;
-        sp.Op = Op.p + (size_t)s * mp_max * ldb_max;
-        sp.variance = d_var.p + (size_t)q * rank_max;
-      }
-      d_sp.upload(h_sp.data(), h_sp.size());
-    }
-    void* pinned_rec = nullptr;
-    pinned_alloc(&pinned_rec, eigen_many_record_bytes(n_live));
-    struct PinnedGuard { void* p; ~PinnedGuard() { pinned_free(p); } } _pg{pinned_rec};
-    size_t rec_used = 0;
-    EigenProblem* rec_base = (EigenProblem*)pinned_rec;
+    gpm_mspace_run(st, factors, false, variance_out, basis_out, info_out, item_status);
+  }
+}
 
-    // the m-space work of items q0 .. q1-1 (one group).  alone: every decomposition by launch_posterior_eigen, which falls back to the
-    // Jacobi iteration on the device where the multisection gives up.
-    auto run_mspace = [&](int q0, int q1, bool alone) {
-      const int n = q1 - q0;
-      int gmp = 16, gldb = 16, gslabs = 1;
-      for (int q = q0; q < q1; ++q) {
-        gmp = std::max(gmp, h_sp[q].mp); gldb = std::max(gldb, h_sp[q].ldb); gslabs = std::max(gslabs, h_sp[q].slabs);
-      }
-      HIP_OK(hipMemsetAsync(work.p, 0, sizeof(double) * work_max * (size_t)std::min(n, slots), st));  // (the decompositions' progress words)
-      launch_gpm_gram(st, n, gmp, gslabs, d_sp.p + q0);
-      std::vector<int> order(n);  // decompositions, rank by rank
-      for (int i = 0; i < n; ++i) order[i] = q0 + i;
-      std::stable_sort(order.begin(), order.end(), [&](int x, int y) { return h_sp[x].me < h_sp[y].me; });
-      for (int i0 = 0; i0 < n;) {
-        int i1 = i0;
-        const int r = h_sp[order[i0]].me;
-        while (i1 < n && h_sp[order[i1]].me == r) ++i1;
-        std::vector<EigenRequest> rq;
-        for (int i = i0; i < i1; ++i) {
-          const int q = order[i], s = q % slots;
-          rq.push_back(EigenRequest{G.p + s * mm, nullptr, V.p + s * mm, Vt.p + s * mm, S.p + (size_t)s * me_max, work.p + s * work_max,
-                                    d_status.p + 4 * (size_t)q + 2, nullptr, nullptr, nullptr, 0, ones.p});
-        }
-        const int m = i1 - i0;
-        bool done = false;
-        if (!alone) {
-          if (eigen_tridiag_many_supported(r)) {
-            launch_posterior_eigen_tridiag_many(st, r, m, rq.data(), nullptr);
-            done = true;
-          } else if (launch_posterior_eigen_many(st, r, m, rq.data(), rec_base + rec_used, nullptr) >= 0) {
-            rec_used += (size_t)m;
-            done = true;
-          }
-        }
-        if (!done)
-          for (const EigenRequest& e : rq) launch_posterior_eigen(st, r, e.M, e.sqrt_lambda, nullptr, e.V, e.Vt, e.S, e.work, e.status);
-        i0 = i1;
-      }
-      launch_gpm_refine(st, n, gmp, d_sp.p + q0);
-      launch_gpm_operand(st, n, gmp, gldb, d_sp.p + q0);
-    };
-    // the rows of the group's bases through the chunk buffer: pieces that fill it are a round (product, copies back, synchronisation)
-    auto run_rounds = [&](int q0, int q1) {
-      struct Back { double* dev; double* host; size_t n; };
-      std::vector<GpmPiece> pcs;
-      std::vector<Back> back;
-      DBuf<GpmPiece> d_pcs;
-      size_t used = 0;
-      int rows_max = 0, tiles_max = 0;
-      auto flush = [&] {
-        if (pcs.empty()) return;
-        {
-          NullStreamBatch _nb;
-          d_pcs.upload(pcs.data(), pcs.size());
-        }
-        launch_gpm_gemm(st, (int)pcs.size(), rows_max, tiles_max, d_pcs.p);
-        HostCopies cp;
-        for (const Back& k : back) cp.add(k.dev, k.host, k.n);
-        cp.issue(st, false);
-        HIP_OK(hipStreamSynchronize(st));
-        pcs.clear(); back.clear();
-        used = 0; rows_max = 0; tiles_max = 0;
-      };
-      for (int q = q0; q < q1; ++q) {
-        const int b = live[q];
-        if (!(basis_out && basis_out[b])) continue;
-        const GpmSpace& sp = h_sp[q];
-        const size_t per_q = (size_t)kGpmRowQuantum * sp.rank;
-        for (int row0 = 0; row0 < sp.R;) {
-          if (cap - used < per_q || (int)pcs.size() == kGpmMaxPieces) flush();
-          const size_t fit = (cap - used) / per_q * kGpmRowQuantum;
-          const int rows = (int)std::min<size_t>(fit, (size_t)(sp.R - row0));
-          GpmPiece pc{};
-          pc.L = sp.L; pc.Op = sp.Op; pc.R = sp.R; pc.me = sp.me; pc.rank = sp.rank; pc.ldb = sp.ldb; pc.row0 = row0; pc.rows = rows;
-          pc.out = chunk.p + used;
-          used += (size_t)rows * sp.rank;
-          back.push_back(Back{pc.out, basis_out[b] + (size_t)row0 * sp.rank, (size_t)rows * sp.rank});
-          rows_max = std::max(rows_max, rows);
-          tiles_max = std::max(tiles_max, sp.ldb / 16);
-          pcs.push_back(pc);
-          row0 += rows;
-        }
-      }
-      flush();
-    };
-
-    std::vector<double> h_var((size_t)n_live * rank_max);
-    std::vector<int> h_st(4 * (size_t)n_live);
-    auto fetch_small = [&] {
-      HIP_OK(hipMemcpyAsync(h_var.data(), d_var.p, sizeof(double) * h_var.size(), hipMemcpyDeviceToHost, st));
-      HIP_OK(hipMemcpyAsync(h_st.data(), d_status.p, sizeof(int) * h_st.size(), hipMemcpyDeviceToHost, st));
-      HIP_OK(hipStreamSynchronize(st));
-    };
-    for (int q0 = 0; q0 < n_live; q0 += slots) {
-      const int q1 = std::min(n_live, q0 + slots);
-      run_mspace(q0, q1, false);
-      run_rounds(q0, q1);
-    }
-    fetch_small();
-    // a spectrum the side-by-side decomposition could not separate (equal eigenvalues: an isotropic kernel has them in threes): that
-    // item again, on its own
-    bool again = false;
+void gpm_mspace_run(hipStream_t st, const std::vector<GpmFactor>& f, bool rank_rule, double* const* variance_out, double* const* basis_out,
+                    double* const* info_out, std::vector<int>& item_status) {
+  const int n_live = (int)f.size();
+  if (n_live == 0) return;
+  // ---- m-space: kGpmGroup slots of scratch sized for the call's largest decomposition; the chunk
+  int me_max = 1, rank_max = 1, slabs_max = 1;
+  std::vector<GpmSpace> h_sp(n_live);
+  for (int q = 0; q < n_live; ++q) {
+    GpmSpace& s = h_sp[q];
+    s.R = f[q].R; s.me = f[q].me; s.mp = (s.me + 15) / 16 * 16;
+    s.slab_rows = gpm_slab_rows(s.R); s.slabs = cdiv(s.R, s.slab_rows);
+    s.rank = f[q].rank; s.re = std::min(s.rank, s.me); s.ldb = (s.rank + 15) / 16 * 16;
+    s.scale = std::ldexp(1.0, -std::ilogb(f[q].trace));
+    s.n_points = f[q].n_points; s.tau = f[q].tau;
+    s.L = f[q].L;
+    me_max = std::max(me_max, s.me); rank_max = std::max(rank_max, s.rank); slabs_max = std::max(slabs_max, s.slabs);
+  }
+  const int slots = std::min(kGpmGroup, n_live);
+  const int mp_max = (me_max + 15) / 16 * 16, ldb_max = (rank_max + 15) / 16 * 16;
+  const size_t mm = (size_t)me_max * me_max;
+  size_t work_max = 1;
+  for (int q = 0; q < n_live; ++q) work_max = std::max(work_max, eigen_work_doubles(h_sp[q].me));
+  size_t cap = test_chunk_doubles("ICP_TEST_GP_MODELS_CHUNK_DOUBLES", kGpmChunkDoubles);
+  cap = std::max(cap, (size_t)kGpmRowQuantum * rank_max);  // (a piece always fits)
+  DBuf<double> Gpart, G, V, Vt, S, T, Sm, Rm, E, lam, Op, work, ones, d_var, chunk;
+  DBuf<int> d_status, d_order;
+  DBuf<GpmSpace> d_sp;
+  {
+    NullStreamBatch _nb;
+    Gpart.alloc((size_t)slots * slabs_max * mp_max * mp_max);
+    G.alloc(slots * mm); V.alloc(slots * mm); Vt.alloc(slots * mm);
+    S.alloc((size_t)slots * me_max); lam.alloc((size_t)slots * me_max); d_order.alloc((size_t)slots * me_max);
+    T.alloc(slots * mm); Sm.alloc(slots * mm); Rm.alloc(slots * mm); E.alloc(slots * mm);
+    Op.alloc((size_t)slots * mp_max * ldb_max);
+    work.alloc(slots * work_max);
+    d_var.alloc((size_t)n_live * rank_max);
+    chunk.alloc(cap);
+    std::vector<double> h_ones(kGpmMaxPivots, 1.0);
+    ones.upload(h_ones.data(), h_ones.size());
+    d_status.alloc(4 * (size_t)n_live);  // per item {-, sweeps, decomposition, -}
+    d_status.fill_bytes(0);
     for (int q = 0; q < n_live; ++q) {
-      if (h_st[4 * q + 2] == 0) continue;
+      const int s = q % slots;
+      GpmSpace& sp = h_sp[q];
+      sp.Gpart = Gpart.p + (size_t)s * slabs_max * mp_max * mp_max;
+      sp.G = G.p + s * mm; sp.V = V.p + s * mm;
+      sp.T = T.p + s * mm; sp.Sm = Sm.p + s * mm; sp.Rm = Rm.p + s * mm; sp.E = E.p + s * mm;
+      sp.lam = lam.p + (size_t)s * me_max; sp.order = d_order.p + (size_t)s * me_max;
+      sp.Op = Op.p + (size_t)s * mp_max * ldb_max;
+      sp.variance = d_var.p + (size_t)q * rank_max;
+    }
+    d_sp.upload(h_sp.data(), h_sp.size());
+  }
+  void* pinned_rec = nullptr;
+  pinned_alloc(&pinned_rec, eigen_many_record_bytes(n_live));
+  struct PinnedGuard { void* p; ~PinnedGuard() { pinned_free(p); } } _pg{pinned_rec};
+  size_t rec_used = 0;
+  EigenProblem* rec_base = (EigenProblem*)pinned_rec;
+
+  // the m-space work of items q0 .. q1-1 (one group).  alone: every decomposition by launch_posterior_eigen, which falls back to the
+  // Jacobi iteration on the device where the multisection gives up.
+  auto run_mspace = [&](int q0, int q1, bool alone) {
+    const int n = q1 - q0;
+    int gmp = 16, gldb = 16, gslabs = 1;
+    for (int q = q0; q < q1; ++q) {
+      gmp = std::max(gmp, h_sp[q].mp); gldb = std::max(gldb, h_sp[q].ldb); gslabs = std::max(gslabs, h_sp[q].slabs);
+    }
+    HIP_OK(hipMemsetAsync(work.p, 0, sizeof(double) * work_max * (size_t)std::min(n, slots), st));  // (the decompositions' progress words)
+    launch_gpm_gram(st, n, gmp, gslabs, d_sp.p + q0);
+    std::vector<int> order(n);  // decompositions, rank by rank
+    for (int i = 0; i < n; ++i) order[i] = q0 + i;
+    std::stable_sort(order.begin(), order.end(), [&](int x, int y) { return h_sp[x].me < h_sp[y].me; });
+    for (int i0 = 0; i0 < n;) {
+      int i1 = i0;
+      const int r = h_sp[order[i0]].me;
+      while (i1 < n && h_sp[order[i1]].me == r) ++i1;
+      std::vector<EigenRequest> rq;
+      for (int i = i0; i < i1; ++i) {
+        const int q = order[i], s = q % slots;
+        rq.push_back(EigenRequest{G.p + s * mm, nullptr, V.p + s * mm, Vt.p + s * mm, S.p + (size_t)s * me_max, work.p + s * work_max,
+                                  d_status.p + 4 * (size_t)q + 2, nullptr, nullptr, nullptr, 0, ones.p});
+      }
+      const int m = i1 - i0;
+      bool done = false;
+      if (!alone) {
+        if (eigen_tridiag_many_supported(r)) {
+          launch_posterior_eigen_tridiag_many(st, r, m, rq.data(), nullptr);
+          done = true;
+        } else if (launch_posterior_eigen_many(st, r, m, rq.data(), rec_base + rec_used, nullptr) >= 0) {
+          rec_used += (size_t)m;
+          done = true;
+        }
+      }
+      if (!done)
+        for (const EigenRequest& e : rq) launch_posterior_eigen(st, r, e.M, e.sqrt_lambda, nullptr, e.V, e.Vt, e.S, e.work, e.status);
+      i0 = i1;
+    }
+    launch_gpm_refine(st, n, gmp, d_sp.p + q0);
+    if (rank_rule) launch_pca_rank(st, n, d_sp.p + q0);  // the effective rank, decided on the device: k_gpm_operand reads it
+    launch_gpm_operand(st, n, gmp, gldb, d_sp.p + q0);
+  };
+  // the rows of the group's bases through the chunk buffer: pieces that fill it are a round (product, copies back, synchronisation)
+  auto run_rounds = [&](int q0, int q1) {
+    struct Back { double* dev; double* host; size_t n; };
+    std::vector<GpmPiece> pcs;
+    std::vector<Back> back;
+    DBuf<GpmPiece> d_pcs;
+    size_t used = 0;
+    int rows_max = 0, tiles_max = 0;
+    auto flush = [&] {
+      if (pcs.empty()) return;
       {
         NullStreamBatch _nb;
-        HIP_OK(hipMemset(d_status.p + 4 * (size_t)q, 0, sizeof(int) * 4));
+        d_pcs.upload(pcs.data(), pcs.size());
       }
-      run_mspace(q, q + 1, true);
-      run_rounds(q, q + 1);
-      again = true;
-    }
-    if (again) fetch_small();
-    for (int q = 0; q < n_live; ++q) {
-      const int b = live[q];
+      launch_gpm_gemm(st, (int)pcs.size(), rows_max, tiles_max, d_pcs.p);
+      HostCopies cp;
+      for (const Back& k : back) cp.add(k.dev, k.host, k.n);
+      cp.issue(st, false);
+      HIP_OK(hipStreamSynchronize(st));
+      pcs.clear(); back.clear();
+      used = 0; rows_max = 0; tiles_max = 0;
+    };
+    for (int q = q0; q < q1; ++q) {
+      const int b = f[q].b;
+      if (!(basis_out && basis_out[b])) continue;
       const GpmSpace& sp = h_sp[q];
-      const double* var = &h_var[(size_t)q * rank_max];
-      bool ok = h_st[4 * q + 2] == 0;
-      for (int j = 0; ok && j < sp.re; ++j) ok = std::isfinite(var[j]) && var[j] > 0.0;
-      if (!ok) {
-        item_status[b] = ICP_ERR_NOT_FINITE;
-        const size_t R = (size_t)sp.R;
-        if (variance_out && variance_out[b]) std::fill(variance_out[b], variance_out[b] + sp.rank, (double)NAN);
-        if (basis_out && basis_out[b]) std::fill(basis_out[b], basis_out[b] + R * sp.rank, (double)NAN);
-        if (info_out && info_out[b]) std::fill(info_out[b], info_out[b] + 4, (double)NAN);
-        continue;
+      const size_t per_q = (size_t)kGpmRowQuantum * sp.rank;
+      for (int row0 = 0; row0 < sp.R;) {
+        if (cap - used < per_q || (int)pcs.size() == kGpmMaxPieces) flush();
+        const size_t fit = (cap - used) / per_q * kGpmRowQuantum;
+        const int rows = (int)std::min<size_t>(fit, (size_t)(sp.R - row0));
+        GpmPiece pc{};
+        pc.L = sp.L; pc.Op = sp.Op; pc.R = sp.R; pc.me = sp.me; pc.rank = sp.rank; pc.ldb = sp.ldb; pc.row0 = row0; pc.rows = rows;
+        pc.out = chunk.p + used;
+        used += (size_t)rows * sp.rank;
+        back.push_back(Back{pc.out, basis_out[b] + (size_t)row0 * sp.rank, (size_t)rows * sp.rank});
+        rows_max = std::max(rows_max, rows);
+        tiles_max = std::max(tiles_max, sp.ldb / 16);
+        pcs.push_back(pc);
+        row0 += rows;
       }
-      if (variance_out && variance_out[b]) std::memcpy(variance_out[b], var, sizeof(double) * (size_t)sp.rank);
-      if (info_out && info_out[b]) {
-        double sum = 0.0;
-        for (int j = 0; j < sp.re; ++j) sum += var[j];
-        info_out[b][0] = (double)sp.me; info_out[b][1] = (double)sp.re;
-        info_out[b][2] = h_start[2 * (size_t)q + 1] / sp.n_points; info_out[b][3] = sum;
-      }
+    }
+    flush();
+  };
+
+  std::vector<double> h_var((size_t)n_live * rank_max);
+  std::vector<int> h_st(4 * (size_t)n_live);
+  auto fetch_small = [&] {
+    HIP_OK(hipMemcpyAsync(h_var.data(), d_var.p, sizeof(double) * h_var.size(), hipMemcpyDeviceToHost, st));
+    HIP_OK(hipMemcpyAsync(h_st.data(), d_status.p, sizeof(int) * h_st.size(), hipMemcpyDeviceToHost, st));
+    if (rank_rule) HIP_OK(hipMemcpyAsync(h_sp.data(), d_sp.p, sizeof(GpmSpace) * h_sp.size(), hipMemcpyDeviceToHost, st));  // (the records' re)
+    HIP_OK(hipStreamSynchronize(st));
+  };
+  for (int q0 = 0; q0 < n_live; q0 += slots) {
+    const int q1 = std::min(n_live, q0 + slots);
+    run_mspace(q0, q1, false);
+    run_rounds(q0, q1);
+  }
+  fetch_small();
+  // a spectrum the side-by-side decomposition could not separate (equal eigenvalues: an isotropic kernel has them in threes): that
+  // item again, on its own
+  bool again = false;
+  for (int q = 0; q < n_live; ++q) {
+    if (h_st[4 * q + 2] == 0) continue;
+    {
+      NullStreamBatch _nb;
+      HIP_OK(hipMemset(d_status.p + 4 * (size_t)q, 0, sizeof(int) * 4));
+    }
+    run_mspace(q, q + 1, true);
+    run_rounds(q, q + 1);
+    again = true;
+  }
+  if (again) fetch_small();
+  for (int q = 0; q < n_live; ++q) {
+    const int b = f[q].b;
+    const GpmSpace& sp = h_sp[q];
+    const double* var = &h_var[(size_t)q * rank_max];
+    bool ok = h_st[4 * q + 2] == 0 && sp.re >= (rank_rule ? 1 : 0) && sp.re <= std::min(sp.rank, sp.me);
+    for (int j = 0; ok && j < sp.re; ++j) ok = std::isfinite(var[j]) && var[j] > 0.0;
+    if (!ok) {
+      item_status[b] = ICP_ERR_NOT_FINITE;
+      const size_t R = (size_t)sp.R;
+      if (variance_out && variance_out[b]) std::fill(variance_out[b], variance_out[b] + sp.rank, (double)NAN);
+      if (basis_out && basis_out[b]) std::fill(basis_out[b], basis_out[b] + R * sp.rank, (double)NAN);
+      if (info_out && info_out[b]) std::fill(info_out[b], info_out[b] + 4, (double)NAN);
+      continue;
+    }
+    if (variance_out && variance_out[b]) std::memcpy(variance_out[b], var, sizeof(double) * (size_t)sp.rank);
+    if (info_out && info_out[b]) {
+      double sum = 0.0;
+      for (int j = 0; j < sp.re; ++j) sum += var[j];
+      info_out[b][0] = (double)sp.me; info_out[b][1] = (double)sp.re;
+      info_out[b][2] = f[q].trace / sp.n_points; info_out[b][3] = sum;
     }
   }
 }

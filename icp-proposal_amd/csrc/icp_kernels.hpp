@@ -948,6 +948,7 @@ struct GpmSpace {       // one item's m-space record (device): Gram matrix, deco
   int* order;           // [me] order[j] = the index of the j-th largest of lam (ties: the lower index)
   double* Op;           // [mp][ldb] = W·Θ^-1/2·√N, zero padding
   double* variance;     // [rank] θ/N descending, zero behind re
+  double tau;           // icp_pca_models_many's rank rule (k_pca_rank): eigenvalues θ <= tau do not count; unused by the GP models
 };
 struct GpmPiece {       // rows row0 .. row0+rows-1 of one item's L·Op, resident in the chunk buffer (device)
   const double* L; const double* Op;
@@ -971,6 +972,31 @@ void launch_gpm_gram(hipStream_t st, int n, int mp_max, int slabs_max, const Gpm
 void launch_gpm_refine(hipStream_t st, int n, int me_max, const GpmSpace* items);
 void launch_gpm_operand(hipStream_t st, int n, int mp_max, int ldb_max, const GpmSpace* items);
 void launch_gpm_gemm(hipStream_t st, int n_pieces, int rows_max, int col_tiles_max, const GpmPiece* pieces);
+
+// ---- PCA shape models from registered meshes, with generalised Procrustes alignment (kernels_pca_model.hip; icp_pca_models_many)
+constexpr int kPcaBlock = 256;      // vertices (centroids, cross-covariance, apply) or rows (mean, centring) a workgroup owns
+constexpr int kPcaMaxRounds = 32;
+struct PcaItem {        // one item's record (device), the same for every launch of the call
+  int n, N, R;          // meshes; vertices; rows 3N
+  int nblk, nblkR;      // cdiv(N, kPcaBlock) workgroups over vertices; cdiv(R, kPcaBlock) over rows
+  int max_rounds;       // gpa_iterations
+  double halt;          // halt_distance
+  const double* const* src;  // [n] the item's meshes in the pool (device pointers, device array)
+  double* X;            // [n][R] working copies, then the centred columns: the factor L of the m-space half
+  double* mean;         // [R] the current mean shape
+  double* cpart;        // [n + 1][3][nblk] partial coordinate sums of every mesh and (index n) of the mean shape
+  double* hpart;        // [n][9][nblk] partial cross-covariances, mesh against mean shape
+  double* dpart;        // [nblkR] partial Σ (new mean − mean)² of the last round run
+  double* tpart;        // [2][nblkR] partial Σ column² (= trace G) and Σ x² of the aligned meshes, left by the centring launch
+  double* tf;           // [n][12] composite transforms: rotation by rows, then the translation
+  double* state;        // [2] rounds run; the last round's RMS displacement of the mean shape
+  int* stop;            // [1] set by the launch that finds the last round's RMS below `halt`
+};
+void launch_pca_init(hipStream_t st, int n_items, int nblkR_max, const PcaItem* items);
+// one round of the alignment for every item still running: centroids, cross-covariances, solve-and-apply, new mean shape
+void launch_pca_round(hipStream_t st, int n_items, int n_max, int nblk_max, int nblkR_max, int round, const PcaItem* items);
+void launch_pca_centre(hipStream_t st, int n_items, int nblkR_max, const PcaItem* items);
+void launch_pca_rank(hipStream_t st, int n, GpmSpace* items);
 
 // ---- aligned and partial targets from raw scans (kernels_scan_prep.hip; icp_scans_prepare_many)
 constexpr int kScanMaxCuts = 7;     // cuts per item: bits 0..6 of a vertex's flag byte; bit 7 is the mask list's

@@ -652,6 +652,52 @@ ICP_API int icp_region_weights_many(int32_t n_items, int device, const int32_t *
                                     const int32_t *n_region, const double *const *region_points, const double *stddev,
                                     double *const *weights_out, int32_t *status);
 
+/* ---- PCA shape models from registered meshes, with generalised Procrustes alignment, many in one call.
+ * What a registration study is made for: meshes in correspondence (all in the model's vertex order) become a statistical shape model,
+ * Scalismo's DataCollection.gpa followed by StatisticalMeshModel.createUsingPCA.  The alignment rules are this project's restatement
+ * [SCALISMO-UNVERIFIED].  The meshes live in a pool that is uploaded once: pool mesh k is pool[k] [pool_points[k]][3]; item b uses
+ * pool[mesh_ids[b][0 .. n_meshes[b]-1]], all of one N, copied into working copies of its own.  A leave-one-out call on n meshes uploads n.
+ *   alignment   at most gpa_iterations[b] rounds (0: the meshes are taken as given).  The first mean shape is the mean of the copies,
+ *               summed in the order j = 0, 1, ....  A round aligns every mesh to the SAME current mean shape by the least-squares rigid
+ *               transform over all N vertex pairs (proper rotation, no scale), then the aligned meshes' mean is the new mean shape.
+ *               The transform in two passes: the centroids c_x, c_y first, then S = sum (x - c_x)(y - c_y)^T of the centred points
+ *               (not sum x y^T - N c_x c_y^T, which cancels at coordinates of 200 mm); the rotation is Horn's unit quaternion, the
+ *               eigenvector of the largest eigenvalue of the symmetric 4 x 4 matrix of S, by cyclic Jacobi sweeps in f64;
+ *               x <- R (x - c_x) + c_y.  An item stops behind the round in which sqrt(mean_i |new mean_i - mean_i|^2) < halt_distance[b]:
+ *               the RMS displacement of the mean shape, NOT Scalismo's procrustesDistance, which aligns the two means once more.
+ *               transforms_out[b] [n][12]: every mesh's composite transform (R <- R_k R, t <- R_k t + t_k with t_k = c_y - R_k c_x,
+ *               accumulated on the device), rotation by rows, then the translation: aligned = R x + t up to rounding.
+ *   centring    mean_out[b] [3N] is the final mean shape (the model's mean deformation is mean_out - reference, a subtraction the caller
+ *               makes; without a reference the mean shape is the reference mesh and the mean deformation 0); column j of the data
+ *               matrix L is (x_j - mean) / sqrt(n - 1).
+ *   model       the covariance is L L^T over ALL n columns; its eigenpairs through the n x n matrix G = L^T L exactly as
+ *               icp_gp_models_many makes them (the same launches): variance_j = theta_j / N, basis column j = sqrt(N) L w_j / sqrt(theta_j).
+ *               G is singular by construction (the centred columns sum to rounding): rank[b] <= n - 1, and the effective rank is
+ *               min(rank, #{j : theta_j > tau}), tau = max(3N n 2^-52 trace(G), tau_0): the first is the worst-case rounding of the
+ *               Gram sum (3N products per entry, n x n entries in spectral norm); tau_0 = 2^-80 sum_j |x_j|^2 / (n - 1) is a direction
+ *               in which the aligned meshes differ by less than 2^-40 of their size, which is what up to 32 rounds of rotating the
+ *               copies in f64 leave of rounding.  Decided on the device.  Columns and variances behind the effective rank are zero.
+ *               An item that keeps no component (all meshes equal) fails alone: status[b] = ICP_ERR_NOT_FINITE, every output NaN.
+ *   info_out[b] [8] = meshes, effective rank, trace(G) / N (the total variance), sum of variance_out[b], rounds run, the last round's
+ *               RMS displacement (0 without a round), 0, 0.
+ * reference: NULL, or per item NULL or [3N]; checked for finiteness and otherwise the caller's.  Every output array may be NULL as a
+ * whole, and so may each entry.  Limits, checked for every item before the device is touched (status[b] = ICP_ERR_INVALID_ARG, nothing
+ * written for it, the other items computed): 2 <= n_meshes <= 256; N >= 1, 3N <= INT32_MAX; 1 <= rank <= n_meshes - 1;
+ * 0 <= gpa_iterations <= ICP_PCA_MODELS_MAX_ROUNDS; halt_distance >= 0 and finite; ids in [0, n_pool); one N per item; finite points.
+ * Whole-call errors (nothing has run): n_items outside [1, 65535], n_pool < 1, a null required argument; ICP_ERR_DEVICE.
+ * The call takes no context.  1 + 4 * (the call's largest gpa_iterations) + 1 launches carry every item and every mesh, without a
+ * synchronisation between them (a stopped item returns from every later launch); ONE synchronisation; then icp_gp_models_many's
+ * m-space half, one synchronisation per round of output rows.  Device memory: the pool once, and 8 * 3N * (n + 1) bytes per item and a
+ * few partials, all items at once.  No floating-point atomics; an item's bits depend neither on the other items, nor on their order,
+ * nor on how its rows fall into the chunk buffer.  Not covered: more than 256 meshes per item; parity of the halt rule with Scalismo;
+ * degenerate (collinear) vertex sets, whose rotation is not unique. */
+#define ICP_PCA_MODELS_MAX_ROUNDS 32
+ICP_API int icp_pca_models_many(int32_t n_items, int device, int32_t n_pool, const int32_t *pool_points, const double *const *pool,
+                                const int32_t *n_meshes, const int32_t *const *mesh_ids, const double *const *reference,
+                                const int32_t *rank, const int32_t *gpa_iterations, const double *halt_distance,
+                                double *const *variance_out, double *const *basis_out, double *const *mean_out,
+                                double *const *transforms_out, double *const *info_out, int32_t *status);
+
 /* ---- aligned and partial targets from raw scans, many in one call.
  * The step both studies of the reference start with (apps/femur/AlignShapes.scala:30-55, apps/bfm/AlignShapes.scala:33-101): a raw
  * scan is scaled, landmark-aligned, cut around landmarks and by an id list, and what is left is compacted.  Kabsch on a handful of
