@@ -150,6 +150,10 @@ SIGNATURES = {
                                              C.POINTER(c_double_p), C.POINTER(c_int_p), C.POINTER(c_double_p), C.POINTER(c_double_p), c_int_p]),
     "icp_region_weights_many": (C.c_int, [C.c_int32, C.c_int, c_int_p, C.POINTER(c_double_p), c_int_p, C.POINTER(c_double_p), c_double_p,
                                           C.POINTER(c_double_p), c_int_p]),
+    "icp_nystrom_models_many": (C.c_int, [C.c_int32, C.c_int, c_int_p, C.POINTER(c_double_p), c_int_p, C.POINTER(c_double_p), c_int_p,
+                                          C.POINTER(C.POINTER(KernelTermGeneral)), C.POINTER(C.POINTER(c_double_p)), c_int_p, c_double_p,
+                                          C.POINTER(c_double_p), C.POINTER(c_double_p), C.POINTER(c_double_p), C.POINTER(c_double_p),
+                                          C.POINTER(c_double_p), c_int_p]),
     "icp_pca_models_many": (C.c_int, [C.c_int32, C.c_int, C.c_int32, c_int_p, C.POINTER(c_double_p), c_int_p, C.POINTER(c_int_p),
                                       C.POINTER(c_double_p), c_int_p, c_int_p, c_double_p, C.POINTER(c_double_p), C.POINTER(c_double_p),
                                       C.POINTER(c_double_p), C.POINTER(c_double_p), C.POINTER(c_double_p), c_int_p]),

@@ -1162,6 +1162,52 @@ def _psd3(a):
     return bool(det >= -eps * mag)
 
 
+def _kernel_terms(b, kb, p, general, keep, lattice=None):
+    """the checked ctypes terms of item b's kernel `kb` on the points p [N, 3] (nat.KernelTermGeneral if `general`, else nat.KernelTerm);
+    the weights' arrays go into `keep`, alive while the library reads them.  `lattice`: the largest |coordinate| the B-spline lattice has to
+    hold, where that is more than p's"""
+    kb = list(kb)
+    if not (1 <= len(kb) <= GP_MAX_TERMS):
+        raise ValueError(f"item {b}: a kernel has 1 to {GP_MAX_TERMS} terms")
+    arr = ((nat.KernelTermGeneral if general else nat.KernelTerm) * len(kb))()
+    for t, k in enumerate(kb):
+        if not isinstance(k, _KERNEL_TERMS):
+            raise ValueError(f"item {b}, term {t}: a data.GaussianKernelTerm or a data.BSplineKernelTerm")
+        gauss = isinstance(k, _data.GaussianKernelTerm)
+        if gauss and not (math.isfinite(k.scale) and k.scale > 0.0 and math.isfinite(k.sigma) and k.sigma > 0.0
+                          and math.isfinite(k.sigma * k.sigma) and k.sigma * k.sigma > 0.0):
+            raise ValueError(f"item {b}, term {t}: scale and sigma must be finite and positive")
+        if not gauss:
+            if not (math.isfinite(k.scale) and k.scale > 0.0):
+                raise ValueError(f"item {b}, term {t}: scale must be finite and positive")
+            if not (-GP_MAX_LEVEL <= k.level <= GP_MAX_LEVEL) or not (math.ldexp(float(np.abs(p).max()) if lattice is None else lattice, k.level) < 2.0 ** 31):
+                raise ValueError(f"item {b}, term {t}: -{GP_MAX_LEVEL} <= level <= {GP_MAX_LEVEL} and |coordinate| * 2^level < 2^31")
+        a = _f64(k.A)
+        if a.shape != (3, 3) or not _psd3(a):
+            raise ValueError(f"item {b}, term {t}: A must be an exactly symmetric, positive semi-definite, non-zero 3 x 3 matrix")
+        arr[t].scale = k.scale
+        arr[t].A[:] = a.reshape(-1).tolist()
+        if not general:
+            arr[t].sigma = k.sigma
+            continue
+        if k.mirror_axis not in (0, 1, 2) or not (0.0 <= k.mirror_gain <= 1.0):
+            raise ValueError(f"item {b}, term {t}: mirror_axis is 0, 1 or 2 and 0 <= mirror_gain <= 1")
+        ax = k.mirror_axis
+        if k.mirror_gain > 0.0 and any(a[ax, c] != 0.0 or a[c, ax] != 0.0 for c in range(3) if c != ax):
+            raise ValueError(f"item {b}, term {t}: with a mirror gain, A must not couple the mirror axis to the others")
+        arr[t].struct_size = C.sizeof(nat.KernelTermGeneral)
+        arr[t].kind = nat.KERNEL_GAUSSIAN if gauss else nat.KERNEL_BSPLINE3
+        arr[t].sigma, arr[t].level = (k.sigma, 0) if gauss else (0.0, k.level)
+        arr[t].mirror_axis, arr[t].mirror_gain = ax, k.mirror_gain
+        if k.weights is not None:
+            w = _f64(k.weights)
+            if w.shape != (p.shape[0],) or not np.all(np.isfinite(w)) or not np.all(w >= 0.0) or not np.any(w > 0.0):
+                raise ValueError(f"item {b}, term {t}: weights are [N], finite, >= 0 and not all zero")
+            keep.append(w)
+            arr[t].weights = _d(w)
+    return arr
+
+
 def gp_models(meshes, kernels, n_pivots, rank=None, rel_tolerance=0.0, device=0, want=_GP_WANT):
     """Gaussian-process shape models of analytic kernels on many reference meshes in one call (icp_gp_models_many): what
     apps/femur/CreateGPModel.scala makes, by Scalismo's pivoted Cholesky approximation instead of the Nyström one.  Item b: the model
@@ -1214,45 +1260,7 @@ def gp_models(meshes, kernels, n_pivots, rank=None, rel_tolerance=0.0, device=0,
             raise ValueError(f"item {b}: 1 <= rank <= n_pivots <= min({GP_MAX_PIVOTS}, 3N)")
         if not (0.0 <= tol[b] < 1.0):
             raise ValueError(f"item {b}: rel_tolerance lies in [0, 1)")
-        kb = list(ks[b])
-        if not (1 <= len(kb) <= GP_MAX_TERMS):
-            raise ValueError(f"item {b}: a kernel has 1 to {GP_MAX_TERMS} terms")
-        arr = ((nat.KernelTermGeneral if general else nat.KernelTerm) * len(kb))()
-        for t, k in enumerate(kb):
-            if not isinstance(k, _KERNEL_TERMS):
-                raise ValueError(f"item {b}, term {t}: a data.GaussianKernelTerm or a data.BSplineKernelTerm")
-            gauss = isinstance(k, _data.GaussianKernelTerm)
-            if gauss and not (math.isfinite(k.scale) and k.scale > 0.0 and math.isfinite(k.sigma) and k.sigma > 0.0
-                              and math.isfinite(k.sigma * k.sigma) and k.sigma * k.sigma > 0.0):
-                raise ValueError(f"item {b}, term {t}: scale and sigma must be finite and positive")
-            if not gauss:
-                if not (math.isfinite(k.scale) and k.scale > 0.0):
-                    raise ValueError(f"item {b}, term {t}: scale must be finite and positive")
-                if not (-GP_MAX_LEVEL <= k.level <= GP_MAX_LEVEL) or not (math.ldexp(float(np.abs(p).max()), k.level) < 2.0 ** 31):
-                    raise ValueError(f"item {b}, term {t}: -{GP_MAX_LEVEL} <= level <= {GP_MAX_LEVEL} and |coordinate| * 2^level < 2^31")
-            a = _f64(k.A)
-            if a.shape != (3, 3) or not _psd3(a):
-                raise ValueError(f"item {b}, term {t}: A must be an exactly symmetric, positive semi-definite, non-zero 3 x 3 matrix")
-            arr[t].scale = k.scale
-            arr[t].A[:] = a.reshape(-1).tolist()
-            if not general:
-                arr[t].sigma = k.sigma
-                continue
-            if k.mirror_axis not in (0, 1, 2) or not (0.0 <= k.mirror_gain <= 1.0):
-                raise ValueError(f"item {b}, term {t}: mirror_axis is 0, 1 or 2 and 0 <= mirror_gain <= 1")
-            ax = k.mirror_axis
-            if k.mirror_gain > 0.0 and any(a[ax, c] != 0.0 or a[c, ax] != 0.0 for c in range(3) if c != ax):
-                raise ValueError(f"item {b}, term {t}: with a mirror gain, A must not couple the mirror axis to the others")
-            arr[t].struct_size = C.sizeof(nat.KernelTermGeneral)
-            arr[t].kind = nat.KERNEL_GAUSSIAN if gauss else nat.KERNEL_BSPLINE3
-            arr[t].sigma, arr[t].level = (k.sigma, 0) if gauss else (0.0, k.level)
-            arr[t].mirror_axis, arr[t].mirror_gain = ax, k.mirror_gain
-            if k.weights is not None:
-                w = _f64(k.weights)
-                if w.shape != (p.shape[0],) or not np.all(np.isfinite(w)) or not np.all(w >= 0.0) or not np.any(w > 0.0):
-                    raise ValueError(f"item {b}, term {t}: weights are [N], finite, >= 0 and not all zero")
-                keep.append(w)
-                arr[t].weights = _d(w)
+        arr = _kernel_terms(b, ks[b], p, general, keep)
         pts.append(p)
         terms.append(arr)
     shapes = {"variance": lambda b: (rk[b],), "basis": lambda b: (3 * pts[b].shape[0], rk[b]), "pivots": lambda b: (mp[b],),
@@ -1298,6 +1306,109 @@ def gp_models(meshes, kernels, n_pivots, rank=None, rel_tolerance=0.0, device=0,
 def gp_model(mesh, kernel, n_pivots, rank=None, rel_tolerance=0.0, device=0, want=_GP_WANT):
     """One item of gp_models: (model, info) of `kernel` (a list of data.GaussianKernelTerm and data.BSplineKernelTerm) on `mesh`."""
     return gp_models([mesh], [list(kernel)], n_pivots, rank, rel_tolerance, device, want)[0]
+
+
+_NYS_WANT = ("variance", "basis", "sample_eigenvalues", "sample_eigenvectors")
+NYSTROM_MAX_ROWS, NYSTROM_MAX_RANK = 2400, 256
+NYSTROM_NOT_CONVERGED = -7  # ICP_ERR_NOT_CONVERGED: the iteration hit its cap on sweeps; the item's outputs are written all the same
+
+
+def nystrom_models(items, min_variance=1e-8, device=0, want=_NYS_WANT):
+    """Gaussian-process shape models by the Nyström approximation on sample points, many in one call (icp_nystrom_models_many): what
+    apps/femur/CreateGPModel.scala and apps/bfm/CreateGPModel.scala call, LowRankGaussianProcess.approximateGPNystrom.  An item is
+    (mesh, samples, terms, rank) or (mesh, samples, terms, rank, sample_weights): a data.TriangleMesh, sample points [n, 3] (the
+    caller's choice; data.uniform_mesh_samples stands in for UniformMeshSampler3D), a kernel as gp_models takes it (a list of
+    data.GaussianKernelTerm and data.BSplineKernelTerm, plain or general) and the number of basis functions, 1 <= rank <= min(256, 3n)
+    with 3n <= 2,400.  A term with weights — they are the region weights at the mesh points — needs the same region weights at the sample
+    points: sample_weights, one entry per term, None or [n].  K = k(S, S) = U·Λ·Uᵀ; variance_i = λ_i/n; basis column i =
+    k(X, S)·u_i·√n/λ_i; the rank kept, k_eff, is the number of i < rank with λ_i/n >= min_variance (a number for all, or one per item).
+    Returns one (model, info) per item: a data.StatisticalMeshModel of k_eff components with zero mean deformation (its columns are not
+    orthonormal on the mesh; None unless "variance" and "basis" are wanted and the item was computed), and a dict with "rank" (k_eff),
+    "sweeps", "trace", "off_diagonal_mass", "status" (0; -7 where the iteration hit its cap on sweeps, the outputs written all the
+    same) and the wanted ones of "variance" [rank] (λ_i/n, all of them), "sample_eigenvalues" [3n], "sample_eigenvectors" [3n, rank]."""
+    its = [tuple(i) for i in items]
+    n = len(its)
+    if n == 0 or n > 65535:
+        raise ValueError("at least one item, at most 65,535 a call")
+    mv = list(min_variance) if isinstance(min_variance, (list, tuple, np.ndarray)) else [min_variance] * n
+    if len(mv) != n:
+        raise ValueError("min_variance: a number, or one per item")
+    mv = np.array([float(v) for v in mv], dtype=np.float64)
+    want = tuple(want)
+    for w in want:
+        if w not in _NYS_WANT:
+            raise ValueError(f"unknown output {w!r}: one of {_NYS_WANT}")
+    pts, smp, terms, rk, sws, keep = [], [], [], [], [], []
+    for b, item in enumerate(its):
+        if len(item) not in (4, 5):
+            raise ValueError(f"item {b}: (mesh, samples, terms, rank) or (mesh, samples, terms, rank, sample_weights)")
+        mesh, samples, kb, rank = item[:4]
+        p, s = _f64(mesh.points), _f64(samples)
+        if p.ndim != 2 or p.shape[1] != 3 or p.shape[0] < 1:
+            raise ValueError(f"item {b}: a mesh has points [N, 3]")
+        if s.ndim != 2 or s.shape[1] != 3 or s.shape[0] < 1:
+            raise ValueError(f"item {b}: samples are [n, 3]")
+        if int(rank) != rank:
+            raise ValueError(f"item {b}: rank is a whole number")
+        if not np.all(np.isfinite(p)) or not np.all(np.isfinite(s)):
+            raise ValueError(f"item {b}: points or samples contain a non-finite value")
+        if 3 * s.shape[0] > NYSTROM_MAX_ROWS:
+            raise ValueError(f"item {b}: at most {NYSTROM_MAX_ROWS // 3} sample points")
+        if not (1 <= rank <= min(NYSTROM_MAX_RANK, 3 * s.shape[0])):
+            raise ValueError(f"item {b}: 1 <= rank <= min({NYSTROM_MAX_RANK}, 3n)")
+        if not (math.isfinite(mv[b]) and mv[b] >= 0.0):
+            raise ValueError(f"item {b}: min_variance must be finite and >= 0")
+        arr = _kernel_terms(b, kb, p, True, keep, max(float(np.abs(p).max()), float(np.abs(s).max())))
+        sw = list(item[4]) if len(item) == 5 and item[4] is not None else [None] * len(arr)
+        if len(sw) != len(arr):
+            raise ValueError(f"item {b}: sample_weights has one entry (None or [n]) per term")
+        c_sw = (nat.c_double_p * len(arr))()
+        for t in range(len(arr)):
+            if bool(arr[t].weights) != (sw[t] is not None):
+                raise ValueError(f"item {b}, term {t}: a term has weights at the mesh points and at the sample points, or neither")
+            if sw[t] is None:
+                continue
+            w = _f64(sw[t])
+            if w.shape != (s.shape[0],) or not np.all(np.isfinite(w)) or not np.all(w >= 0.0) or not np.any(w > 0.0):
+                raise ValueError(f"item {b}, term {t}: sample weights are [n], finite, >= 0 and not all zero")
+            keep.append(w)
+            c_sw[t] = _d(w)
+        pts.append(p); smp.append(s); terms.append(arr); rk.append(int(rank)); sws.append(c_sw)
+    R = [3 * s.shape[0] for s in smp]
+    shapes = {"variance": lambda b: (rk[b],), "basis": lambda b: (3 * pts[b].shape[0], rk[b]), "sample_eigenvalues": lambda b: (R[b],),
+              "sample_eigenvectors": lambda b: (R[b], rk[b])}
+    out = [{w: np.zeros(shapes[w](b)) for w in want} for b in range(n)]
+    info = np.zeros((n, 4))
+    status = np.zeros(n, dtype=np.int32)
+    outs = [None if w not in want else _ptr_array([o[w] for o in out]) for w in _NYS_WANT]
+    term_t = nat.KernelTermGeneral
+    c_terms = (C.POINTER(term_t) * n)(*[C.cast(a, C.POINTER(term_t)) for a in terms])
+    c_sws = (C.POINTER(nat.c_double_p) * n)(*[C.cast(a, C.POINTER(nat.c_double_p)) for a in sws])
+    n_pts = np.array([p.shape[0] for p in pts], dtype=np.int32)
+    n_smp = np.array([s.shape[0] for s in smp], dtype=np.int32)
+    n_terms = np.array([len(a) for a in terms], dtype=np.int32)
+    a_rk = np.array(rk, dtype=np.int32)
+    rc = nat.lib().icp_nystrom_models_many(n, int(device), _i(n_pts), _ptr_array(pts), _i(n_smp), _ptr_array(smp), _i(n_terms), c_terms, c_sws,
+                                           _i(a_rk), _d(mv), outs[0], outs[1], outs[2], outs[3], _ptr_array(list(info)), _i(status))
+    if rc != 0 and (not status.any() or not np.all((status == 0) | (status == NYSTROM_NOT_CONVERGED))):
+        nat.check(rc, "icp_nystrom_models_many")  # a whole-call error, or an item the checks above should have refused
+    res = []
+    for b in range(n):
+        ke = int(info[b, 0])
+        d = {"rank": ke, "sweeps": int(info[b, 1]), "trace": float(info[b, 2]), "off_diagonal_mass": float(info[b, 3]), "status": int(status[b])}
+        for w in want:
+            if w != "basis":
+                d[w] = out[b][w]
+        model = None
+        if "variance" in want and "basis" in want:
+            model = _data.StatisticalMeshModel(pts[b], its[b][0].cells, np.zeros_like(pts[b]), out[b]["basis"][:, :ke], out[b]["variance"][:ke])
+        res.append((model, d))
+    return res
+
+
+def nystrom_model(mesh, samples, terms, rank, sample_weights=None, min_variance=1e-8, device=0, want=_NYS_WANT):
+    """One item of nystrom_models: (model, info) of the kernel `terms` on `mesh`, approximated on the sample points `samples`."""
+    return nystrom_models([(mesh, samples, list(terms), rank, sample_weights)], min_variance, device, want)[0]
 
 
 _PCA_WANT = ("variance", "mean", "transforms")

@@ -973,6 +973,46 @@ void launch_gpm_refine(hipStream_t st, int n, int me_max, const GpmSpace* items)
 void launch_gpm_operand(hipStream_t st, int n, int mp_max, int ldb_max, const GpmSpace* items);
 void launch_gpm_gemm(hipStream_t st, int n_pieces, int rows_max, int col_tiles_max, const GpmPiece* pieces);
 
+// ---- Gaussian-process shape models by the Nyström approximation on sample points (kernels_nystrom_model.hip; icp_nystrom_models_many)
+constexpr int kNysMaxRows = 2400;   // R = 3n, at most
+constexpr int kNysMaxRank = 256;
+constexpr int kNysBlock = 32;       // columns of a block of the two-sided block Jacobi iteration; a pair has 2·kNysBlock = 64
+constexpr int kNysMaxSweeps = 40;
+struct NysItem {        // one item's record (device), the same for every launch of the call
+  int n, R, Rp, nb;     // sample points; 3n; R rounded up to an even number of blocks; blocks Rp / 32
+  int N, rank, kp;      // mesh points; eigenpairs asked for; rank rounded up to 16
+  int n_terms, general; // kernel terms; 0: every term is plain and the plain expression runs
+  double min_variance;
+  GpmTerm terms[kGpmMaxTerms];        // (w: the weights at the MESH points)
+  const double* sw[kGpmMaxTerms];     // [n] the weights at the sample points, or null: 1
+  const double* pts;    // [3N]
+  const double* smp;    // [3n]
+  double* A;            // [Rp][Rp] K(S,S), then VᵀKV; padding rows and columns zero
+  double* V;            // [Rp][Rp] the accumulated rotations (columns: eigenvectors)
+  double* U;            // [Rp/64][64][64] the round's pair rotations
+  int* rotated;         // [Rp/64] the round's pairs that were rotated (the others' U is the identity: nothing is applied)
+  double* mass;         // [nb-1][Rp/64] the sweep's pre-rotation off-diagonal mass, per round and pair
+  double* norm;         // [4] ‖K‖_F², trace K, the stop level (R·2⁻⁵²·‖K‖_F)², the rotation threshold
+  int* state;           // [4] done; sweeps used; k_eff; -
+  double* offmass;      // [1] the last sweep's summed mass
+  double* lam;          // [R] eigenvalues, descending
+  int* order;           // [R] order[j] = the column of V of the j-th largest
+  double* W;            // [Rp][kp] the basis product's operand U_k·√n·diag(1/λ), zero padding
+  double* variance;     // [rank] λ/n
+  double* Uk;           // [R][rank] the eigenvectors as handed out
+};
+struct NysPiece {       // rows row0 .. row0+rows-1 of one item's basis, resident in the chunk buffer (device)
+  const NysItem* item;
+  int row0, rows;
+  double* out;          // [rows][rank]
+};
+void launch_nys_kernel_matrix(hipStream_t st, int n_items, int n_max, const NysItem* items);
+// one round of the tournament for every item still iterating: pair decompositions, row panels, column panels
+void launch_nys_round(hipStream_t st, int n_items, int rp_max, int round, const NysItem* items);
+void launch_nys_sweep_end(hipStream_t st, int n_items, const NysItem* items, int* active_word);
+void launch_nys_finish(hipStream_t st, int n_items, int rp_max, int kp_max, const NysItem* items);
+void launch_nys_basis(hipStream_t st, int n_pieces, int rows_max, int col_tiles_max, const NysPiece* pieces);
+
 // ---- PCA shape models from registered meshes, with generalised Procrustes alignment (kernels_pca_model.hip; icp_pca_models_many)
 constexpr int kPcaBlock = 256;      // vertices (centroids, cross-covariance, apply) or rows (mean, centring) a workgroup owns
 constexpr int kPcaMaxRounds = 32;

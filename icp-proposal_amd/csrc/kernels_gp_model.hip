@@ -34,6 +34,7 @@
 // No floating-point atomics anywhere.
 #include "icp_kernels.hpp"
 #include "icp_dense.hpp"
+#include "icp_gp_terms.hpp"
 
 #include <algorithm>
 #include <climits>
@@ -80,31 +81,7 @@ __device__ __forceinline__ double gpm_kernel_value(const GpmItem& it, double x0,
   return acc;
 }
 
-// ---- general terms (icp_gp_models_general_many): B-spline, weighted, mirrored.  One operation at a time (the unit is built without
-// contraction); the lattice indices are doubles, exact below 2^31.
-__device__ __forceinline__ double gpm_beta3(double t) {
-  const double a = fabs(t);
-  if (a < 1.0) return (2.0 / 3.0 - a * a) + ((0.5 * a) * a) * a;
-  if (a < 2.0) return (((1.0 / 6.0) * (2.0 - a)) * (2.0 - a)) * (2.0 - a);
-  return 0.0;
-}
-// S(u, v) = Σ_k β(u − k)·β(v − k), k = ⌈max(u, v) − 2⌉ … ⌊min(u, v) + 2⌋ ascending: at most five k
-__device__ __forceinline__ double gpm_spline_sum(double u, double v) {
-  const double k0 = ceil(fmax(u, v) - 2.0), k1 = floor(fmin(u, v) + 2.0);
-  double s = 0.0;
-  for (double k = k0; k <= k1; k += 1.0) s = s + gpm_beta3(u - k) * gpm_beta3(v - k);
-  return s;
-}
-// the scalar base kernel of a term between x and p
-__device__ __forceinline__ double gpm_base(const GpmTerm& tm, double x0, double x1, double x2, double p0, double p1, double p2) {
-  if (tm.kind == 0) {
-    const double dx = x0 - p0, dy = x1 - p1, dz = x2 - p2;
-    const double d2 = (dx * dx + dy * dy) + dz * dz;
-    return exp(-(d2 / tm.sigma2));
-  }
-  const double c = tm.c;
-  return (gpm_spline_sum(x0 * c, p0 * c) * gpm_spline_sum(x1 * c, p1 * c)) * gpm_spline_sum(x2 * c, p2 * c);
-}
+// ---- general terms (icp_gp_models_general_many): B-spline, weighted, mirrored; the scalar base kernels are icp_gp_terms.hpp's.
 // K[3·v + c][3·vp + cp] of a general item, the terms summed in order: ((scale·(w(v)·w(vp)))·(b(x, p) + (γ·s_c)·b(x, p̄)))·A[c][cp].
 // A plain term among them has gpm_kernel_value's bits (scale·1 = scale, b + 0·b̄ = b).  `pv` is the pivot as GP1 stages it, uniform
 // over the workgroup: the point p [0..2], term t's mirrored point [3 + 3t ..], term t's weight of the pivot's vertex [kGpmPivotW + t].

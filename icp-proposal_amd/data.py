@@ -203,6 +203,28 @@ def femur_kernel(reference_mesh) -> list:
     return [GaussianKernelTerm(10.0, 90.0, b), GaussianKernelTerm(5.0, 40.0, np.eye(3)), GaussianKernelTerm(3.0, 10.0, np.eye(3))]
 
 
+def uniform_mesh_samples(mesh: TriangleMesh, n: int, seed: int = 0, return_cells: bool = False):
+    """n random points on the surface of `mesh`, uniform by area: the stand-in for Scalismo's UniformMeshSampler3D, whose points
+    api.nystrom_models takes as its sample points.  A triangle is drawn with probability proportional to its area, a point in it from
+    uniform barycentric coordinates (the square-root map).  numpy on the host; the same seed gives the same points.
+    -> points [n, 3], and with return_cells the triangle of every point [n] as well."""
+    if int(n) != n or n < 1:
+        raise ValueError("n is a whole number >= 1")
+    p, cells = mesh.points, mesh.cells
+    if cells.shape[0] < 1:
+        raise ValueError("the mesh has no triangle")
+    a, b, c = p[cells[:, 0]], p[cells[:, 1]], p[cells[:, 2]]
+    area = 0.5 * np.linalg.norm(np.cross(b - a, c - a), axis=1)
+    if not (np.all(np.isfinite(area)) and area.sum() > 0.0):
+        raise ValueError("the mesh has no area")
+    rng = np.random.default_rng(seed)
+    tri = rng.choice(cells.shape[0], size=int(n), p=area / area.sum())
+    r1, r2 = np.sqrt(rng.random(int(n))), rng.random(int(n))
+    w = np.stack([1.0 - r1, r1 * (1.0 - r2), r1 * r2], axis=1)
+    pts = w[:, 0:1] * a[tri] + w[:, 1:2] * b[tri] + w[:, 2:3] * c[tri]
+    return (pts, tri.astype(np.int32)) if return_cells else pts
+
+
 def load_femur_model(n_components: int = 50, fixture_dir: str = FIXTURE_DIR) -> StatisticalMeshModel:
     """femur GPMM with `n_components`+1 basis functions (reference: data/femur/femur_gp_model_*-components.h5)."""
     z = np.load(os.path.join(fixture_dir, f"femur_gp_model_{n_components}.npz"))

@@ -47,7 +47,8 @@ typedef enum {
   ICP_ERR_NOT_FINITE = -3,  /* a result is NaN (the Scalismo chain throws on NaN transition probabilities) */
   ICP_ERR_NOT_SPD = -4,     /* a normal-equation matrix failed to factor */
   ICP_ERR_EMPTY = -5,       /* boundary-aware evaluator dropped every point (reference: empty .max throws) */
-  ICP_ERR_BUSY = -6         /* the context is part of a batch between icp_chain_step_batched_issue and _collect / _abandon */
+  ICP_ERR_BUSY = -6,        /* the context is part of a batch between icp_chain_step_batched_issue and _collect / _abandon */
+  ICP_ERR_NOT_CONVERGED = -7 /* icp_nystrom_models_many: an item's iteration hit its cap on sweeps (its outputs are written all the same) */
 } icp_status;
 
 /* api/other/IcpProjectionDirection.scala:19-25.  ModelAndTargetSampling is not a proposal direction: the
@@ -651,6 +652,44 @@ ICP_API int icp_gp_models_general_many(int32_t n_items, int device, const int32_
 ICP_API int icp_region_weights_many(int32_t n_items, int device, const int32_t *n_points, const double *const *points,
                                     const int32_t *n_region, const double *const *region_points, const double *stddev,
                                     double *const *weights_out, int32_t *status);
+
+/* ---- Gaussian-process shape models by the Nystrom approximation on sample points, many in one call.
+ * What apps/femur/CreateGPModel.scala:93 and apps/bfm/CreateGPModel.scala:56 call: LowRankGaussianProcess.approximateGPNystrom(gp,
+ * sampler, numBasisFunctions).  The formulas are this project's restatement [SCALISMO-UNVERIFIED].  Item b: mesh points X
+ * (points[b], [3 * n_points]), sample points S given by the caller (samples[b], [3 * n_samples], n = n_samples; data.uniform_mesh_samples
+ * stands in for UniformMeshSampler3D), the kernel of terms[b] (n_terms[b] general terms: icp_gp_models_general_many's, a plain term
+ * running icp_gp_models_many's expression), rank[b] = k basis functions, min_variance[b] (NULL: 1e-8 for every item):
+ *   1. K = k(S, S), R x R with R = 3n, the terms summed in order; both triangles come from one evaluation
+ *   2. K = U L U^T, eigenvalues descending; all R are handed out (sample_eigenvalues_out[b], [R])
+ *   3. k_eff = the number of i < k with lambda_i / n >= min_variance
+ *   4. variance_out[b][i] = lambda_i / n for every i < k
+ *   5. basis column i = k(X, S) u_i sqrt(n) / lambda_i for i < k_eff: basis_out[b] is [3 * n_points][k] row by row, the columns from
+ *      k_eff on are zero
+ *   6. the mean deformation is zero
+ * sample_eigenvectors_out[b] [R][k]: the device's own u_i, row by row.  info_out[b] [4] = {k_eff, sweeps used, trace K, the
+ * off-diagonal mass (sum of squares) the last sweep met in front of its rotations}.  Every output pointer, and every array of them,
+ * may be NULL.
+ * A term with weights (its `weights` are the region weights at the MESH points, [n_points]) needs the same region weights at the
+ * sample points: sample_weights[b][t], [n_samples], finite, >= 0, at least one positive.  sample_weights, or sample_weights[b], may be
+ * NULL when no term of the call, or of item b, has weights.
+ * Limits, checked for every item before the device is touched (status[b] = ICP_ERR_INVALID_ARG for that item alone, nothing of it
+ * written, its neighbours computed): 1 <= rank <= min(ICP_NYSTROM_MAX_RANK, R); R <= ICP_NYSTROM_MAX_ROWS; min_variance >= 0; finite
+ * points and samples; the terms' checks of icp_gp_models_general_many, the lattice range over points and samples.
+ * The eigenproblem is a two-sided block Jacobi iteration on the device (blocks of 32 columns, R padded with zero rows to an even
+ * number of blocks; the pairs of a round side by side, every pair's rotation the one nearest the identity; row and column panels on
+ * the f64 matrix cores).  An item stops behind the first sweep whose off-diagonal mass is <= (R 2^-52 |K|_F)^2; the host reads one
+ * word per sweep.  After ICP_NYSTROM_MAX_SWEEPS sweeps an item gets ICP_ERR_NOT_CONVERGED, and its outputs are written from the
+ * iteration as it stands.  k(X, S) is never stored: the basis product evaluates it tile by tile and streams its rows through ONE chunk
+ * buffer of ICP_GP_MODELS_CHUNK_BYTES.  An item's bits depend on the item alone.  Returns the first bad item's code, or ICP_OK. */
+#define ICP_NYSTROM_MAX_ROWS 2400
+#define ICP_NYSTROM_MAX_RANK 256
+#define ICP_NYSTROM_MAX_SWEEPS 40
+ICP_API int icp_nystrom_models_many(int32_t n_items, int device, const int32_t *n_points, const double *const *points,
+                                    const int32_t *n_samples, const double *const *samples, const int32_t *n_terms,
+                                    const icp_kernel_term_general *const *terms, const double *const *const *sample_weights,
+                                    const int32_t *rank, const double *min_variance, double *const *variance_out,
+                                    double *const *basis_out, double *const *sample_eigenvalues_out,
+                                    double *const *sample_eigenvectors_out, double *const *info_out, int32_t *status);
 
 /* ---- PCA shape models from registered meshes, with generalised Procrustes alignment, many in one call.
  * What a registration study is made for: meshes in correspondence (all in the model's vertex order) become a statistical shape model,
