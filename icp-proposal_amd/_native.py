@@ -162,6 +162,9 @@ SIGNATURES = {
                                          C.POINTER(c_int_p), c_int_p, C.POINTER(c_int_p), C.POINTER(c_double_p), C.POINTER(c_double_p),
                                          C.POINTER(c_ubyte_p), C.POINTER(c_double_p), C.POINTER(c_int_p), C.POINTER(c_int_p), c_int_p,
                                          c_int_p]),
+    "icp_decimate_many": (C.c_int, [C.c_int32, C.c_int, c_int_p, C.POINTER(c_double_p), c_int_p, C.POINTER(c_int_p), c_int_p, c_int_p, c_int_p,
+                                    C.POINTER(c_int_p), C.POINTER(c_double_p), C.POINTER(c_double_p), C.POINTER(c_int_p), C.POINTER(c_int_p),
+                                    c_int_p]),
     "icp_chain_step":(C.c_int, [C.c_void_p, C.c_int32, C.POINTER(C.c_void_p), C.c_int32, c_double_p, c_double_p, c_double_p,
                                  c_double_p, c_double_p, c_double_p]),
     "icp_chain_step_batched_issue": (C.c_int, [C.c_int32, C.POINTER(C.c_void_p), C.c_int32, C.POINTER(C.c_void_p), C.POINTER(C.c_int32),

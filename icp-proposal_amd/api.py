@@ -14,7 +14,9 @@ reference's src/main/scala/), implemented as thin wrappers over the C ABI (inclu
     ModelToTargetEvaluation / …            api/sampling/evaluators/EvaluationModeType.scala:20-26
 
 Differences forced by the boundary: the Scalismo mesh decimations inside the reference's
-constructors stay with the caller (here: `data.decimated_point_subset`, a deterministic stand-in), and the
+constructors stay outside them — the default is `data.decimated_point_subset`, a stride over the vertex list;
+`decimated_meshes` / `data.decimate` (icp_decimate_many: farthest points and their graph-distance cells, a
+decimation of this library's own kind, not VTK's) give the points to pass as `decimatedTargetPoints=` —, and the
 standard normals of `posterior.sample()` are passed in explicitly (`propose(theta, z)`).
 """
 from __future__ import annotations
@@ -299,7 +301,8 @@ class IcpPosterior:
 
 
 class NonRigidIcpProposal:
-    """NonRigidIcpProposal.scala:30-41.  `projectionDirection` is ModelSampling or TargetSampling."""
+    """NonRigidIcpProposal.scala:30-41.  `projectionDirection` is ModelSampling or TargetSampling.  `decimatedTargetPoints` defaults to
+    data.decimated_point_subset(target, numOfSamplePoints); data.decimate(target, numOfSamplePoints).points is the opt-in alternative."""
 
     def __init__(self, ctx: IcpContext, stepLength: float, tangentialNoise: float, noiseAlongNormal: float,
                  numOfSamplePoints: int, projectionDirection=ModelSampling, boundaryAware: bool = True,
@@ -421,6 +424,8 @@ class AcceptAllEvaluator:
 
 
 def _sides(ctx, numberOfPointsForComparison, decimatedTargetPoints, numDecimatedModelPoints):
+    """the evaluators' two sides: `decimatedTargetPoints` defaults to data.decimated_point_subset(target, n); the points of
+    data.decimate(target, n) are the opt-in alternative"""
     tp = (decimatedTargetPoints if decimatedTargetPoints is not None
           else _data.decimated_point_subset(ctx.target, numberOfPointsForComparison))
     k = int(numDecimatedModelPoints if numDecimatedModelPoints is not None else min(numberOfPointsForComparison, ctx.N))
@@ -1692,3 +1697,83 @@ def prepare_scans(scans, transforms, landmarks=None, cuts=None, mask_ids=None, d
             item["cut_flags"] = flags[b]
         out.append(item)
     return out
+
+
+_DECIMATE_WANT = ("ids", "points", "cells", "labels", "cover2", "counts")
+_DECIMATE_MAX_VERTICES, _DECIMATE_MAX_TRIANGLES, _DECIMATE_MAX_POINTS, _DECIMATE_MAX_MAGNITUDE = 1 << 24, 1 << 26, 65535, 2.0 ** 60
+
+
+def decimated_meshes(meshes, counts, starts=None, device=0, want=_DECIMATE_WANT) -> list:
+    """Many meshes decimated to vertex subsets in one call (icp_decimate_many): per item min(counts[b], M)
+    farthest-point samples from vertex starts[b] (default 0; equal distances go to the lowest id), every vertex labelled with the
+    sample nearest along mesh edges, and the dual triangles of those cells.  A decimation of this library's own kind — VTK's quadric
+    decimation is not reproduced —, deterministic to the bit, whose points are vertices of the input.  Any prefix of "ids" is the
+    decimation to that smaller count: one call at the largest count serves a whole ladder of counts (the triangles and labels belong
+    to the full count).  One count or start serves every item; a list holds one per item.
+    -> one dict per item with the keys of `want`: "ids" [k_eff] int32, "points" [k_eff, 3], "cells" [T_out, 3] int32 (ids into "ids"),
+    "labels" [M] int32 (−1: no sample reaches the vertex), "cover2" [k_eff] (squared covering radius after j + 1 samples), "counts"
+    (k_eff, T_out, sweeps).  The result need not be a manifold: data.mesh_edge_census counts the edges by their triangles."""
+    want = _want(want, _DECIMATE_WANT)
+    meshes = [meshes] if isinstance(meshes, _data.TriangleMesh) else list(meshes)
+    n = len(meshes)
+    if n == 0 or n > 65535:
+        raise ValueError("at least one mesh, at most 65,535 a call")
+    ks = _scan_per_item(counts, n, _is_int_like, "counts")
+    ss = _scan_per_item(0 if starts is None else starts, n, _is_int_like, "starts")
+    pts, cells = [], []
+    for b in range(n):
+        mesh = meshes[b]
+        if not isinstance(mesh, _data.TriangleMesh):
+            raise ValueError(f"item {b}: a data.TriangleMesh")
+        p, c = mesh.points, mesh.cells.reshape(-1, 3)
+        M = p.shape[0]
+        if p.ndim != 2 or p.shape[1] != 3 or M < 1 or M > _DECIMATE_MAX_VERTICES or c.shape[0] > _DECIMATE_MAX_TRIANGLES:
+            raise ValueError(f"item {b}: points are [1 .. 2^24, 3], at most 2^26 triangles")
+        if c.size and (c.min() < 0 or c.max() >= M):
+            raise ValueError(f"item {b}: a triangle's vertex id is out of range")
+        if not (_is_int_like(ks[b]) and 1 <= ks[b] <= _DECIMATE_MAX_POINTS):
+            raise ValueError(f"item {b}: the count is an integer in [1, {_DECIMATE_MAX_POINTS}]")
+        if not (_is_int_like(ss[b]) and 0 <= ss[b] < M):
+            raise ValueError(f"item {b}: the start is a vertex id in [0, {M})")
+        with np.errstate(invalid="ignore"):
+            if not np.all(np.abs(p) <= _DECIMATE_MAX_MAGNITUDE):
+                raise ValueError(f"item {b}: every coordinate is finite and at most 2^60 in magnitude")
+        pts.append(p); cells.append(np.ascontiguousarray(c, dtype=np.int32))
+    n_pts = np.array([p.shape[0] for p in pts], dtype=np.int32)
+    n_tri = np.array([c.shape[0] for c in cells], dtype=np.int32)
+    k_arr, s_arr = np.array(ks, dtype=np.int32), np.array(ss, dtype=np.int32)
+    ids = [np.zeros(k, dtype=np.int32) for k in ks] if "ids" in want else None
+    spts = [np.zeros((k, 3)) for k in ks] if "points" in want else None
+    cover = [np.zeros(k) for k in ks] if "cover2" in want else None
+    labels = [np.zeros(p.shape[0], dtype=np.int32) for p in pts] if "labels" in want else None
+    tris = [np.zeros((c.shape[0], 3), dtype=np.int32) for c in cells] if "cells" in want else None
+    cnt = np.zeros(3 * n, dtype=np.int32)
+    status = np.zeros(n, dtype=np.int32)
+    out_d = lambda a: None if a is None else _ptr_array(a)  # noqa: E731
+    out_i = lambda a: None if a is None else _ptr_array(a, nat.c_int_p, _i)  # noqa: E731
+    rc = nat.lib().icp_decimate_many(n, int(device), _i(n_pts), _ptr_array(pts), _i(n_tri), _ptr_array(cells, nat.c_int_p, _i), _i(k_arr),
+                                     _i(s_arr), _i(cnt), out_i(ids), out_d(spts), out_d(cover), out_i(labels), out_i(tris), _i(status))
+    nat.check(rc, "icp_decimate_many")
+    out = []
+    for b in range(n):
+        ke, to, sw = (int(x) for x in cnt[3 * b:3 * b + 3])
+        item = {}
+        if "ids" in want:
+            item["ids"] = ids[b][:ke].copy()
+        if "points" in want:
+            item["points"] = spts[b][:ke].copy()
+        if "cells" in want:
+            item["cells"] = tris[b][:to].copy()
+        if "labels" in want:
+            item["labels"] = labels[b]
+        if "cover2" in want:
+            item["cover2"] = cover[b][:ke].copy()
+        if "counts" in want:
+            item["counts"] = (ke, to, sw)
+        out.append(item)
+    return out
+
+
+def decimated_mesh(mesh, k, start=0, device=0, want=_DECIMATE_WANT) -> dict:
+    """decimated_meshes for one mesh"""
+    return decimated_meshes([mesh], [k], [start], device, want)[0]

@@ -1073,5 +1073,67 @@ void launch_scan_triangles(hipStream_t st, int n_items, int t_max, const ScanIte
 void launch_scan_prefix(hipStream_t st, int n_items, int n_max, const ScanItem* items);  // block scan, scan of the block totals
 void launch_scan_scatter(hipStream_t st, int n_items, int n_max, const ScanItem* items);
 
+// exclusive prefix of one value per thread over a workgroup of kThreads threads (s: kThreads ints of LDS) -> the prefix; *total = the
+// sum.  Shared by the block scans of kernels_scan_prep.hip and kernels_decimate.hip
+template <int kThreads>
+__device__ __forceinline__ int block_exclusive_scan(int value, int* s, int* total) {
+  const int tid = threadIdx.x;
+  s[tid] = value;
+  __syncthreads();
+  for (int d = 1; d < kThreads; d <<= 1) {
+    const int add = tid >= d ? s[tid - d] : 0;
+    __syncthreads();
+    s[tid] += add;
+    __syncthreads();
+  }
+  const int incl = s[tid];
+  *total = s[kThreads - 1];
+  __syncthreads();
+  return incl - value;
+}
+
+// ---- mesh decimation: farthest points, graph-distance cells, dual triangles (kernels_decimate.hip; icp_decimate_many)
+constexpr int kDecMaxSamples = 65535;     // three labels fit one 64-bit triple key (16 bits each)
+constexpr int kDecBlock = 256;            // threads of the per-element launches; vertices of one selection partial
+constexpr int kDecGroupThreads = 1024;    // the one-workgroup selection: threads ...
+constexpr int kDecGroupPerThread = 8;     // ... and vertices a thread keeps in registers
+constexpr int kDecGroupVertices = 8192;   // = kDecGroupThreads * kDecGroupPerThread: items up to this size take the one-workgroup route
+constexpr int kDecSweepGroup = 8;         // sweeps the host launches between two reads of the flags
+static_assert(kDecGroupVertices == kDecGroupThreads * kDecGroupPerThread, "the one-workgroup route holds every vertex in a register");
+struct DecItem {        // one item's record (device), the same for every launch of its round
+  int M, T, kk, start;  // kk = min(k, M)
+  int nblk;             // cdiv(M, kDecBlock)
+  int group;            // 1: the one-workgroup selection, 0: the general one
+  const double* pts;    // [3M]
+  const int* tris;      // [3T]
+  double* D;            // [M] squared distance to the nearest sample so far (general route)
+  double* pmax;         // [2][nblk] per-block partials (max D, lowest id), double-buffered by the step's parity
+  int* pidx;            // [2][nblk]
+  int* counts;          // [4] k_eff, T_out (filled in by the host), sweeps (host), candidate triangles
+  int* ids;             // [kk]
+  double* spts;         // [3kk] the samples' coordinates
+  double* cover2;       // [kk]
+  unsigned long long* key[2];  // [M] each: (f32 distance bits) << 32 | label, all ones = not reached
+  int* flags;           // [kDecSweepGroup] flags[g] = sweep g of the current group lowered a key of this item
+  int* labels;          // [M]
+  unsigned long long* tkey;    // [T] canonical triple key of a candidate triangle, all ones otherwise
+  unsigned char* keep;  // [T]
+  int* tpre;            // [T] exclusive prefix of keep[] within its tile
+  int* tblk;            // [cdiv(T, kScanTile)] tile totals, then their exclusive prefix
+};
+struct DecTable {       // the duplicate table of one item (sized by the host from the candidate count) and what depends on it
+  unsigned long long* slots;   // [size] keys, all ones = empty
+  unsigned* lowest;     // [size] the lowest original index of the slot's key
+  unsigned mask;        // size - 1, size a power of two >= 2 * candidates
+  int* t_out;           // [1] kept triangles
+  int* cells;           // [3 * cap] rows 0 .. T_out-1: label triples, smallest label first
+  int cap;              // the candidates the table and `cells` were sized for
+};
+void launch_dec_select(hipStream_t st, int n_items, int nblk_max, int kk_max, bool any_group, const DecItem* items);  // nblk_max, kk_max: of the general items (0: none)
+void launch_dec_seed(hipStream_t st, int n_items, int m_max, int kk_max, const DecItem* items);
+void launch_dec_sweep(hipStream_t st, int n_items, int t_max, int slot, int parity, const DecItem* items);
+void launch_dec_candidates(hipStream_t st, int n_items, int n_max, int parity, const DecItem* items);  // n_max = max(M, T)
+void launch_dec_triangles(hipStream_t st, int n_items, int t_max, const DecItem* items, const DecTable* tables);
+
 
 }  // namespace icp

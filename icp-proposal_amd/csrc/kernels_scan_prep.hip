@@ -184,23 +184,6 @@ __global__ void __launch_bounds__(kScanBlock) k_scan_triangles(const ScanItem* _
   }
 }
 
-// exclusive prefix of one value per thread over the workgroup (kScanBlock threads) -> the prefix; *total = the sum
-__device__ __forceinline__ int scan_block_exclusive(int value, int* s, int* total) {
-  const int tid = threadIdx.x;
-  s[tid] = value;
-  __syncthreads();
-  for (int d = 1; d < kScanBlock; d <<= 1) {
-    const int add = tid >= d ? s[tid - d] : 0;
-    __syncthreads();
-    s[tid] += add;
-    __syncthreads();
-  }
-  const int incl = s[tid];
-  *total = s[kScanBlock - 1];
-  __syncthreads();
-  return incl - value;
-}
-
 // S5: blockIdx.z = 0: used[M]; 1: keep[T]
 __global__ void __launch_bounds__(kScanBlock) k_scan_block(const ScanItem* __restrict__ items) {
   const ScanItem& it = items[blockIdx.y];
@@ -219,7 +202,7 @@ __global__ void __launch_bounds__(kScanBlock) k_scan_block(const ScanItem* __res
     sum += b[e];
   }
   int total;
-  int at = scan_block_exclusive(sum, s, &total);
+  int at = block_exclusive_scan<kScanBlock>(sum, s, &total);
 #pragma unroll
   for (int e = 0; e < kScanPerThread; ++e) {
     if (e0 + e < n) pre[e0 + e] = at;
@@ -241,7 +224,7 @@ __global__ void __launch_bounds__(kScanBlock) k_scan_totals(const ScanItem* __re
     const int i = c0 + (int)threadIdx.x;
     const int value = i < tiles ? blk[i] : 0;
     int total;
-    const int at = scan_block_exclusive(value, s, &total);
+    const int at = block_exclusive_scan<kScanBlock>(value, s, &total);
     if (i < tiles) blk[i] = carry + at;
     carry += total;
   }

@@ -83,6 +83,16 @@ class StatisticalMeshModel:
         q = self.basis * np.sqrt(self.variance)[None, :]
         return self.ref_points + self.mean_def + (q @ np.asarray(coeffs, dtype=np.float64)).reshape(-1, 3)
 
+    def decimate(self, k: int, start: int = 0, device: int = 0) -> "StatisticalMeshModel":
+        """The model on its reference mesh decimated to min(k, N) vertices (`decimate` below): the new points are reference vertices, so
+        rows 3·id … 3·id + 2 of the mean deformation and of the basis are gathered as they are and the variances stay — what
+        Scalismo's model.decimate(n) yields when the new points are reference vertices, without its interpolation."""
+        from . import api
+        got = api.decimated_mesh(self.reference_mesh, k, start, device, want=("ids", "points", "cells"))
+        ids = got["ids"].astype(np.int64)
+        rows = (3 * ids[:, None] + np.arange(3)[None, :]).reshape(-1)
+        return StatisticalMeshModel(got["points"], got["cells"], self.mean_def[ids], self.basis[rows], self.variance.copy())
+
 
 def _general_fields(term):
     """A, weights, mirror_gain and mirror_axis of a kernel term, as arrays and numbers"""
@@ -357,6 +367,28 @@ def decimated_point_subset(mesh: TriangleMesh, k: int) -> np.ndarray:
     k = min(k, mesh.n_points)
     idx = (np.arange(k, dtype=np.int64) * mesh.n_points) // k
     return mesh.points[idx].copy()
+
+
+def decimate(mesh: TriangleMesh, k: int, start: int = 0, device: int = 0) -> TriangleMesh:
+    """`mesh` decimated to min(k, M) of its own vertices on the device (api.decimated_meshes, icp_decimate_many):
+    farthest-point samples from vertex `start`, triangles from their graph-distance cells.  Not VTK's quadric decimation (which the
+    reference's mesh.operations.decimate(k) calls and which cannot be reproduced), deterministic to the bit.  Its `.points` are the
+    opt-in alternative to decimated_point_subset for the `decimatedTargetPoints=` arguments; mesh_edge_census says whether the
+    triangles form a manifold."""
+    from . import api
+    got = api.decimated_mesh(mesh, k, start, device, want=("points", "cells"))
+    return TriangleMesh(got["points"], got["cells"])
+
+
+def mesh_edge_census(mesh: TriangleMesh) -> dict:
+    """How many undirected edges of `mesh` lie in exactly one triangle ("boundary"), in two ("interior") and in three or more
+    ("non_manifold"), and the Euler characteristic V − E + F over all its vertices ("euler").  A closed manifold has no boundary and
+    no non-manifold edge; a sphere's Euler characteristic is 2."""
+    c = mesh.cells.astype(np.int64).reshape(-1, 3)
+    e = np.sort(np.concatenate([c[:, [0, 1]], c[:, [1, 2]], c[:, [2, 0]]], axis=0), axis=1)
+    _, cnt = np.unique(e[:, 0] * mesh.n_points + e[:, 1], return_counts=True)
+    return {"boundary": int((cnt == 1).sum()), "interior": int((cnt == 2).sum()), "non_manifold": int((cnt >= 3).sum()),
+            "euler": int(mesh.n_points - cnt.shape[0] + c.shape[0])}
 
 
 def boundary_vertex_flags(mesh: TriangleMesh) -> np.ndarray:

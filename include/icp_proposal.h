@@ -781,6 +781,47 @@ ICP_API int icp_scans_prepare_many(int32_t n_items, int device, const int32_t *n
                                    int32_t *const *partial_triangles_out, int32_t *const *kept_ids_out,
                                    int32_t *counts_out /* [n_items * 2] */, int32_t *status);
 
+/* ---- mesh decimation to a vertex subset, many in one call.
+ * The step in front of every hot-path object of the reference (NonRigidIcpProposal.scala:45-46, the evaluators' constructors,
+ * BfmFittingComplete.scala:45-47, apps/bfm/CreateGPModel.scala:43).  VTK's quadric decimation is a sequential priority queue and is NOT
+ * reproduced: this is a decimation of this library's own kind — farthest-point samples, their graph-distance cells, the cells' dual
+ * triangles — deterministic to the bit, whose vertices are a SUBSET of the input's, so that a model is decimated by a row gather.
+ * Per item b, with M = n_points[b], T = n_triangles[b], k = n_samples[b], kk = min(k, M):
+ *   selection   d2(u, v) = ((dx*dx + dy*dy) + dz*dz) in f64, every operation rounded separately.  ids[0] = starts[b] (starts == NULL:
+ *               0); after j samples D_j(v) = min over i < j of d2(v, ids[i]), and ids[j] is the vertex with the largest D_j: EQUAL
+ *               VALUES GO TO THE LOWEST ID.  If that largest value is 0 every vertex coincides with a sample and the selection stops:
+ *               k_eff = j, otherwise k_eff = kk.  cover2[j] = max over v of D_{j+1}(v), the squared covering radius after j + 1
+ *               samples: finite, not increasing, 0 at the last index when the selection stopped early.  ANY PREFIX OF ids IS THE
+ *               DECIMATION TO THAT SMALLER COUNT: one call at the largest count serves a whole ladder of counts.
+ *   labels      a half-edge (u -> v) for every ordered pair of distinct corners of every triangle, of length (float)sqrt(d2(u, v)):
+ *               the f64 square root, then one rounding to f32.  A vertex's key is the unsigned 64-bit word (bits of its f32
+ *               distance) << 32 | label; sample j starts with (0, j), every other vertex with all ones.  Sweep s:
+ *               key'[v] = min(key[v], min over half-edges (u -> v) with key[u] not all ones of ((f32)(dist[u] + len), label[u])),
+ *               every right-hand side read from sweep s (synchronous); the iteration ends at the first sweep that changes no key of
+ *               the item.  labels[v] = the low word of the final key, -1 for a vertex no sample reaches; equal distances go to the
+ *               lowest label.  sweeps = the number of sweeps that changed a key.
+ *   triangles   triangle t with labels (a, b, c) is a candidate iff all three are >= 0 and pairwise distinct; its canonical form is
+ *               the rotation that puts the smallest label first (the orientation is kept); a candidate is kept iff no candidate of a
+ *               lower index has the same canonical form.  Kept triangles stay in the order of their index; their rows are the
+ *               canonical label triples, ids into `ids`.  The other orientation of a kept triple is a different triple and is kept.
+ *   outputs     counts_out [3 * n_items]: (k_eff, T_out, sweeps); ids_out[b] (caller: [k]), points_out[b] ([3 * k], the samples'
+ *               coordinates bit for bit), cover2_out[b] ([k]): rows 0 .. k_eff - 1; labels_out[b] ([M]); cells_out[b] (caller:
+ *               [3 * T]): rows 0 .. T_out - 1.  The rows behind k_eff and T_out are left untouched.  Every sample is a vertex of the
+ *               result, whether a triangle uses it or not.
+ * Any output array, or any entry of one, may be NULL, but not all six arguments; status may not.  Limits, checked for every item before
+ * the device is touched (status[b] = ICP_ERR_INVALID_ARG, nothing written for that item): 1 <= M <= 2^24, 0 <= T <= 2^26, triangle
+ * ids in [0, M), 1 <= k <= ICP_DECIMATE_MAX_POINTS (three labels fit one 64-bit triple key), 0 <= start < M, every coordinate finite
+ * with |x| <= 2^60 (no length or path sum overflows f32); n_items in [1, 65535].  The items go through the device in rounds of at most
+ * ICP_DECIMATE_ROUND_BYTES (an item above that has a round of its own); an item's bits depend on the item alone.  No floating-point
+ * atomics.  Not covered: lengths below 2^-126 (f32 subnormals) are untested; the result need not be a manifold (data.mesh_edge_census
+ * of the Python layer counts the edges by their triangles). */
+#define ICP_DECIMATE_MAX_POINTS 65535
+#define ICP_DECIMATE_ROUND_BYTES (64u << 20)
+ICP_API int icp_decimate_many(int32_t n_items, int device, const int32_t *n_points, const double *const *points,
+                              const int32_t *n_triangles, const int32_t *const *cells, const int32_t *n_samples, const int32_t *starts,
+                              int32_t *counts_out /* [n_items * 3] */, int32_t *const *ids_out, double *const *points_out,
+                              double *const *cover2_out, int32_t *const *labels_out, int32_t *const *cells_out, int32_t *status);
+
 /* ---------------------------------------------------------------- the per-method entry points as ONE submission per step (round 6)
  * The drop-in contract is "Scalismo's chain, unchanged": MetropolisHastings.next (constructed at
  * api/sampling/SamplingRegistration.scala:52-58) calls  logValue(current) [memoised] → propose(current) → logValue(proposal) →
