@@ -116,6 +116,7 @@ SIGNATURES = {
     "icp_chain_step_prelaunch2": (C.c_int, [C.c_void_p, C.c_int32, C.c_void_p, C.c_int32, C.c_void_p, C.c_void_p, C.c_int32, C.c_void_p,
                                             C.POINTER(C.c_int32)]),
     "icp_ctx_twin_stats": (C.c_int, [C.c_void_p, C.POINTER(C.c_int64)]),
+    "icp_ctx_search_hints": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int32, C.POINTER(C.c_int32), C.c_int32, C.POINTER(C.c_int32)]),
     "icp_ctx_twin_eigen_stats": (C.c_int, [C.c_void_p, C.POINTER(C.c_int64)]),
     "icp_ctx_profile_stop": (C.c_int, [C.c_void_p, C.POINTER(KernelStat), C.c_int32, C.POINTER(C.c_int32)]),
     "icp_chain_eval_step": (C.c_int, [C.c_void_p, C.c_int32, C.POINTER(C.c_void_p), c_double_p, c_double_p, c_double_p,

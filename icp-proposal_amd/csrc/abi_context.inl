@@ -27,6 +27,9 @@ void attach_target(icp_ctx* ctx, const icp_mesh_desc* target, int device) {
       tg.tri_order.upload(order.data(), order.size());
     }
     launch_tri_spheres(ctx->stream, tg.T, tg.verts.p, tg.tris.p, tg.tri_order.p, tg.spheres.p);
+    tg.balls.alloc((size_t)patch_count(tg.T));
+    tg.corner_recs.alloc((size_t)tg.T);
+    launch_target_tables(ctx->stream, tg.T, tg.verts.p, tg.tris.p, tg.spheres.p, tg.balls.p, tg.corner_recs.p);
     HIP_OK(hipStreamSynchronize(ctx->stream));  // (complete before another context may find it)
     g_shared_targets[tkey] = stg;
   }
@@ -35,6 +38,7 @@ void attach_target(icp_ctx* ctx, const icp_mesh_desc* target, int device) {
   const DeviceMesh& o = stg->mesh;
   tg.V = o.V; tg.T = o.T; tg.n_boundary = o.n_boundary;
   tg.verts.alias(o.verts); tg.tris.alias(o.tris); tg.tri_order.alias(o.tri_order); tg.spheres.alias(o.spheres); tg.boundary.alias(o.boundary);
+  tg.balls.alias(o.balls); tg.corner_recs.alias(o.corner_recs);
 }
 }  // namespace
 

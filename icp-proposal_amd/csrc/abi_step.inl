@@ -312,8 +312,16 @@ void front_launches(icp_evaluator* e, int n_props, icp_proposal* const* props, i
                               s.pose, c.ref.p, c.mean.p, c.tris.p, c.adj_off.p, c.adj.p};
     q.v_corr[0] = n_corr++;
   }
-  launch_step_filter(F.stream, q);
-  launch_step_resolve(F.stream, q);
+  // one surface task (the static target) and at most one vertex task of a lone chain: a wave per query, one launch (k_step_search)
+  // (its kernel takes the surface task's posterior, if any, as corr[0]: q.s_corr[0] <= 0 by the order above)
+  const bool one_search = !batched && !ev_t2m && !c.step_search_split && c.target.T > 0 && c.target.balls.p != nullptr &&
+                          (!pt || c.N <= kStepSearchMaxV);
+  if (one_search) {
+    launch_step_search(F.stream, q, c.target.tables());
+  } else {
+    launch_step_filter(F.stream, q);
+    launch_step_resolve(F.stream, q);
+  }
 
   // 4: regressions + likelihood reduction
   StepRegressionArgs g{};
@@ -819,6 +827,19 @@ int icp_ctx_twin_stats(icp_ctx* ctx, int64_t out[3]) {
     require(ctx && out, "null argument");
     std::lock_guard<std::recursive_mutex> lk(ctx->mu);
     for (int i = 0; i < 3; ++i) out[i] = ctx->twin_stats[i];
+  });
+}
+
+int icp_ctx_search_hints(icp_ctx* ctx, icp_proposal* prop, int32_t n_surface, int32_t* surface_out, int32_t n_vertex, int32_t* vertex_out) {
+  return guard([&] {
+    require(ctx && n_surface >= 0 && n_vertex >= 0 && (n_surface == 0 || surface_out) && (n_vertex == 0 || vertex_out), "bad argument");
+    require(n_surface <= ctx->N, "more surface hints asked for than the model has points");
+    require(n_vertex == 0 || (prop && prop->ctx == ctx && n_vertex <= prop->K && prop->hint_nn.p), "vertex hints need a TargetSampling proposal of this context");
+    std::lock_guard<std::recursive_mutex> lk(ctx->mu);
+    ctx->bind();
+    HIP_OK(hipDeviceSynchronize());  // (diagnostic: whatever was launched ahead has written its hints)
+    if (n_surface) HIP_OK(hipMemcpy(surface_out, ctx->hint_surf.p, sizeof(int32_t) * n_surface, hipMemcpyDeviceToHost));
+    if (n_vertex) HIP_OK(hipMemcpy(vertex_out, prop->hint_nn.p, sizeof(int32_t) * n_vertex, hipMemcpyDeviceToHost));
   });
 }
 

@@ -223,6 +223,10 @@ struct DeviceMesh {
   DBuf<int> tri_order;       // position in the sphere list -> triangle (coherent_triangle_order)
   DBuf<float4> spheres;      // sphere_floats4(T): spheres in that order, then the triangle ids
   DBuf<uint8_t> boundary;
+  // a static mesh only (the target): the per-query search's resident tables (TargetTables), made once behind the spheres
+  DBuf<float4> balls;        // patch_count(T)
+  DBuf<CornerRecord> corner_recs;  // T, in sphere-list order
+  TargetTables tables() const { TargetTables t; t.balls = balls.p; t.recs = corner_recs.p; t.npatch = patch_count(T); return t; }
 };
 
 // Immutable device data of one statistical model / one target mesh, shared by every context of a device that was created from
@@ -423,6 +427,8 @@ struct icp_ctx {
   // ICP_NO_PIPELINE=1, or a first launch once timed out on its word (a tool that lets one kernel run at a time, in an order
   // of its own): every step on `stream`, nothing launched ahead, no device-side waits
   bool pipeline_off = std::getenv("ICP_NO_PIPELINE") != nullptr;
+  // ICP_STEP_SEARCH=split: launches 2 and 3 of the lone-chain merged step stay the filter and the resolve launch (k_step_search off)
+  bool step_search_split = std::getenv("ICP_STEP_SEARCH") != nullptr && std::strcmp(std::getenv("ICP_STEP_SEARCH"), "split") == 0;
   bool twin_off = std::getenv("ICP_NO_TWIN") != nullptr;  // ICP_NO_TWIN=1: one step per front (icp_chain_step_prelaunch2 issues one lane)
   bool stream_used_elsewhere = false;           // an entry point other than the chain step has enqueued on `stream`
   int last_back_seq = 0;                         // sequence number of the last finish launch

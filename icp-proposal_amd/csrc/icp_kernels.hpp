@@ -41,7 +41,7 @@ enum KernelId {
   KID_INSTANCE = 0, KID_SURFACE_INIT, KID_SURFACE_FILTER, KID_SURFACE_RESOLVE,
   KID_VERTEX_INIT, KID_VERTEX_FILTER, KID_VERTEX_RESOLVE, KID_TRI_SPHERES, KID_CORRESPOND,
   KID_REGRESSION, KID_FACTOR, KID_TAIL, KID_EIGEN, KID_PROPOSE, KID_REDUCE,
-  KID_STEP_BEGIN, KID_STEP_FILTER, KID_STEP_RESOLVE, KID_STEP_REGRESSION, KID_STEP_FINISH, KID_COUNT
+  KID_STEP_BEGIN, KID_STEP_FILTER, KID_STEP_RESOLVE, KID_STEP_REGRESSION, KID_STEP_FINISH, KID_STEP_SEARCH, KID_COUNT
 };
 extern const char* const kKernelNames[KID_COUNT];
 
@@ -95,6 +95,17 @@ void launch_vertex_normals(hipStream_t st, int N, const double* x, const int* tr
 // `spheres` holds sphere_floats4(T) float4: the T spheres, then the T triangle ids they belong to (position -> triangle)
 void launch_tri_spheres(hipStream_t st, int T, const double* verts, const int* tris, const int* order /* device, or nullptr */,
                         float4* spheres);
+// Resident tables of a STATIC searched mesh (the target), made once behind launch_tri_spheres — what the per-query search of the
+// merged step (k_step_search) reads instead of rebuilding it every step:
+//   balls[p]  the ball (Cx, Cy, Cz, Rw) of patch p = sphere-list positions 128p .. 128p+127, by the arithmetic of surface_filter (the
+//             wave's ball there: same operations in the same order, so the same patches survive); a patch without a finite sphere
+//             has a NaN centre and passes no test
+//   recs      per sphere-list position one CornerRecord: the triangle's corners as the nine f64 that verts[3·tris[3t + …]] hold, and t
+struct alignas(16) CornerRecord { double c[9]; int tri; int pad_; };
+static_assert(sizeof(CornerRecord) == 80, "five aligned 16-byte loads");
+struct TargetTables { const float4* balls = nullptr; const CornerRecord* recs = nullptr; int npatch = 0; };
+inline int patch_count(int T) { return T > 0 ? (T + 127) / 128 : 0; }
+void launch_target_tables(hipStream_t st, int T, const double* verts, const int* tris, const float4* spheres, float4* balls, CornerRecord* recs);
 inline size_t sphere_floats4(int T) { return (size_t)(T > 0 ? T : 0) + ((size_t)(T > 0 ? T : 0) + 3) / 4 + 1; }
 std::vector<int> coherent_triangle_order(int V, int T, const double* verts /* host */, const int* tris /* host */);
 
@@ -467,6 +478,11 @@ bool step_finish_supported(int r);
 void launch_step_begin(hipStream_t st, const StepBeginArgs& a);
 void launch_step_filter(hipStream_t st, const StepSearchArgs& a);
 void launch_step_resolve(hipStream_t st, const StepSearchArgs& a);
+// launches 2 and 3 in one: a wave per query searches the static target through its resident tables (k_step_search; a.s[0] is that
+// search, a.n_surf == 1, a.n_vert <= 1) — no candidate lists, no filter grid.  Same winners, points and hints as the two launches.
+constexpr int kStepSearchMaxV = 8192;  // vertex queries scan the instance per lane: above this many vertices the filter launch is taken
+                                       // (an assumption: 16 vertices a lane and round trip, the old filter's 10 us are 12 rounds — not measured)
+void launch_step_search(hipStream_t st, const StepSearchArgs& a, const TargetTables& t);
 void launch_step_regression(hipStream_t st, const StepRegressionArgs& a);
 void launch_step_finish(hipStream_t st, const StepFinishArgs& a);
 
@@ -477,6 +493,7 @@ void launch_step_finish(hipStream_t st, const StepFinishArgs& a);
 struct StepCapture {
   StepBeginArgs begin; StepSearchArgs search; StepRegressionArgs regression; StepFinishArgs finish;
   int grid[5];
+  TargetTables tables;  // balls != nullptr: launches 2 and 3 are the one per-query search (launch_step_search; grid[1] == 0)
 };
 void step_capture(StepCapture* c);  // nullptr: launch as usual
 size_t step_batch_bytes(int B);

@@ -27,7 +27,7 @@ const char* const kKernelNames[KID_COUNT] = {
     "k_instance", "k_surface_init", "k_surface_filter", "k_surface_resolve",
     "k_vertex_init", "k_vertex_filter", "k_vertex_resolve", "k_tri_spheres", "k_correspond",
     "k_regression", "k_posterior_factor", "k_transition_tail", "k_posterior_eigen", "k_propose", "k_reduce",
-    "k_step_begin", "k_step_filter", "k_step_resolve", "k_step_regression", "k_step_finish"};
+    "k_step_begin", "k_step_filter", "k_step_resolve", "k_step_regression", "k_step_finish", "k_step_search"};
 
 void Profiler::begin(hipStream_t st, int id) {
   if (used >= pool.size()) { overflow = true; return; }
@@ -145,6 +145,46 @@ __global__ void __launch_bounds__(kBlock) k_tri_spheres(int T, const double* __r
   const int t = order ? order[pos] : pos;
   spheres[pos] = tri_sphere(verts, tris, t);
   sphere_triangles(spheres, T)[pos] = t;
+}
+
+// the resident tables of a static mesh (TargetTables).  One wave per patch: lane l holds the spheres at positions 128p + 2l, + 1 and
+// the ball is taken by the operations of surface_filter's wave, in its order (the butterfly sums included) — the same bits.
+__global__ void __launch_bounds__(64) k_patch_balls(int T, const float4* __restrict__ spheres, float4* __restrict__ balls) {
+  const int t0 = ((int)blockIdx.x * 64 + (int)threadIdx.x) * kSpheresPerLane;
+  const bool v0 = t0 < T, v1 = t0 + 1 < T;
+  f2_t cx = {__builtin_nanf(""), __builtin_nanf("")}, cy = cx, cz = cx, R = {0.f, 0.f};
+  if (v0) { const float4 s = spheres[t0]; cx.x = s.x; cy.x = s.y; cz.x = s.z; R.x = s.w; }
+  if (v1) { const float4 s = spheres[t0 + 1]; cx.y = s.x; cy.y = s.y; cz.y = s.z; R.y = s.w; }
+  auto finite4 = [](float a, float b, float c, float d) { return fabsf(a) + fabsf(b) + fabsf(c) + fabsf(d) <= 3.0e38f; };
+  const bool b0 = v0 && finite4(cx.x, cy.x, cz.x, R.x), b1 = v1 && finite4(cx.y, cy.y, cz.y, R.y);
+  float sx = (b0 ? cx.x : 0.f) + (b1 ? cx.y : 0.f), sy = (b0 ? cy.x : 0.f) + (b1 ? cy.y : 0.f), sz = (b0 ? cz.x : 0.f) + (b1 ? cz.y : 0.f);
+  float sn = (b0 ? 1.f : 0.f) + (b1 ? 1.f : 0.f);
+  for (int o = 32; o > 0; o >>= 1) {
+    sx += __shfl_xor(sx, o, 64); sy += __shfl_xor(sy, o, 64); sz += __shfl_xor(sz, o, 64); sn += __shfl_xor(sn, o, 64);
+  }
+  const bool wave_live = sn > 0.f;
+  const float inv_n = wave_live ? 1.f / sn : 0.f;
+  const float Cx = sx * inv_n, Cy = sy * inv_n, Cz = sz * inv_n;
+  float rad = 0.f;
+  if (b0) { const float dx = cx.x - Cx, dy = cy.x - Cy, dz = cz.x - Cz; rad = fmaxf(rad, sqrtf(dx * dx + dy * dy + dz * dz) + R.x); }
+  if (b1) { const float dx = cx.y - Cx, dy = cy.y - Cy, dz = cz.y - Cz; rad = fmaxf(rad, sqrtf(dx * dx + dy * dy + dz * dz) + R.y); }
+  for (int o = 32; o > 0; o >>= 1) rad = fmaxf(rad, __shfl_xor(rad, o, 64));
+  const float Rw = rad * 1.00002f + 2e-5f * (fabsf(Cx) + fabsf(Cy) + fabsf(Cz) + rad);
+  // (no finite sphere: a NaN centre — its squared distance passes no limit, not even an infinite one, as the filter's dead wave offers nothing)
+  if (threadIdx.x == 0) balls[blockIdx.x] = wave_live ? make_float4(Cx, Cy, Cz, Rw) : make_float4(__builtin_nanf(""), __builtin_nanf(""), __builtin_nanf(""), 0.f);
+}
+__global__ void __launch_bounds__(kBlock) k_corner_records(int T, const double* __restrict__ verts, const int* __restrict__ tris,
+                                                            const float4* __restrict__ spheres, CornerRecord* __restrict__ recs) {
+  const int pos = blockIdx.x * kBlock + threadIdx.x;
+  if (pos >= T) return;
+  const int t = sphere_triangles(spheres, T)[pos];
+  CornerRecord r;
+  for (int j = 0; j < 3; ++j) {
+    const int v = tris[3 * t + j];
+    r.c[3 * j] = verts[3 * v]; r.c[3 * j + 1] = verts[3 * v + 1]; r.c[3 * j + 2] = verts[3 * v + 2];
+  }
+  r.tri = t; r.pad_ = 0;
+  recs[pos] = r;
 }
 
 __global__ void __launch_bounds__(kBlock) k_surface_init(SurfaceTask q) { surface_init(q, blockIdx.x * kBlock + threadIdx.x); }
@@ -274,6 +314,13 @@ void launch_tri_spheres(hipStream_t st, int T, const double* verts, const int* t
   if (T <= 0) return;
   ProfScope _ps(st, KID_TRI_SPHERES);
   hipLaunchKernelGGL(k_tri_spheres, dim3(cdiv(T, kBlock)), dim3(kBlock), 0, st, T, verts, tris, order, spheres);
+}
+
+void launch_target_tables(hipStream_t st, int T, const double* verts, const int* tris, const float4* spheres, float4* balls, CornerRecord* recs) {
+  if (T <= 0) return;
+  ProfScope _ps(st, KID_TRI_SPHERES);
+  hipLaunchKernelGGL(k_patch_balls, dim3(patch_count(T)), dim3(64), 0, st, T, spheres, balls);
+  hipLaunchKernelGGL(k_corner_records, dim3(cdiv(T, kBlock)), dim3(kBlock), 0, st, T, verts, tris, spheres, recs);
 }
 
 // Order of the triangles in the sphere list: a k-d split of the centroids (longest box axis, cut at a multiple of 128

@@ -272,6 +272,238 @@ __device__ __forceinline__ void step_resolve_body(const StepSearchArgs& a, const
 
 __global__ void __launch_bounds__(64) k_step_resolve(StepSearchArgs a) { step_resolve_body(a, blockIdx.x); }
 
+// ---------------------------------------------------------------- 2 + 3 in one: per-query search of the static target
+//
+// One wave per query, through the target's resident tables (TargetTables) instead of a filter grid and candidate lists in memory.
+// The two levels, the thresholds and the exact test are those of surface_filter / surface_resolve:
+//   A  the query against every patch ball, 16 balls a lane in flight; the surviving patches are compacted into LDS
+//   B  the two spheres a lane holds of up to eight surviving patches at a time, by the packed-f32 test; the positions that pass are
+//      compacted into LDS — the candidate list of the filter launch (same positions, another order), which never leaves the CU
+//   C  a lane per listed position: its corner record (one lane, five 16-byte loads) and closest_point_triangle; a list longer than
+//      the task's stride is the filter's overflowed list: the scan of every sphere with the shrinking bound, as surface_resolve's
+// so listed and scanned queries are the ones of the two launches, and the winner — the lexicographic (d², triangle) minimum of the
+// same set — its point and the hint are theirs bit for bit.  The ModelSampling correspondence's vertex normal does not depend on
+// the search: its chain of loads (adjacency -> triangles -> corners) is started first and runs beside A–C.
+
+constexpr int kBallsPerLane = 16;   // A: patch balls a lane tests per round (1024 patches a round)
+constexpr int kPatchGroup = 8;      // B: surviving patches whose spheres are fetched together
+
+__device__ __forceinline__ int lanes_below(unsigned long long m) {  // set bits of m below this lane
+  return (int)__builtin_amdgcn_mbcnt_hi((unsigned)(m >> 32), __builtin_amdgcn_mbcnt_lo((unsigned)m, 0u));
+}
+struct CornerLoad { double2 v[5]; };
+__device__ __forceinline__ CornerLoad load_corners(const CornerRecord* __restrict__ recs, int pos) {
+  const double2* p = reinterpret_cast<const double2*>(recs + pos);
+  CornerLoad c;
+#pragma unroll
+  for (int j = 0; j < 5; ++j) c.v[j] = p[j];
+  return c;
+}
+// = tri_dist2 of the record's triangle (the corner values are the ones verts[3·tris[3t + …]] hold)
+__device__ __forceinline__ double corners_dist2(d3 p, const CornerLoad& c, int* t, d3* cp_out) {
+  const d3 a = {c.v[0].x, c.v[0].y, c.v[1].x}, b = {c.v[1].y, c.v[2].x, c.v[2].y}, cc = {c.v[3].x, c.v[3].y, c.v[4].x};
+  *t = (int)(unsigned)(unsigned long long)__double_as_longlong(c.v[4].y);  // (low word: CornerRecord::tri)
+  const d3 cp = closest_point_triangle(p, a, b, cc);
+  *cp_out = cp;
+  const d3 d = sub(p, cp);
+  return dot(d, d);
+}
+
+// has_corr: the query feeds the ModelSampling correspondence `cr` of model vertex k
+__device__ __forceinline__ void search_surface_query(const SurfaceTask& q, const TargetTables& tb, int k, const bool has_corr, const CorrTask& cr) {
+  __shared__ int s_patch[kBallsPerLane * 64];
+  __shared__ int s_pos[kCandStrideMax];
+  const int lane = lane_id();
+  // ---- the normal's chain, first link
+  int nk0 = 0, nk1 = 0;
+  if (has_corr) { nk0 = cr.adj_off[k]; nk1 = cr.adj_off[k + 1]; }
+  const bool normal_ahead = has_corr && nk1 - nk0 <= 64;  // (uniform; a vertex of more than 64 triangles: vertex_normal_wave at the end)
+  const float4 qq = q.qrec[k];
+  const float thr = q.thrA[k];
+  const d3 p = ld3(q.P + 3 * k);
+  int nt = 0;
+  const bool my_cell = normal_ahead && lane < nk1 - nk0;
+  if (my_cell) nt = cr.adj[nk0 + lane];
+  int nia = 0, nib = 0, nic = 0;
+  bool cell_asked = false;
+  d3 na = {0.0, 0.0, 0.0}, nb = na, nc = na;
+  const float qslack = 2e-5f * (fabsf(qq.x) + fabsf(qq.y) + fabsf(qq.z));
+  int n = 0;                 // listed positions (uniform)
+  unsigned n_ball = 0, n_sphere = 0;
+  for (int pb = 0; pb < tb.npatch && n <= q.stride; pb += kBallsPerLane * 64) {
+    // ---- A
+    float4 ball[kBallsPerLane];
+#pragma unroll
+    for (int j = 0; j < kBallsPerLane; ++j) {
+      const int pi = pb + j * 64 + lane;
+      ball[j] = tb.balls[min(pi, tb.npatch - 1)];
+    }
+    if (my_cell && !cell_asked) { nia = cr.tris[3 * nt]; nib = cr.tris[3 * nt + 1]; nic = cr.tris[3 * nt + 2]; }
+    if (pb != 0) __syncthreads();  // (s_patch of the round before has been read)
+    int ns = 0;              // surviving patches of this round (uniform)
+#pragma unroll
+    for (int j = 0; j < kBallsPerLane; ++j) {
+      const int pi = pb + j * 64 + lane;
+      const float Cx = ball[j].x, Cy = ball[j].y, Cz = ball[j].z, Rw = ball[j].w;
+      const float dx = qq.x - Cx, dy = qq.y - Cy, dz = qq.z - Cz;
+      const float lim = thr + Rw + qslack;
+      const bool near = pi < tb.npatch && dx * dx + dy * dy + dz * dz <= lim * lim;
+      const unsigned long long m = __ballot(near);
+      if (near) s_patch[ns + lanes_below(m)] = pi;
+      ns += __popcll(m);
+    }
+    n_ball += (unsigned)min(kBallsPerLane * 64, tb.npatch - pb);
+    n_sphere += (unsigned)ns;
+    if (my_cell && !cell_asked) { na = ld3(cr.x + 3 * nia); nb = ld3(cr.x + 3 * nib); nc = ld3(cr.x + 3 * nic); }
+    cell_asked = true;
+    __syncthreads();
+    // ---- B
+    for (int g = 0; g < ns && n <= q.stride; g += kPatchGroup) {
+      float4 s0[kPatchGroup], s1[kPatchGroup];
+      int pos0[kPatchGroup];
+#pragma unroll
+      for (int u = 0; u < kPatchGroup; ++u) {  // (every load from a valid address — the last survivor's, the last sphere's — and unconditional)
+        const int pi = s_patch[min(g + u, ns - 1)];
+        pos0[u] = pi * 128 + lane * kSpheresPerLane;
+        s0[u] = q.spheres[min(pos0[u], q.T - 1)];
+        s1[u] = q.spheres[min(pos0[u] + 1, q.T - 1)];
+      }
+#pragma unroll
+      for (int u = 0; u < kPatchGroup; ++u) {
+        // past the end of the survivors, or of the list: a NaN centre passes no threshold, not even an infinite one
+        const bool have = g + u < ns;
+        if (!(have && pos0[u] < q.T)) s0[u].x = __builtin_nanf("");
+        if (!(have && pos0[u] + 1 < q.T)) s1[u].x = __builtin_nanf("");
+      }
+#pragma unroll
+      for (int u = 0; u < kPatchGroup; ++u) {
+        const f2_t cx = {s0[u].x, s1[u].x}, cy = {s0[u].y, s1[u].y}, cz = {s0[u].z, s1[u].z}, R = {s0[u].w, s1[u].w};
+        const f2_t tt = f2_t{thr, thr} + R;
+        const f2_t dx = f2_t{qq.x, qq.x} - cx, dy = f2_t{qq.y, qq.y} - cy, dz = f2_t{qq.z, qq.z} - cz;
+        const f2_t dc2 = __builtin_elementwise_fma(dz, dz, __builtin_elementwise_fma(dy, dy, dx * dx));
+        const f2_t t2 = tt * tt;
+        const bool h0 = dc2.x <= t2.x, h1 = dc2.y <= t2.y;
+        const unsigned long long m0 = __ballot(h0), m1 = __ballot(h1);
+        const int i0 = n + lanes_below(m0), i1 = n + __popcll(m0) + lanes_below(m1);
+        if (h0 && i0 < kCandStrideMax) s_pos[i0] = pos0[u];
+        if (h1 && i1 < kCandStrideMax) s_pos[i1] = pos0[u] + 1;
+        n += __popcll(m0) + __popcll(m1);
+      }
+    }
+  }
+  __syncthreads();
+  // ---- C
+  double best = __builtin_inf();
+  int bi = kNoIndex;
+  d3 bc = {__builtin_nan(""), __builtin_nan(""), __builtin_nan("")};
+  const bool listed = n <= q.stride;  // (uniform; q.stride <= kCandStrideMax: every listed position is in s_pos)
+  if (listed) {
+    for (int i = lane; i < n; i += 64) {
+      const CornerLoad cl = load_corners(tb.recs, s_pos[i]);
+      int t; d3 c;
+      const double d2 = corners_dist2(p, cl, &t, &c);
+      if (d2 < best || (d2 == best && t < bi)) { best = d2; bi = t; bc = c; }  // NaN (degenerate triangle) never wins
+    }
+  } else {  // the else branch of surface_resolve, the triangle taken from its record
+    const double thd = (double)thr;
+    double lim2 = thd * thd;
+    for (int pos = lane; pos < q.T; pos += 64) {
+      const float4 s = q.spheres[pos];
+      const double dx = p.x - (double)s.x, dy = p.y - (double)s.y, dz = p.z - (double)s.z;
+      const double dc = sqrt(dx * dx + dy * dy + dz * dz) - (double)s.w;
+      const double lb = dc > 0.0 ? dc * dc * (1.0 - 1e-6) : 0.0;
+      if (lb > lim2) continue;  // (NaN spheres fall through to the exact evaluation)
+      const CornerLoad cl = load_corners(tb.recs, pos);
+      int t; d3 c;
+      const double d2 = corners_dist2(p, cl, &t, &c);
+      if (d2 < best || (d2 == best && t < bi)) { best = d2; bi = t; bc = c; if (d2 < lim2) lim2 = d2; }
+    }
+  }
+  const double my_best = best;
+  const int my_bi = bi;
+  wave_lexmin(best, bi);
+  d3 c = {__builtin_nan(""), __builtin_nan(""), __builtin_nan("")};
+  if (bi != kNoIndex) {  // the winner's closest point sits in a lane that evaluated it (see surface_resolve)
+    const unsigned long long owners = __ballot(my_bi == bi && my_best == best);
+    const int src = __ffsll((long long)owners) - 1;
+    c.x = __shfl(bc.x, src, 64); c.y = __shfl(bc.y, src, 64); c.z = __shfl(bc.z, src, 64);
+  }
+  if (lane == 0) {
+    if (q.cp) { q.cp[3 * k] = c.x; q.cp[3 * k + 1] = c.y; q.cp[3 * k + 2] = c.z; }
+    if (q.d2) q.d2[k] = best;
+    if (q.tri) q.tri[k] = bi == kNoIndex ? -1 : bi;
+    if (q.hint && !q.keep_hint) q.hint[k] = bi == kNoIndex ? -1 : bi;
+    if (q.stats) {
+      atomicAdd(q.stats + 0, (unsigned long long)n_ball);
+      atomicAdd(q.stats + 1, (unsigned long long)n_sphere * 64ull * kSpheresPerLane);
+      atomicAdd(q.stats + 2, (unsigned long long)(listed ? n : q.T));
+    }
+  }
+  if (has_corr && bi != kNoIndex) {  // correspond_model_wave with the normal (nearly) in hand
+    const int aux = cr.nnv ? cr.nnv[k] : -1;
+    const bool on_boundary = (cr.nnv && aux >= 0) ? cr.boundary[aux] != 0 : false;
+    d3 nrm;
+    if (normal_ahead) {  // = vertex_normal_wave: the cell normals one per lane, summed by every lane in ascending position
+      const int cnt = nk1 - nk0;
+      d3 cn = {0.0, 0.0, 0.0};
+      if (lane < cnt) cn = normalized(cross(sub(nb, na), sub(nc, na)));
+      d3 s = {0.0, 0.0, 0.0};
+      for (int j = 0; j < cnt; ++j) { s.x += __shfl(cn.x, j, 64); s.y += __shfl(cn.y, j, 64); s.z += __shfl(cn.z, j, 64); }
+      nrm = normalized(s);
+    } else {
+      nrm = vertex_normal_wave(cr.x, cr.tris, cr.adj_off, cr.adj, k);
+    }
+    if (lane == 0) write_corr(cr.cb, k, k, aux, c, cr.boundary_aware ? !on_boundary : true, nrm, cr.pose, cr.ref, cr.mean);
+  }
+}
+
+// nearest vertex of the new instance: every lane its share of ALL vertices, 16 in flight, by the expressions of vertex_resolve (the
+// listed candidates of the filter are the vertices within the hint's distance: the same lexicographic minimum).  No bound is needed.
+constexpr int kVertsPerLane = 16;
+__device__ __forceinline__ void search_vertex_query(const VertexTask& q, int k, int* idx_out) {
+  const int lane = lane_id();
+  const d3 p = ld3(q.P + 3 * k);
+  double best = __builtin_inf();
+  int bi = kNoIndex;
+  for (int v0 = 0; v0 < q.V; v0 += kVertsPerLane * 64) {
+    d3 e[kVertsPerLane];
+#pragma unroll
+    for (int j = 0; j < kVertsPerLane; ++j) e[j] = ld3(q.verts + 3 * min(v0 + j * 64 + lane, q.V - 1));
+#pragma unroll
+    for (int j = 0; j < kVertsPerLane; ++j) {
+      const int v = v0 + j * 64 + lane;
+      const d3 d = sub(p, e[j]);
+      const double d2 = dot(d, d);
+      if (v < q.V && (d2 < best || (d2 == best && v < bi))) { best = d2; bi = v; }
+    }
+  }
+  wave_lexmin(best, bi);
+  if (lane == 0) {
+    if (q.d2) q.d2[k] = best;
+    if (q.idx) q.idx[k] = bi == kNoIndex ? -1 : bi;
+    if (q.hint && !q.keep_hint) q.hint[k] = bi == kNoIndex ? -1 : bi;
+    if (q.stats) atomicAdd(q.stats + 4, (unsigned long long)q.V);
+  }
+  *idx_out = bi;
+}
+
+struct StepOneSearchArgs { StepSearchArgs a; TargetTables t; };
+static_assert(sizeof(StepTwin<StepOneSearchArgs>) + 64 <= 4096, "both lanes' records must fit the kernel argument segment");
+
+__device__ __forceinline__ void step_search_body(const StepOneSearchArgs& o, const int b) {
+  const StepSearchArgs& a = o.a;
+  if (b < a.rstart[1]) {  // (the surface task's posterior, if any, is the first: launch_step_search)
+    search_surface_query(a.s[0], o.t, b, a.s_corr[0] == 0 && b < a.corr[0].K, a.corr[0]);
+  } else {
+    const int k = b - a.rstart[1], ci = a.v_corr[0];
+    int idx;
+    search_vertex_query(a.v[0], k, &idx);
+    if (ci == 0 && k < a.corr[0].K && idx != kNoIndex) correspond_target_wave(a.corr[0], k, idx);
+    if (ci == 1 && k < a.corr[1].K && idx != kNoIndex) correspond_target_wave(a.corr[1], k, idx);
+  }
+}
+__global__ void __launch_bounds__(64) k_step_search(StepOneSearchArgs o) { step_search_body(o, blockIdx.x); }
+
 // ---------------------------------------------------------------- 4: regression partial sums + likelihood reduction
 
 __device__ __forceinline__ void dist_stats_body(int K, const double* __restrict__ d2, double* __restrict__ out) {
@@ -479,6 +711,11 @@ __global__ void __launch_bounds__(64) k_step_resolve_twin(StepTwin<StepSearchArg
   if ((int)blockIdx.x >= a.rstart[a.n_surf + a.n_vert]) return;
   step_resolve_body(a, blockIdx.x);
 }
+__global__ void __launch_bounds__(64) k_step_search_twin(StepTwin<StepOneSearchArgs> t) {
+  const StepOneSearchArgs& o = t.a[blockIdx.y];
+  if ((int)blockIdx.x >= o.a.rstart[o.a.n_surf + o.a.n_vert]) return;
+  step_search_body(o, blockIdx.x);
+}
 __global__ void __launch_bounds__(kStepBlock) k_step_regression_twin(StepTwin<StepRegressionArgs> t) {
   const StepRegressionArgs& a = t.a[blockIdx.y];
   if ((int)blockIdx.x >= step_regression_grid(a)) return;
@@ -542,7 +779,7 @@ void launch_step_begin(hipStream_t st, const StepBeginArgs& a_in) {
 
 void launch_step_filter(hipStream_t st, const StepSearchArgs& a) {
   const int grid = a.fstart[a.n_surf + a.n_vert];
-  if (t_capture) { t_capture->search = a; t_capture->grid[1] = grid; return; }
+  if (t_capture) { t_capture->search = a; t_capture->grid[1] = grid; t_capture->tables = TargetTables{}; return; }
   if (grid <= 0) return;
   ProfScope _ps(st, KID_STEP_FILTER);
   hipLaunchKernelGGL(k_step_filter, dim3(grid), dim3(kSearchBlock), 0, st, a);
@@ -554,6 +791,14 @@ void launch_step_resolve(hipStream_t st, const StepSearchArgs& a) {
   if (grid <= 0) return;
   ProfScope _ps(st, KID_STEP_RESOLVE);
   hipLaunchKernelGGL(k_step_resolve, dim3(grid), dim3(64), 0, st, a);
+}
+
+void launch_step_search(hipStream_t st, const StepSearchArgs& a, const TargetTables& t) {
+  const int grid = a.rstart[a.n_surf + a.n_vert];
+  if (t_capture) { t_capture->search = a; t_capture->tables = t; t_capture->grid[1] = 0; t_capture->grid[2] = grid; return; }
+  if (grid <= 0) return;
+  ProfScope _ps(st, KID_STEP_SEARCH);
+  hipLaunchKernelGGL(k_step_search, dim3(grid), dim3(64), 0, st, StepOneSearchArgs{a, t});
 }
 
 void launch_step_regression(hipStream_t st, const StepRegressionArgs& a) {
@@ -604,13 +849,21 @@ void launch_step_twin_front(hipStream_t st, const StepCapture& l0, const StepCap
     else if (hold && r >= 32 && r <= 64) hipLaunchKernelGGL(k_step_begin_twin_reg<64>, grid, dim3(kStepBlock), 0, st, t);
     else hipLaunchKernelGGL(k_step_begin_twin, grid, dim3(kStepBlock), 0, st, t);
   }
+  // (both lanes take the same route: one evaluator, one set of proposals)
+  const bool one_search = l0.tables.balls != nullptr && l1.tables.balls != nullptr;
   StepTwin<StepSearchArgs> q;
   q.a[0] = l0.search; q.a[1] = l1.search;
-  if (const int gx = std::max(l0.grid[1], l1.grid[1]); gx > 0) {
+  if (const int gx = std::max(l0.grid[2], l1.grid[2]); one_search && gx > 0) {
+    StepTwin<StepOneSearchArgs> o;
+    o.a[0] = StepOneSearchArgs{l0.search, l0.tables}; o.a[1] = StepOneSearchArgs{l1.search, l1.tables};
+    ProfScope _ps(st, KID_STEP_SEARCH);
+    hipLaunchKernelGGL(k_step_search_twin, dim3(gx, 2), dim3(64), 0, st, o);
+  }
+  if (const int gx = std::max(l0.grid[1], l1.grid[1]); !one_search && gx > 0) {
     ProfScope _ps(st, KID_STEP_FILTER);
     hipLaunchKernelGGL(k_step_filter_twin, dim3(gx, 2), dim3(kSearchBlock), 0, st, q);
   }
-  if (const int gx = std::max(l0.grid[2], l1.grid[2]); gx > 0) {
+  if (const int gx = std::max(l0.grid[2], l1.grid[2]); !one_search && gx > 0) {
     ProfScope _ps(st, KID_STEP_RESOLVE);
     hipLaunchKernelGGL(k_step_resolve_twin, dim3(gx, 2), dim3(64), 0, st, q);
   }

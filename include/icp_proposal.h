@@ -464,6 +464,11 @@ ICP_API int icp_chain_step_prelaunch2(icp_evaluator *e, int32_t n_props, icp_pro
                                       const double *z_or_theta_prop2, int32_t *lanes_issued);
 /* out: twin passes issued, second-lane results used, second-lane results dropped (icp_chain_step_prelaunch2) */
 ICP_API int icp_ctx_twin_stats(icp_ctx *ctx, int64_t out[3]);
+/* Diagnostic: the searches' hints as they stand on the device — the last winning target triangle of model ids 0..n_surface-1 (-1: none
+ * yet), and, for a TargetSampling proposal of the context, the last nearest model vertex of its first n_vertex target points (prop may be
+ * NULL with n_vertex == 0).  Waits for the device. */
+ICP_API int icp_ctx_search_hints(icp_ctx *ctx, icp_proposal *prop, int32_t n_surface, int32_t *surface_out, int32_t n_vertex,
+                                 int32_t *vertex_out);
 /* The speculative decompositions of a twin pass's second lane go out with the first lane's, in one launch (ranks <= 64, the eigen
  * sampler; ICP_TWIN_LATE_EIGEN=1 in the environment — any value but empty or 0 —: at the second lane's own call, as before).  out: second-lane decompositions
  * started early, kept (the second lane's proposal was accepted), cancelled because the first lane's was accepted, started cold. */
