@@ -15,6 +15,7 @@ LIB_PATH = os.environ.get("ICP_LIBRARY_PATH") or os.path.join(_HERE, "libicp_pro
 c_double_p = C.POINTER(C.c_double)
 c_int_p = C.POINTER(C.c_int32)
 c_ubyte_p = C.POINTER(C.c_uint8)
+c_uint64_p = C.POINTER(C.c_uint64)
 
 
 class ModelDesc(C.Structure):
@@ -166,6 +167,12 @@ SIGNATURES = {
     "icp_decimate_many": (C.c_int, [C.c_int32, C.c_int, c_int_p, C.POINTER(c_double_p), c_int_p, C.POINTER(c_int_p), c_int_p, c_int_p, c_int_p,
                                     C.POINTER(c_int_p), C.POINTER(c_double_p), C.POINTER(c_double_p), C.POINTER(c_int_p), C.POINTER(c_int_p),
                                     c_int_p]),
+    "icp_surface_samples_many": (C.c_int, [C.c_int32, C.c_int, c_int_p, C.POINTER(c_double_p), c_int_p, C.POINTER(c_int_p), c_int_p, c_uint64_p,
+                                           C.POINTER(c_double_p), C.POINTER(c_int_p), C.POINTER(c_double_p), C.POINTER(c_int_p),
+                                           C.POINTER(c_double_p), c_int_p]),
+    "icp_kernel_total_variance_many": (C.c_int, [C.c_int32, C.c_int, c_int_p, C.POINTER(c_double_p), c_int_p,
+                                                 C.POINTER(C.POINTER(KernelTermGeneral)), C.POINTER(C.POINTER(c_double_p)), c_double_p,
+                                                 c_int_p]),
     "icp_chain_step":(C.c_int, [C.c_void_p, C.c_int32, C.POINTER(C.c_void_p), C.c_int32, c_double_p, c_double_p, c_double_p,
                                  c_double_p, c_double_p, c_double_p]),
     "icp_chain_step_batched_issue": (C.c_int, [C.c_int32, C.POINTER(C.c_void_p), C.c_int32, C.POINTER(C.c_void_p), C.POINTER(C.c_int32),

@@ -703,7 +703,7 @@ def icp_fits(contexts, theta_inits, numIterations: int, iterationSeq=(1.0, 0.1, 
 
 class IcpBasedSurfaceFitting:
     """api/other/IcpBasedSurfaceFitting.scala:32 — the deterministic non-rigid ICP baseline (posterior MEAN, isotropic noise).
-    `modelPointIds` / `targetPointSamples` stand for the UniformMeshSampler3D draws of :51-53 (made by the caller).
+    `modelPointIds` / `targetPointSamples` stand for the UniformMeshSampler3D draws of :51-53 (made by the caller: data.fit_samples draws them on the device).
     ModelAndTargetSampling draws the direction afresh for every recursion (:63-69); here from np.random.default_rng(seed)
     (direction_schedule) — the reference draws from the unseeded global scala.util.Random, so only the distribution of the
     directions is the reference's, not one fit's draw."""
@@ -1322,7 +1322,7 @@ def nystrom_models(items, min_variance=1e-8, device=0, want=_NYS_WANT):
     """Gaussian-process shape models by the Nyström approximation on sample points, many in one call (icp_nystrom_models_many): what
     apps/femur/CreateGPModel.scala and apps/bfm/CreateGPModel.scala call, LowRankGaussianProcess.approximateGPNystrom.  An item is
     (mesh, samples, terms, rank) or (mesh, samples, terms, rank, sample_weights): a data.TriangleMesh, sample points [n, 3] (the
-    caller's choice; data.uniform_mesh_samples stands in for UniformMeshSampler3D), a kernel as gp_models takes it (a list of
+    caller's choice; data.surface_samples draws them on the device, data.uniform_mesh_samples on the host), a kernel as gp_models takes it (a list of
     data.GaussianKernelTerm and data.BSplineKernelTerm, plain or general) and the number of basis functions, 1 <= rank <= min(256, 3n)
     with 3n <= 2,400.  A term with weights — they are the region weights at the mesh points — needs the same region weights at the sample
     points: sample_weights, one entry per term, None or [n].  K = k(S, S) = U·Λ·Uᵀ; variance_i = λ_i/n; basis column i =
@@ -1777,3 +1777,131 @@ def decimated_meshes(meshes, counts, starts=None, device=0, want=_DECIMATE_WANT)
 def decimated_mesh(mesh, k, start=0, device=0, want=_DECIMATE_WANT) -> dict:
     """decimated_meshes for one mesh"""
     return decimated_meshes([mesh], [k], [start], device, want)[0]
+
+
+_SAMPLES_MAX_VERTICES, _SAMPLES_MAX_TRIANGLES, _SAMPLES_MAX_COUNT, _SAMPLES_MAX_MAGNITUDE = 1 << 24, 1 << 26, 1 << 24, 2.0 ** 60
+SAMPLES_NO_AREA = -3  # ICP_ERR_NOT_FINITE: an item whose every triangle is degenerate has nothing to draw from
+
+
+@dataclasses.dataclass
+class SurfaceSamples:
+    """One item of surface_samples: `points` [n, 3], the triangle of every sample `cells` [n] int32, its barycentric weights `bary`
+    [n, 3] (point = w0·a + w1·b + w2·c), the nearest vertex of every sample `vertex_ids` [n] int32 (None if not asked for; equal
+    distances go to the lowest id), `info` = {"triangles": those with a positive weight, "largest_area", "area"} and `status`: 0, or
+    -3 for a mesh without area (NaN points and weights, −1 ids)."""
+    points: np.ndarray
+    cells: np.ndarray
+    bary: np.ndarray
+    vertex_ids: np.ndarray
+    info: dict
+    status: int = 0
+
+
+def surface_samples(meshes, counts, seeds, device=0, vertex_ids=True) -> list:
+    """Uniform random points on the surfaces of many meshes in one call (icp_surface_samples_many; Scalismo's UniformMeshSampler3D;
+    DESIGN.md §5.19): per item counts[b] points, a triangle drawn in proportion to its area and a point uniform in it, from the
+    counter-based generator of the Dice samples under seeds[b] (0 <= seed < 2^64) — deterministic to the bit, and an item's points
+    depend on nothing but its mesh, count and seed.  Areas are quantised to 2^-32 of the largest triangle: a smaller triangle is never
+    drawn.  With `vertex_ids` every sample also gets its nearest vertex over the whole mesh (findClosestPoint(p).id; equal distances go
+    to the lowest id); one flag for all items, or one per item.  One count or seed serves every item; a list holds one per item.
+    -> one SurfaceSamples per item."""
+    meshes = [meshes] if isinstance(meshes, _data.TriangleMesh) else list(meshes)
+    n = len(meshes)
+    if n == 0 or n > 65535:
+        raise ValueError("at least one mesh, at most 65,535 a call")
+    ks = _scan_per_item(counts, n, _is_int_like, "counts")
+    sd = _scan_per_item(seeds, n, _is_int_like, "seeds")
+    ids_wanted = _scan_per_item(vertex_ids, n, lambda v: isinstance(v, (bool, np.bool_)), "vertex_ids")
+    pts, cells = [], []
+    for b in range(n):
+        mesh = meshes[b]
+        if not isinstance(mesh, _data.TriangleMesh):
+            raise ValueError(f"item {b}: a data.TriangleMesh")
+        p, c = mesh.points, mesh.cells.reshape(-1, 3)
+        M = p.shape[0]
+        if p.ndim != 2 or p.shape[1] != 3 or M < 1 or M > _SAMPLES_MAX_VERTICES or not (1 <= c.shape[0] <= _SAMPLES_MAX_TRIANGLES):
+            raise ValueError(f"item {b}: points are [1 .. 2^24, 3], 1 to 2^26 triangles")
+        if c.min() < 0 or c.max() >= M:
+            raise ValueError(f"item {b}: a triangle's vertex id is out of range")
+        if not (_is_int_like(ks[b]) and 1 <= ks[b] <= _SAMPLES_MAX_COUNT):
+            raise ValueError(f"item {b}: the count is an integer in [1, 2^24]")
+        if not (_is_int_like(sd[b]) and 0 <= sd[b] < 2 ** 64):
+            raise ValueError(f"item {b}: the seed is an integer in [0, 2^64)")
+        if not isinstance(ids_wanted[b], (bool, np.bool_)):
+            raise ValueError(f"item {b}: vertex_ids is True or False")
+        with np.errstate(invalid="ignore"):
+            if not np.all(np.abs(p) <= _SAMPLES_MAX_MAGNITUDE):
+                raise ValueError(f"item {b}: every coordinate is finite and at most 2^60 in magnitude")
+        pts.append(p); cells.append(np.ascontiguousarray(c, dtype=np.int32))
+    n_pts = np.array([p.shape[0] for p in pts], dtype=np.int32)
+    n_tri = np.array([c.shape[0] for c in cells], dtype=np.int32)
+    k_arr, s_arr = np.array(ks, dtype=np.int32), np.array([int(s) for s in sd], dtype=np.uint64)
+    spts = [np.zeros((k, 3)) for k in ks]
+    scells = [np.zeros(k, dtype=np.int32) for k in ks]
+    bary = [np.zeros((k, 3)) for k in ks]
+    vids = [np.zeros(k, dtype=np.int32) if ids_wanted[b] else None for b, k in enumerate(ks)]
+    info = np.zeros((n, 4))
+    status = np.zeros(n, dtype=np.int32)
+    rc = nat.lib().icp_surface_samples_many(n, int(device), _i(n_pts), _ptr_array(pts), _i(n_tri), _ptr_array(cells, nat.c_int_p, _i),
+                                            _i(k_arr), s_arr.ctypes.data_as(nat.c_uint64_p), _ptr_array(spts),
+                                            _ptr_array(scells, nat.c_int_p, _i), _ptr_array(bary), _ptr_array(vids, nat.c_int_p, _i),
+                                            _ptr_array(list(info)), _i(status))
+    if rc != 0 and (not status.any() or not np.all((status == 0) | (status == SAMPLES_NO_AREA))):
+        nat.check(rc, "icp_surface_samples_many")  # a whole-call error, or an item the checks above should have refused
+    return [SurfaceSamples(spts[b], scells[b], bary[b], vids[b],
+                           {"triangles": int(info[b, 0]), "largest_area": float(info[b, 1]), "area": float(info[b, 2])}, int(status[b]))
+            for b in range(n)]
+
+
+def total_variance(points_list, kernels, point_weights=None, device=0) -> np.ndarray:
+    """The mean trace of a kernel at given points, many in one call (icp_kernel_total_variance_many; apps/femur/CreateGPModel.scala:38-46,
+    approxTotalVariance): item b is the mean over points_list[b] [n, 3] of trace k(x, x) for kernels[b], a kernel as gp_models takes it
+    (`kernels`: one list of terms for every item, or one list per item).  A term's own `weights` belong to a mesh's vertices and are not
+    read: a weighted term needs its region weights AT THESE POINTS, point_weights[b][t] ([n]; None for a term without weights; see
+    region_weights).  One bare [n, 3] array is one item, and point_weights then that item's list.  The sum has a fixed shape that depends on n alone, so an item's bits depend on the item alone.  -> [n_items]."""
+    single = isinstance(points_list, np.ndarray)
+    ps = [points_list] if single else list(points_list)
+    n = len(ps)
+    if n == 0 or n > 65535:
+        raise ValueError("at least one item, at most 65,535 a call")
+    ks = list(kernels)
+    if len(ks) > 0 and isinstance(ks[0], _KERNEL_TERMS):
+        ks = [ks] * n
+    if len(ks) != n:
+        raise ValueError("kernels: one list of terms, or one list per item")
+    pws = [None] * n if point_weights is None else [point_weights] if single else list(point_weights)
+    if len(pws) != n:
+        raise ValueError("point_weights: None, or one list (an entry per term) per item")
+    keep, pts, terms, c_pws = [], [], [], []
+    for b in range(n):
+        p = _f64(ps[b])
+        if p.ndim != 2 or p.shape[1] != 3 or not (1 <= p.shape[0] <= _SAMPLES_MAX_COUNT) or not np.all(np.isfinite(p)):
+            raise ValueError(f"item {b}: points are [1 .. 2^24, 3] and finite")
+        kb = list(ks[b])
+        pw = [None] * len(kb) if pws[b] is None else list(pws[b])
+        if len(pw) != len(kb):
+            raise ValueError(f"item {b}: point_weights has one entry (None or [n]) per term")
+        bare = [dataclasses.replace(k, weights=None) if isinstance(k, _KERNEL_TERMS) else k for k in kb]
+        arr = _kernel_terms(b, bare, p, True, keep)
+        c_pw = (nat.c_double_p * len(arr))()
+        for t in range(len(arr)):
+            if (kb[t].weights is not None) != (pw[t] is not None):
+                raise ValueError(f"item {b}, term {t}: a term with weights needs them at these points (point_weights), a term without has none")
+            if pw[t] is None:
+                continue
+            w = _f64(pw[t])
+            if w.shape != (p.shape[0],) or not np.all(np.isfinite(w)) or not np.all(w >= 0.0) or not np.any(w > 0.0):
+                raise ValueError(f"item {b}, term {t}: point weights are [n], finite, >= 0 and not all zero")
+            keep.append(w)
+            c_pw[t] = _d(w)
+        pts.append(p); terms.append(arr); c_pws.append(c_pw)
+    term_t = nat.KernelTermGeneral
+    c_terms = (C.POINTER(term_t) * n)(*[C.cast(a, C.POINTER(term_t)) for a in terms])
+    c_w = (C.POINTER(nat.c_double_p) * n)(*[C.cast(a, C.POINTER(nat.c_double_p)) for a in c_pws])
+    n_pts = np.array([p.shape[0] for p in pts], dtype=np.int32)
+    n_terms = np.array([len(a) for a in terms], dtype=np.int32)
+    out = np.zeros(n)
+    status = np.zeros(n, dtype=np.int32)
+    rc = nat.lib().icp_kernel_total_variance_many(n, int(device), _i(n_pts), _ptr_array(pts), _i(n_terms), c_terms, c_w, _d(out), _i(status))
+    nat.check(rc, "icp_kernel_total_variance_many")
+    return out

@@ -27,6 +27,7 @@
 #include "abi_nystrom_models.inl"  // C ABI: icp_nystrom_models_many (GP shape models by the Nyström approximation on sample points, kernels_nystrom_model.hip)
 #include "abi_scan_prep.inl"  // C ABI: icp_scans_prepare_many (aligned and partial targets of many raw scans, kernels_scan_prep.hip)
 #include "abi_decimate.inl"  // C ABI: icp_decimate_many (decimation of many meshes to vertex subsets, kernels_decimate.hip)
+#include "abi_samples.inl"  // C ABI: icp_surface_samples_many / icp_kernel_total_variance_many (uniform surface samples with nearest vertices; a kernel's mean trace, kernels_samples.hip)
 #include "abi_step.inl"  // the merged step (five launches): flag poll, argument checks and finish arguments its entry points share; fronts, speculative decompositions, icp_chain_step_prelaunch; icp_chain_step in phases
 #include "abi_wide.inl"  // the wide step's host side (kernels_wide.hip)
 #include "abi_batched.inl"  // C ABI: icp_chain_step_batched (_issue / _collect / _abandon), icp_chain_step_path, icp_proposal_basis_state

@@ -1091,19 +1091,19 @@ void launch_scan_prefix(hipStream_t st, int n_items, int n_max, const ScanItem* 
 void launch_scan_scatter(hipStream_t st, int n_items, int n_max, const ScanItem* items);
 
 // exclusive prefix of one value per thread over a workgroup of kThreads threads (s: kThreads ints of LDS) -> the prefix; *total = the
-// sum.  Shared by the block scans of kernels_scan_prep.hip and kernels_decimate.hip
-template <int kThreads>
-__device__ __forceinline__ int block_exclusive_scan(int value, int* s, int* total) {
+// sum.  Shared by the block scans of kernels_scan_prep.hip and kernels_decimate.hip (int) and of kernels_samples.hip (64-bit weights)
+template <int kThreads, typename V = int>
+__device__ __forceinline__ V block_exclusive_scan(V value, V* s, V* total) {
   const int tid = threadIdx.x;
   s[tid] = value;
   __syncthreads();
   for (int d = 1; d < kThreads; d <<= 1) {
-    const int add = tid >= d ? s[tid - d] : 0;
+    const V add = tid >= d ? s[tid - d] : V(0);
     __syncthreads();
     s[tid] += add;
     __syncthreads();
   }
-  const int incl = s[tid];
+  const V incl = s[tid];
   *total = s[kThreads - 1];
   __syncthreads();
   return incl - value;
@@ -1151,6 +1151,40 @@ void launch_dec_seed(hipStream_t st, int n_items, int m_max, int kk_max, const D
 void launch_dec_sweep(hipStream_t st, int n_items, int t_max, int slot, int parity, const DecItem* items);
 void launch_dec_candidates(hipStream_t st, int n_items, int n_max, int parity, const DecItem* items);  // n_max = max(M, T)
 void launch_dec_triangles(hipStream_t st, int n_items, int t_max, const DecItem* items, const DecTable* tables);
+
+// ---- uniform surface samples and a kernel's total variance (kernels_samples.hip; icp_surface_samples_many, icp_kernel_total_variance_many)
+constexpr int kSmpBlock = 256;            // threads of every launch; samples of one workgroup of the pick and of the nearest-vertex search
+constexpr int kSmpVertexTile = 1024;      // vertices of one LDS tile of the nearest-vertex search (24 KiB)
+struct SmpItem {        // one item's record (device), the same for every launch of its round
+  int M, T, n, tiles;   // vertices, triangles, samples; tiles = cdiv(T, kScanTile)
+  int want_ids;         // 0: the nearest-vertex search returns at once for this item
+  unsigned long long seed;
+  const double* pts;    // [3M]
+  const int* tris;      // [3T]
+  double* a2;           // [T] twice the area (0 where it is not finite)
+  double* tmax;         // [tiles] the largest a2 of a tile
+  unsigned long long* C;     // [T] inclusive prefix of the integer weights q within the tile; + tblk[tile] = the item's prefix
+  unsigned long long* tblk;  // [tiles] tile totals, then their exclusive prefix
+  int* tcnt;            // [tiles] triangles of the tile with q > 0
+  unsigned long long* Q;     // [1] the sum of all weights; 0: nothing to draw from
+  double* info;         // [4] outputs from here on
+  double* opts;         // [3n]
+  int* ocells;          // [n]
+  double* obary;        // [3n]
+  int* oids;            // [n]
+};
+void launch_smp_weights(hipStream_t st, int n_items, int t_max, const SmpItem* items);   // stages 1-3: areas, integer weights, their prefix
+void launch_smp_pick(hipStream_t st, int n_items, int n_max, const SmpItem* items);      // stage 4
+void launch_smp_nearest(hipStream_t st, int n_items, int n_max, const SmpItem* items);   // stage 5
+constexpr int kTvBlock = 256;             // consecutive points of one block of the trace sum: a function of n alone
+struct TvItem {         // one item of icp_kernel_total_variance_many (device)
+  int n, n_terms, nblk; // points; kernel terms; cdiv(n, kTvBlock)
+  GpmTerm terms[kGpmMaxTerms];  // (w: the weights at THESE points, or null)
+  const double* pts;    // [3n]
+  double* bsum;         // [nblk] block sums
+  double* out;          // [1] the mean trace
+};
+void launch_tv(hipStream_t st, int n_items, int n_max, const TvItem* items);
 
 
 }  // namespace icp

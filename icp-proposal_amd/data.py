@@ -235,6 +235,56 @@ def uniform_mesh_samples(mesh: TriangleMesh, n: int, seed: int = 0, return_cells
     return (pts, tri.astype(np.int32)) if return_cells else pts
 
 
+def surface_samples(mesh: TriangleMesh, n: int, seed: int = 0, device: int = 0):
+    """n uniform random points on the surface of `mesh` on the device, with the triangle, the barycentric weights and the nearest
+    vertex of every point (api.surface_samples, icp_surface_samples_many): Scalismo's UniformMeshSampler3D,
+    deterministic to the bit under `seed`.  -> an api.SurfaceSamples; a mesh without area raises."""
+    from . import api
+    got = api.surface_samples([mesh], [n], [seed], device)[0]
+    if got.status != 0:
+        raise ValueError("the mesh has no area")
+    return got
+
+
+def approx_total_variance(mesh: TriangleMesh, kernel, n: int = 50000, seed: int = 1024, device: int = 0, mask=None) -> float:
+    """apps/femur/CreateGPModel.scala:38-46, approxTotalVariance: the mean of trace k(x, x) over n uniform surface samples of `mesh`
+    (surface_samples), for `kernel`, a list of kernel terms as api.gp_models takes it.  The reference's "ratio of approximated
+    variance" of a model built from that kernel (:96) is
+
+        variance.sum() / approx_total_variance(mesh, kernel)
+
+    with `variance` the model's eigenvalues (api.nystrom_models, api.gp_models).  A term with weights — api.face_kernel(mesh, mask) —
+    needs the `mask` (a FaceMask) it was made from: the smoothed region weights of the term's level are computed AT THE SAMPLES
+    (api.region_weights, stddev 40), all levels in one call."""
+    from . import api
+    smp = api.surface_samples([mesh], [n], [seed], device, vertex_ids=False)[0]
+    if smp.status != 0:
+        raise ValueError("the mesh has no area")
+    terms = list(kernel)
+    weighted = [t for t, k in enumerate(terms) if getattr(k, "weights", None) is not None]
+    pw = None
+    if weighted:
+        if mask is None or not all(isinstance(terms[t], BSplineKernelTerm) for t in weighted):
+            raise ValueError("a kernel with weighted terms needs the FaceMask its B-spline terms' weights were made from")
+        ws = api.region_weights([smp.points] * len(weighted), [mask.region(mesh, terms[t].level) for t in weighted], 40.0, device)
+        pw = [None] * len(terms)
+        for t, w in zip(weighted, ws):
+            pw[t] = w
+        pw = [pw]
+    return float(api.total_variance([smp.points], [terms], pw, device)[0])
+
+
+def fit_samples(model: StatisticalMeshModel, target: TriangleMesh, n: int, seed: int = 0, device: int = 0):
+    """IcpBasedSurfaceFitting.scala:51-53: n uniform samples of the model's reference mesh, reduced to their nearest vertex ids, and n
+    uniform samples of the target's surface — the `modelPointIds` / `targetPointSamples` of api.icp_fits and
+    api.IcpBasedSurfaceFitting.  ONE device call with two items (api.surface_samples).  -> (ids [n] int32, points [n, 3])."""
+    from . import api
+    ref, tgt = api.surface_samples([model.reference_mesh, target], [n, n], [seed, seed], device, vertex_ids=[True, False])
+    if ref.status != 0 or tgt.status != 0:
+        raise ValueError("the model's reference mesh or the target has no area")
+    return ref.vertex_ids, tgt.points
+
+
 def load_femur_model(n_components: int = 50, fixture_dir: str = FIXTURE_DIR) -> StatisticalMeshModel:
     """femur GPMM with `n_components`+1 basis functions (reference: data/femur/femur_gp_model_*-components.h5)."""
     z = np.load(os.path.join(fixture_dir, f"femur_gp_model_{n_components}.npz"))

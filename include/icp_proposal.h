@@ -239,7 +239,7 @@ ICP_API int icp_prior_log_value(int32_t rank, const double *theta, double *out);
  * sigma2 of the sequence (:36-40: 1, 0.1, 0.01) the recursion (:55-104) runs numIterations + 1 times: instance, correspondences
  * in one direction (:71-79), GP regression with ISOTROPIC noise sigma2 (:81), posterior MEAN (:82), its coefficients (:84), step
  * (:85).  The sample ids / sample points are drawn by Scalismo's UniformMeshSampler3D in the reference (:51-53) and are inputs
- * here; so is the per-iteration direction draw of ModelAndTargetSampling (:66-69: icp_fit_deterministic_many takes a schedule
+ * here (icp_surface_samples_many draws such ids and points); so is the per-iteration direction draw of ModelAndTargetSampling (:66-69: icp_fit_deterministic_many takes a schedule
  * of directions).  All iterations run on the device without host round trips.  theta_out = theta_init with the fitted shape
  * coefficients. */
 typedef struct {
@@ -661,8 +661,8 @@ ICP_API int icp_region_weights_many(int32_t n_items, int device, const int32_t *
 /* ---- Gaussian-process shape models by the Nystrom approximation on sample points, many in one call.
  * What apps/femur/CreateGPModel.scala:93 and apps/bfm/CreateGPModel.scala:56 call: LowRankGaussianProcess.approximateGPNystrom(gp,
  * sampler, numBasisFunctions).  The formulas are this project's restatement [SCALISMO-UNVERIFIED].  Item b: mesh points X
- * (points[b], [3 * n_points]), sample points S given by the caller (samples[b], [3 * n_samples], n = n_samples; data.uniform_mesh_samples
- * stands in for UniformMeshSampler3D), the kernel of terms[b] (n_terms[b] general terms: icp_gp_models_general_many's, a plain term
+ * (points[b], [3 * n_points]), sample points S given by the caller (samples[b], [3 * n_samples], n = n_samples; icp_surface_samples_many
+ * draws them as UniformMeshSampler3D does), the kernel of terms[b] (n_terms[b] general terms: icp_gp_models_general_many's, a plain term
  * running icp_gp_models_many's expression), rank[b] = k basis functions, min_variance[b] (NULL: 1e-8 for every item):
  *   1. K = k(S, S), R x R with R = 3n, the terms summed in order; both triangles come from one evaluation
  *   2. K = U L U^T, eigenvalues descending; all R are handed out (sample_eigenvalues_out[b], [R])
@@ -826,6 +826,65 @@ ICP_API int icp_decimate_many(int32_t n_items, int device, const int32_t *n_poin
                               const int32_t *n_triangles, const int32_t *const *cells, const int32_t *n_samples, const int32_t *starts,
                               int32_t *counts_out /* [n_items * 3] */, int32_t *const *ids_out, double *const *points_out,
                               double *const *cover2_out, int32_t *const *labels_out, int32_t *const *cells_out, int32_t *status);
+
+/* ---- uniform surface samples of many meshes, with the nearest vertex of every sample, many in one call.
+ * Scalismo's UniformMeshSampler3D as the reference draws from it: IcpBasedSurfaceFitting.scala:51-53 (target points, model points and
+ * their nearest vertex ids), apps/femur/CreateGPModel.scala:92-93 and apps/bfm/CreateGPModel.scala:55-56 (the sample points of
+ * approximateGPNystrom), apps/femur/CreateGPModel.scala:38-46 (approxTotalVariance).  The generator is this library's own, so the
+ * points are not Scalismo's; the law is: a triangle in proportion to its area, a point uniform in it.  Deterministic to the bit.
+ * Per item b, with M = n_points[b], T = n_triangles[b], n = n_samples[b], seed = seeds[b]; all floating point f64 with every operation
+ * rounded separately:
+ *   weights     triangle t with corners a, b, c: e1 = b - a, e2 = c - a, the normal (e1y*e2z - e1z*e2y, e1z*e2x - e1x*e2z,
+ *               e1x*e2y - e1y*e2x) - two products and one subtraction per component -, A2_t = sqrt((nx*nx + ny*ny) + nz*nz), twice
+ *               the area (a value that is not finite counts as 0; within the limits below there is none).  Amax = the largest A2_t.
+ *               q_t = (uint64) trunc((A2_t / Amax) * 2^32), AN INTEGER WEIGHT in [0, 2^32]; C_t = q_0 + ... + q_t in 64-bit integers,
+ *               Q = C_{T-1} < 2^58.  Integers, because a floating-point prefix sum would tie an item's bits to the shape of the scan.
+ *               DEVIATION from sampling by exact area: A TRIANGLE BELOW 2^-32 OF THE LARGEST IS NEVER DRAWN, and every other
+ *               probability is off by at most 2^-32 relative to the largest triangle's.
+ *   draws       h(seed, step, lane) = splitmix64(splitmix64(splitmix64(seed) ^ step * 0xD1342543DE82EF95) ^ lane * 0x2545F4914F6CDD1D)
+ *               >> 11, a 53-bit integer (splitmix64(x): x += 0x9E3779B97F4A7C15; x = (x ^ x >> 30) * 0xBF58476D1CE4E5B9;
+ *               x = (x ^ x >> 27) * 0x94D049BB133111EB; x ^ x >> 31), and u(seed, step, lane) = (h + 0.5) * 2^-53: the generator of
+ *               icp_mesh_metrics_many's Dice samples.  Sample k: x = (h(seed, 0, k) * Q) >> 53, the high word of the 64 x 64 bit
+ *               product (h << 11) * Q, in [0, Q - 1]; its triangle is THE FIRST t WITH C_t > x (a triangle of weight 0 is never
+ *               chosen); r = sqrt(u(seed, 1, k)), v = u(seed, 2, k); w0 = 1 - r, w1 = r * (1 - v), w2 = r * v;
+ *               p = (w0 * a + w1 * b) + w2 * c per coordinate.
+ *   nearest     vertex_ids_out[b][k] = the lexicographic minimum of (d2, id) over ALL M vertices, d2 = (dx*dx + dy*dy) + dz*dz from p:
+ *               EQUAL DISTANCES GO TO THE LOWEST ID.  Not the nearest of the triangle's three corners: on a needle triangle some
+ *               other vertex is nearer.  (Scalismo's findClosestPoint(p).id; its KD-tree leaves ties open.)
+ *   outputs     points_out[b] [3 * n], cells_out[b] [n] (the triangle of every sample), bary_out[b] [3 * n] (w0, w1, w2),
+ *               vertex_ids_out[b] [n], info_out[b] [4] = {triangles with q_t > 0, 0.5 * Amax, the surface area as
+ *               (0.5 * Amax) * ((double)Q * 2^-32), 0}.  Every output array, and every entry of one, may be NULL, but not all five
+ *               arguments; status may not.  The nearest-vertex launch is skipped for a round in which no item asks for ids.
+ * Limits, checked for every item before the device is touched (status[b] = ICP_ERR_INVALID_ARG for that item alone, nothing of it
+ * written, its neighbours computed): 1 <= M <= 2^24, 1 <= T <= 2^26, triangle ids in [0, M), 1 <= n <= 2^24, every coordinate finite
+ * with |x| <= 2^60, non-null points[b] and cells[b].  Whole-call errors (nothing has run, nothing is written): n_items outside
+ * [1, 65535], a null required argument, no output at all; ICP_ERR_DEVICE.
+ * Decided on the device: an item whose every A2_t is 0 has nothing to draw from: status[b] = ICP_ERR_NOT_FINITE, NaN in its double
+ * outputs, -1 in its int outputs, info = {0, 0, 0, 0}; the other items complete.
+ * The call takes no context.  The items go through the device in rounds of at most ICP_SURFACE_SAMPLES_ROUND_BYTES (an item above
+ * that has a round of its own), one upload, one copy back and one synchronisation per round; per round one grid per stage for all its
+ * items: areas and tile maxima; Amax, q and tile totals; tile offsets; pick and point; nearest vertex.  No atomics.  An item's bits
+ * depend neither on the other items, nor on their order, nor on the rounds, nor on which outputs are asked for.
+ *
+ * icp_kernel_total_variance_many: approxTotalVariance, many in one call.  Item b: the mean over its n = n_points[b] points (any points,
+ * [3 * n]; the reference takes 50,000 surface samples) of the trace of k(x, x).  Per point and component c the diagonal entry is the
+ * term expression of icp_gp_models_general_many at y = x, ((scale * (w(x) * w(x))) * (b(x, x) + (gain * s_c) * b(x, xm))) * A[c][c],
+ * the terms summed in order; the trace is (entry 0 + entry 1) + entry 2.  A term's `weights` field is NOT read: the weights at these
+ * points are point_weights[b][t] ([n], finite, >= 0, at least one positive), NULL where the term has none; point_weights, or
+ * point_weights[b], may be NULL.  The sum has a shape that depends on n alone: blocks of 256 consecutive points, inside a block
+ * tr[i] += tr[i + s] for s = 128, 64, ..., 1 with +0.0 for the entries past n, the block sums added in block order, the result
+ * divided by n: total_variance_out[b].  Limits (status[b] = ICP_ERR_INVALID_ARG, total_variance_out[b] untouched): 1 <= n <= 2^24,
+ * finite points, 1 <= n_terms <= 8, the terms' checks of icp_gp_models_general_many with the lattice range over these points, the
+ * weights.  Whole-call errors as above. */
+#define ICP_SURFACE_SAMPLES_ROUND_BYTES (64u << 20)
+ICP_API int icp_surface_samples_many(int32_t n_items, int device, const int32_t *n_points, const double *const *points,
+                                     const int32_t *n_triangles, const int32_t *const *cells, const int32_t *n_samples,
+                                     const uint64_t *seeds, double *const *points_out, int32_t *const *cells_out,
+                                     double *const *bary_out, int32_t *const *vertex_ids_out, double *const *info_out,
+                                     int32_t *status);
+ICP_API int icp_kernel_total_variance_many(int32_t n_items, int device, const int32_t *n_points, const double *const *points,
+                                           const int32_t *n_terms, const icp_kernel_term_general *const *terms,
+                                           const double *const *const *point_weights, double *total_variance_out, int32_t *status);
 
 /* ---------------------------------------------------------------- the per-method entry points as ONE submission per step (round 6)
  * The drop-in contract is "Scalismo's chain, unchanged": MetropolisHastings.next (constructed at
