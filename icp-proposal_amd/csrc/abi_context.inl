@@ -1,6 +1,8 @@
 // abi_context.inl — part of icp_abi.hip (one translation unit; included there, in order).
 // C ABI: contexts — create / destroy / set_target / set_rotation, counters, profiling, geometry entry points
 namespace {
+int resolve_device(int device);  // abi_pool_many.inl: the device count's check, the LOCAL_RANK default, the range check
+
 // the target's immutable device data (vertices, triangles, boundary flags, bounding spheres in patch order): shared by every context of
 // the device made from the same arrays (g_shared_targets).  The caller holds g_shared_mu and has bound the device.
 void attach_target(icp_ctx* ctx, const icp_mesh_desc* target, int device) {
@@ -98,15 +100,7 @@ int icp_ctx_create_keyed(const icp_model_desc* model, const icp_mesh_desc* targe
     check_triangles(target->n_points, target->n_triangles, target->triangles, "target");
     for (int j = 0; j < r; ++j) require(model->variance[j] > 0.0 && std::isfinite(model->variance[j]), "variance must be positive");
 
-    int ndev = 0;
-    hipError_t e = hipGetDeviceCount(&ndev);
-    if (e != hipSuccess || ndev <= 0)
-      fail(ICP_ERR_DEVICE, std::string("no usable HIP device (this library has no CPU fallback): ") + hipGetErrorString(e));
-    if (device < 0) {
-      const char* lr = std::getenv("LOCAL_RANK");
-      device = lr ? std::atoi(lr) % ndev : 0;
-    }
-    require(device < ndev, "device ordinal out of range");
+    device = resolve_device(device);
 
     static const bool create_timing = std::getenv("ICP_CREATE_TIMING") != nullptr;  // (operational: where a context's creation goes)
     auto t_mark = std::chrono::steady_clock::now();

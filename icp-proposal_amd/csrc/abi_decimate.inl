@@ -8,8 +8,9 @@
 // the outputs (ONE copy back).  Per round: the selection's launches, then — only if an item of the round asks for counts, labels or
 // triangles — the sweeps in groups of kDecSweepGroup with one read of the flags per group, the candidates with one read of the
 // outputs, and — only if an item asks for counts or triangles — the duplicate tables, sized from the candidate counts, in a second
-// buffer with one copy back.  It takes no context: a stream and buffers from the pools, as icp_scans_prepare_many.  An item's bits
-// depend neither on the other items, nor on their order, nor on the rounds, nor on the selection's route.
+// buffer with one copy back.  It takes no context: the live items, the device and the stream are abi_pool_many.inl's, the rounds and
+// every item's place in their regions RegionRounds' (icp_round_plan.hpp).  An item's bits depend neither on the other items, nor on
+// their order, nor on the rounds, nor on the selection's route.
 
 namespace {
 constexpr size_t kDecRoundWords = (size_t)ICP_DECIMATE_ROUND_BYTES / sizeof(double);
@@ -20,23 +21,21 @@ static_assert(kDecMaxSamples == ICP_DECIMATE_MAX_POINTS, "header and kernels agr
 
 // where an item's arrays lie, in 8-byte words from the start of its part of the round's region: inputs, work arrays, outputs
 struct DecLayout {
-  size_t in_words, work_words, out_words;
+  size_t words[3];                                           // the regions' lengths: kPoolIn, kPoolWork, kPoolOut
   size_t pts, tris;                                          // inputs
   size_t D, pmax, pidx, key0, key1, tkey, keep, tpre, tblk;  // work arrays
   size_t counts, ids, spts, cover2, labels;                  // outputs
   DecLayout(size_t M, size_t T, size_t kk) {
     const size_t nblk = (M + kDecBlock - 1) / kDecBlock, tiles = (T + kScanTile - 1) / kScanTile;
-    size_t at = 0;
-    auto take = [&](size_t bytes) { const size_t o = at; at += scan_words(bytes); return o; };
-    pts = take(24 * M); tris = take(12 * T);
-    in_words = at; at = 0;
-    D = take(8 * M); pmax = take(16 * nblk); pidx = take(8 * nblk); key0 = take(8 * M); key1 = take(8 * M);
-    tkey = take(8 * T); keep = take(T); tpre = take(4 * T); tblk = take(4 * tiles);
-    work_words = at; at = 0;
-    counts = take(16); ids = take(4 * kk); spts = take(24 * kk); cover2 = take(8 * kk); labels = take(4 * M);
-    out_words = at;
+    RegionCursor c;
+    pts = c.take(24 * M); tris = c.take(12 * T);
+    words[kPoolIn] = c.close();
+    D = c.take(8 * M); pmax = c.take(16 * nblk); pidx = c.take(8 * nblk); key0 = c.take(8 * M); key1 = c.take(8 * M);
+    tkey = c.take(8 * T); keep = c.take(T); tpre = c.take(4 * T); tblk = c.take(4 * tiles);
+    words[kPoolWork] = c.close();
+    counts = c.take(16); ids = c.take(4 * kk); spts = c.take(24 * kk); cover2 = c.take(8 * kk); labels = c.take(4 * M);
+    words[kPoolOut] = c.close();
   }
-  size_t words() const { return in_words + work_words + out_words; }
 };
 
 // the duplicate table of an item with `cand` candidate triangles: a power of two of at least twice as many slots
@@ -60,37 +59,17 @@ int icp_decimate_many(int32_t n_items, int device, const int32_t* n_points, cons
     require(counts_out || ids_out || points_out || cover2_out || labels_out || cells_out, "null argument: at least one output");
     const int B = n_items;
     // ---- validation, item by item, before the device is touched
-    item_status.assign(B, ICP_OK);
-    std::vector<int> live;
-    for (int b = 0; b < B; ++b) {
-      auto good = [&] {
-        const long long M = n_points[b], T = n_triangles[b], k = n_samples[b], s = starts ? starts[b] : 0;
-        if (M < 1 || M > kDecMaxVertices || T < 0 || T > kDecMaxTriangles || k < 1 || k > kDecMaxSamples || s < 0 || s >= M) return false;
-        if (!points[b] || (T > 0 && !(cells && cells[b]))) return false;
-        for (size_t i = 0; i < 3 * (size_t)M; ++i)
-          if (!(std::fabs(points[b][i]) <= kDecMaxMagnitude)) return false;
-        for (long long i = 0; i < 3 * T; ++i)
-          if (cells[b][i] < 0 || cells[b][i] >= M) return false;
-        return true;
-      };
-      if (good()) live.push_back(b);
-      else item_status[b] = ICP_ERR_INVALID_ARG;
-    }
+    const std::vector<int> live = live_items(B, item_status, [&](int b) {
+      const long long M = n_points[b], T = n_triangles[b], k = n_samples[b], s = starts ? starts[b] : 0;
+      if (M < 1 || M > kDecMaxVertices || T < 0 || T > kDecMaxTriangles || k < 1 || k > kDecMaxSamples || s < 0 || s >= M) return false;
+      if (!points[b] || (T > 0 && !(cells && cells[b]))) return false;
+      return all_within(points[b], 3 * (size_t)M, kDecMaxMagnitude) && (T == 0 || ids_in_range(cells[b], 3 * (size_t)T, M));
+    });
     const int n_live = (int)live.size();
     if (n_live == 0) return;
 
-    int ndev = 0;
-    hipError_t e = hipGetDeviceCount(&ndev);
-    if (e != hipSuccess || ndev <= 0)
-      fail(ICP_ERR_DEVICE, std::string("no usable HIP device (this library has no CPU fallback): ") + hipGetErrorString(e));
-    if (device < 0) {
-      const char* lr = std::getenv("LOCAL_RANK");
-      device = lr ? std::atoi(lr) % ndev : 0;
-    }
-    require(device < ndev, "device ordinal out of range");
-    DeviceScope _dev(device);
-    StreamScope _st(device);
-    hipStream_t st = _st.st;
+    PoolCall call(device);
+    hipStream_t st = call.st;
 
     // test-hooks build: the size up to which the one-workgroup selection is taken (0: never), the sweeps between two reads of the flags
     int group_vertices = kDecGroupVertices, sweep_group = kDecSweepGroup;
@@ -98,43 +77,23 @@ int icp_decimate_many(int32_t n_items, int device, const int32_t* n_points, cons
     if (const char* v = dev_env("ICP_TEST_DECIMATE_SWEEP_GROUP")) sweep_group = std::min(std::max(std::atoi(v), 1), kDecSweepGroup);
 
     // ---- the plan: every item's layout; rounds = ranges of consecutive live items whose footprints fit the budget
-    const size_t cap = test_chunk_doubles("ICP_TEST_DECIMATE_CHUNK_DOUBLES", kDecRoundWords);
-    struct Round { int q0, q1; size_t in_words, work_words, out_words; };
     std::vector<DecLayout> lay;
-    std::vector<Round> rounds;
     lay.reserve(n_live);
-    size_t buffer_words = 1, stage_in_words = 1, stage_out_words = 1;
-    int round_items = 1;
-    {
-      size_t used = 0;
-      for (int q = 0; q < n_live; ++q) {
-        const int b = live[q];
-        lay.emplace_back((size_t)n_points[b], (size_t)n_triangles[b], (size_t)std::min(n_samples[b], n_points[b]));
-        const DecLayout& l = lay.back();
-        if (rounds.empty() || used + l.words() > cap) {  // (an item above the budget: a round of its own)
-          rounds.push_back(Round{q, q, 0, 0, 0});
-          used = 0;
-        }
-        Round& rd = rounds.back();
-        rd.q1 = q + 1;
-        rd.in_words += l.in_words; rd.work_words += l.work_words; rd.out_words += l.out_words;
-        used += l.words();
-        buffer_words = std::max(buffer_words, used);
-        stage_in_words = std::max(stage_in_words, rd.in_words);
-        stage_out_words = std::max(stage_out_words, rd.out_words);
-        round_items = std::max(round_items, rd.q1 - rd.q0);
-      }
+    RegionRounds<3> plan(test_chunk_doubles("ICP_TEST_DECIMATE_CHUNK_DOUBLES", kDecRoundWords), n_live);
+    using Round = RegionRounds<3>::Round;
+    for (int b : live) {
+      lay.emplace_back((size_t)n_points[b], (size_t)n_triangles[b], (size_t)std::min(n_samples[b], n_points[b]));
+      plan.add(lay.back().words);
     }
+    const int round_items = plan.round_items;
     DBuf<double> chunk, tables;
     DBuf<DecItem> d_items;
     DBuf<DecTable> d_tables;
     DBuf<int> d_flags;
     std::vector<DecItem> h_items(n_live);
-    std::vector<size_t> in_at(n_live), out_at(n_live);  // an item's parts, from the start of its round's regions
-    chunk.alloc(buffer_words);
+    chunk.alloc(plan.buffer_words);
     d_flags.alloc((size_t)round_items * kDecSweepGroup);
-    for (const Round& rd : rounds) {
-      size_t in = 0, w = 0, o = 0;
+    for (const Round& rd : plan.rounds) {
       for (int q = rd.q0; q < rd.q1; ++q) {
         const int b = live[q];
         const DecLayout& l = lay[q];
@@ -143,9 +102,10 @@ int icp_decimate_many(int32_t n_items, int device, const int32_t* n_points, cons
         it.M = n_points[b]; it.T = n_triangles[b]; it.kk = std::min(n_samples[b], n_points[b]); it.start = starts ? starts[b] : 0;
         it.nblk = (it.M + kDecBlock - 1) / kDecBlock;
         it.group = it.M <= group_vertices ? 1 : 0;
-        double* ib = chunk.p + in;
-        double* wb = chunk.p + rd.in_words + w;
-        double* ob = chunk.p + rd.in_words + rd.work_words + o;
+        const auto& at = plan.at[q];  // the item's parts, from the start of its round's regions
+        double* ib = chunk.p + rd.base(kPoolIn) + at[kPoolIn];
+        double* wb = chunk.p + rd.base(kPoolWork) + at[kPoolWork];
+        double* ob = chunk.p + rd.base(kPoolOut) + at[kPoolOut];
         it.pts = ib + l.pts; it.tris = (const int*)(ib + l.tris);
         it.D = wb + l.D; it.pmax = wb + l.pmax; it.pidx = (int*)(wb + l.pidx);
         it.key[0] = (unsigned long long*)(wb + l.key0); it.key[1] = (unsigned long long*)(wb + l.key1);
@@ -154,23 +114,21 @@ int icp_decimate_many(int32_t n_items, int device, const int32_t* n_points, cons
         it.counts = (int*)(ob + l.counts); it.ids = (int*)(ob + l.ids); it.spts = ob + l.spts; it.cover2 = ob + l.cover2;
         it.labels = (int*)(ob + l.labels);
         it.flags = d_flags.p + (size_t)(q - rd.q0) * kDecSweepGroup;
-        in_at[q] = in; out_at[q] = o;
-        in += l.in_words; w += l.work_words; o += l.out_words;
       }
     }
     {
       NullStreamBatch _nb;
       d_items.upload(h_items.data(), h_items.size());
     }
-    std::vector<double> stage_in(stage_in_words), stage_out(stage_out_words), stage_tri;
+    std::vector<double> stage_in(plan.stage_words[kPoolIn]), stage_out(plan.stage_words[kPoolOut]), stage_tri;
     std::vector<int> h_flags((size_t)round_items * kDecSweepGroup);
     std::vector<DecTable> h_tables;
 
     // ---- the rounds
-    for (const Round& rd : rounds) {
+    for (const Round& rd : plan.rounds) {
       const int n = rd.q1 - rd.q0;
       const DecItem* items = d_items.p + rd.q0;
-      double* out_dev = chunk.p + rd.in_words + rd.work_words;
+      double* out_dev = chunk.p + rd.base(kPoolOut);
       int m_max = 0, t_max = 0, kk_max = 0, nblk_general = 0, kk_general = 0;
       bool any_group = false, want_graph = counts_out != nullptr, want_triangles = counts_out != nullptr;
       for (int q = rd.q0; q < rd.q1; ++q) {
@@ -182,11 +140,11 @@ int icp_decimate_many(int32_t n_items, int device, const int32_t* n_points, cons
         else { nblk_general = std::max(nblk_general, it.nblk); kk_general = std::max(kk_general, it.kk); }
         if (cells_out && cells_out[b]) want_graph = want_triangles = true;
         if (labels_out && labels_out[b]) want_graph = true;
-        double* blk = stage_in.data() + in_at[q];
+        double* blk = stage_in.data() + plan.at[q][kPoolIn];
         std::memcpy(blk + l.pts, points[b], sizeof(double) * 3 * (size_t)it.M);
         if (it.T > 0) std::memcpy(blk + l.tris, cells[b], sizeof(int) * 3 * (size_t)it.T);
       }
-      HIP_OK(hipMemcpyAsync(chunk.p, stage_in.data(), sizeof(double) * rd.in_words, hipMemcpyHostToDevice, st));
+      HIP_OK(hipMemcpyAsync(chunk.p, stage_in.data(), sizeof(double) * rd.words[kPoolIn], hipMemcpyHostToDevice, st));
       launch_dec_select(st, n, nblk_general, kk_general, any_group, items);
       std::vector<int> sweeps(n, 0);
       if (want_graph) {
@@ -208,13 +166,13 @@ int icp_decimate_many(int32_t n_items, int device, const int32_t* n_points, cons
         }
         launch_dec_candidates(st, n, std::max(m_max, t_max), launched & 1, items);
       }
-      HIP_OK(hipMemcpyAsync(stage_out.data(), out_dev, sizeof(double) * rd.out_words, hipMemcpyDeviceToHost, st));
+      HIP_OK(hipMemcpyAsync(stage_out.data(), out_dev, sizeof(double) * rd.words[kPoolOut], hipMemcpyDeviceToHost, st));
       HIP_OK(hipStreamSynchronize(st));
       // k_eff and the candidate counts are here: the rows the caller gets, and the tables' sizes
       std::vector<int> k_eff(n), cand(n);
       for (int q = rd.q0; q < rd.q1; ++q) {
         int cnt[4];
-        std::memcpy(cnt, stage_out.data() + out_at[q] + lay[q].counts, sizeof(cnt));
+        std::memcpy(cnt, stage_out.data() + plan.at[q][kPoolOut] + lay[q].counts, sizeof(cnt));
         const DecItem& it = h_items[q];
         if (cnt[0] < 1 || cnt[0] > it.kk || cnt[3] < 0 || cnt[3] > it.T) fail(ICP_ERR_DEVICE, "the decimation's counts are out of range");
         k_eff[q - rd.q0] = cnt[0]; cand[q - rd.q0] = cnt[3];
@@ -223,8 +181,8 @@ int icp_decimate_many(int32_t n_items, int device, const int32_t* n_points, cons
       size_t table_words = 0, tri_words = 0;
       if (want_triangles) {
         h_tables.assign(n, DecTable{});
-        for (int i = 0; i < n; ++i) table_words += scan_words(12 * dec_table_size((size_t)cand[i]));
-        for (int i = 0; i < n; ++i) { tri_at[i] = tri_words; tri_words += 1 + scan_words(12 * (size_t)cand[i]); }
+        for (int i = 0; i < n; ++i) table_words += region_words(12 * dec_table_size((size_t)cand[i]));
+        for (int i = 0; i < n; ++i) { tri_at[i] = tri_words; tri_words += 1 + region_words(12 * (size_t)cand[i]); }
         tables.alloc(table_words + tri_words);
         size_t at = 0;
         for (int i = 0; i < n; ++i) {
@@ -236,7 +194,7 @@ int icp_decimate_many(int32_t n_items, int device, const int32_t* n_points, cons
           tb.t_out = (int*)(tables.p + table_words + tri_at[i]);
           tb.cells = (int*)(tables.p + table_words + tri_at[i] + 1);
           tb.cap = cand[i];
-          at += scan_words(12 * size);
+          at += region_words(12 * size);
         }
         {
           NullStreamBatch _nb;
@@ -252,7 +210,7 @@ int icp_decimate_many(int32_t n_items, int device, const int32_t* n_points, cons
         const int b = live[q], i = q - rd.q0;
         const DecLayout& l = lay[q];
         const DecItem& it = h_items[q];
-        const double* blk = stage_out.data() + out_at[q];
+        const double* blk = stage_out.data() + plan.at[q][kPoolOut];
         const size_t ke = (size_t)k_eff[i];
         if (ids_out && ids_out[b]) std::memcpy(ids_out[b], blk + l.ids, sizeof(int) * ke);
         if (points_out && points_out[b]) std::memcpy(points_out[b], blk + l.spts, sizeof(double) * 3 * ke);

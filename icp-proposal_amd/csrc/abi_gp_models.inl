@@ -12,7 +12,8 @@
 // could not separate), one refinement step of the eigenvectors and the operands in a launch each, and the group's rows of L·Op through ONE chunk buffer, round by round, one
 // synchronisation per round.  The decompositions see sqrt_lambda ≡ 1 and a Gram matrix scaled by an exact power of two (trace(K) brought
 // into [1, 2)): magnitudes like a posterior's, and θ comes back exactly.  An item's bits depend neither on the other items, nor on
-// their order, nor on how its rows fall into rounds.
+// their order, nor on how its rows fall into rounds.  The entry points take no context: the live items, the device and the stream are
+// abi_pool_many.inl's, a term's device record is gpm_term_record's, and the rows are cut into pieces by RowPieces (icp_round_plan.hpp).
 
 namespace {
 constexpr size_t kGpmChunkDoubles = (size_t)ICP_GP_MODELS_CHUNK_BYTES / sizeof(double);
@@ -35,19 +36,6 @@ bool gpm_psd(const double* A) {
   return det >= -eps * mag;
 }
 
-struct DeviceScope {  // the calling thread's device, put back when the call ends
-  int prev = -1;
-  explicit DeviceScope(int device) {
-    (void)hipGetDevice(&prev);
-    HIP_OK(hipSetDevice(device));
-  }
-  ~DeviceScope() { if (prev >= 0) (void)hipSetDevice(prev); }
-};
-struct StreamScope {
-  hipStream_t st;
-  explicit StreamScope(int device) : st(take_stream(device, false, 0)) {}
-  ~StreamScope() { give_stream(st); }
-};
 // a term with icp_gp_models_many's meaning: Gaussian, no weights, no mirror
 bool gpm_term_plain(const icp_kernel_term_general& k) { return k.kind == ICP_KERNEL_GAUSSIAN && !k.weights && k.mirror_gain == 0.0; }
 
@@ -104,43 +92,27 @@ void gpm_models_run(int32_t n_items, int device, const int32_t* n_points, const 
   {
     const int B = n_items;
     // ---- validation, item by item, before the device is touched
-    item_status.assign(B, ICP_OK);
-    std::vector<int> live;
-    for (int b = 0; b < B; ++b) {
-      auto good = [&] {
-        if (!points[b] || !terms[b]) return false;
-        const long long N = n_points[b];
-        if (N < 1 || 3 * N > (long long)INT32_MAX) return false;
-        if (n_terms[b] < 1 || n_terms[b] > kGpmMaxTerms) return false;
-        if (!(rank[b] >= 1 && rank[b] <= n_pivots[b] && n_pivots[b] <= kGpmMaxPivots && (long long)n_pivots[b] <= 3 * N)) return false;
-        if (rel_tolerance && !(rel_tolerance[b] >= 0.0 && rel_tolerance[b] < 1.0)) return false;
-        double lattice = 0.0;
-        for (long long i = 0; i < 3 * N; ++i) {
-          if (!std::isfinite(points[b][i])) return false;
-          lattice = std::max(lattice, std::fabs(points[b][i]));
-        }
-        for (int t = 0; t < n_terms[b]; ++t)
-          if (!gpm_term_good(terms[b][t], N, lattice)) return false;
-        return true;
-      };
-      if (good()) live.push_back(b);
-      else item_status[b] = ICP_ERR_INVALID_ARG;
-    }
+    std::vector<int> live = live_items(B, item_status, [&](int b) {
+      if (!points[b] || !terms[b]) return false;
+      const long long N = n_points[b];
+      if (N < 1 || 3 * N > (long long)INT32_MAX) return false;
+      if (n_terms[b] < 1 || n_terms[b] > kGpmMaxTerms) return false;
+      if (!(rank[b] >= 1 && rank[b] <= n_pivots[b] && n_pivots[b] <= kGpmMaxPivots && (long long)n_pivots[b] <= 3 * N)) return false;
+      if (rel_tolerance && !(rel_tolerance[b] >= 0.0 && rel_tolerance[b] < 1.0)) return false;
+      double lattice = 0.0;
+      for (long long i = 0; i < 3 * N; ++i) {
+        if (!std::isfinite(points[b][i])) return false;
+        lattice = std::max(lattice, std::fabs(points[b][i]));
+      }
+      for (int t = 0; t < n_terms[b]; ++t)
+        if (!gpm_term_good(terms[b][t], N, lattice)) return false;
+      return true;
+    });
     int n_live = (int)live.size();
     if (n_live == 0) return;
 
-    int ndev = 0;
-    hipError_t e = hipGetDeviceCount(&ndev);
-    if (e != hipSuccess || ndev <= 0)
-      fail(ICP_ERR_DEVICE, std::string("no usable HIP device (this library has no CPU fallback): ") + hipGetErrorString(e));
-    if (device < 0) {
-      const char* lr = std::getenv("LOCAL_RANK");
-      device = lr ? std::atoi(lr) % ndev : 0;
-    }
-    require(device < ndev, "device ordinal out of range");
-    DeviceScope _dev(device);
-    StreamScope _st(device);
-    hipStream_t st = _st.st;
+    PoolCall call(device);
+    hipStream_t st = call.st;
 
     // ---- the pivot loop: every item's points, d, L and partials; one record per item
     std::vector<GpmItem> h_items(n_live);
@@ -192,16 +164,10 @@ void gpm_models_run(int32_t n_items, int device, const int32_t* n_points, const 
         it.R = 3 * n_points[b]; it.m = n_pivots[b]; it.n_terms = n_terms[b]; it.nblk = cdiv(it.R, kGpmBlockRows);
         it.rel_tol = rel_tolerance ? rel_tolerance[b] : 0.0;
         for (int t = 0; t < kGpmMaxTerms; ++t) {
-          GpmTerm& tm = it.terms[t];
-          tm = GpmTerm{};
+          it.terms[t] = GpmTerm{};
           if (t >= it.n_terms) continue;
           const icp_kernel_term_general& k = terms[b][t];
-          tm.scale = k.scale;
-          std::memcpy(tm.A, k.A, sizeof(tm.A));
-          tm.kind = k.kind; tm.axis = k.mirror_axis; tm.gain = k.mirror_gain;
-          if (k.kind == ICP_KERNEL_GAUSSIAN) tm.sigma2 = k.sigma * k.sigma;
-          else tm.c = std::ldexp(1.0, k.level);
-          if (k.weights) tm.w = d_pts.p + w0 + off_w[(size_t)q * kGpmMaxTerms + t];
+          it.terms[t] = gpm_term_record(k, k.weights ? d_pts.p + w0 + off_w[(size_t)q * kGpmMaxTerms + t] : nullptr);
           it.general = it.general || !gpm_term_plain(k);
         }
         it.pts = d_pts.p + off_pts[q]; it.d = d_d.p + off_pts[q]; it.L = d_L.p + off_L[q];
@@ -362,47 +328,37 @@ void gpm_mspace_run(hipStream_t st, const std::vector<GpmFactor>& f, bool rank_r
   };
   // the rows of the group's bases through the chunk buffer: pieces that fill it are a round (product, copies back, synchronisation)
   auto run_rounds = [&](int q0, int q1) {
-    struct Back { double* dev; double* host; size_t n; };
     std::vector<GpmPiece> pcs;
-    std::vector<Back> back;
     DBuf<GpmPiece> d_pcs;
-    size_t used = 0;
+    HostCopies back;
     int rows_max = 0, tiles_max = 0;
-    auto flush = [&] {
-      if (pcs.empty()) return;
-      {
-        NullStreamBatch _nb;
-        d_pcs.upload(pcs.data(), pcs.size());
-      }
-      launch_gpm_gemm(st, (int)pcs.size(), rows_max, tiles_max, d_pcs.p);
-      HostCopies cp;
-      for (const Back& k : back) cp.add(k.dev, k.host, k.n);
-      cp.issue(st, false);
-      HIP_OK(hipStreamSynchronize(st));
-      pcs.clear(); back.clear();
-      used = 0; rows_max = 0; tiles_max = 0;
-    };
-    for (int q = q0; q < q1; ++q) {
-      const int b = f[q].b;
-      if (!(basis_out && basis_out[b])) continue;
-      const GpmSpace& sp = h_sp[q];
-      const size_t per_q = (size_t)kGpmRowQuantum * sp.rank;
-      for (int row0 = 0; row0 < sp.R;) {
-        if (cap - used < per_q || (int)pcs.size() == kGpmMaxPieces) flush();
-        const size_t fit = (cap - used) / per_q * kGpmRowQuantum;
-        const int rows = (int)std::min<size_t>(fit, (size_t)(sp.R - row0));
-        GpmPiece pc{};
-        pc.L = sp.L; pc.Op = sp.Op; pc.R = sp.R; pc.me = sp.me; pc.rank = sp.rank; pc.ldb = sp.ldb; pc.row0 = row0; pc.rows = rows;
-        pc.out = chunk.p + used;
-        used += (size_t)rows * sp.rank;
-        back.push_back(Back{pc.out, basis_out[b] + (size_t)row0 * sp.rank, (size_t)rows * sp.rank});
-        rows_max = std::max(rows_max, rows);
-        tiles_max = std::max(tiles_max, sp.ldb / 16);
-        pcs.push_back(pc);
-        row0 += rows;
-      }
-    }
-    flush();
+    RowPieces{cap, kGpmRowQuantum, kGpmMaxPieces}.cut(
+        q0, q1,
+        [&](int q) {
+          const int b = f[q].b;
+          return RowPieces::Item{h_sp[q].R, (size_t)h_sp[q].rank, basis_out && basis_out[b]};
+        },
+        [&](int q, int row0, int rows, size_t at) {
+          const GpmSpace& sp = h_sp[q];
+          GpmPiece pc{};
+          pc.L = sp.L; pc.Op = sp.Op; pc.R = sp.R; pc.me = sp.me; pc.rank = sp.rank; pc.ldb = sp.ldb; pc.row0 = row0; pc.rows = rows;
+          pc.out = chunk.p + at;
+          back.add(pc.out, basis_out[f[q].b] + (size_t)row0 * sp.rank, (size_t)rows * sp.rank);
+          rows_max = std::max(rows_max, rows);
+          tiles_max = std::max(tiles_max, sp.ldb / 16);
+          pcs.push_back(pc);
+        },
+        [&] {
+          {
+            NullStreamBatch _nb;
+            d_pcs.upload(pcs.data(), pcs.size());
+          }
+          launch_gpm_gemm(st, (int)pcs.size(), rows_max, tiles_max, d_pcs.p);
+          back.issue(st, false);
+          HIP_OK(hipStreamSynchronize(st));
+          pcs.clear();
+          rows_max = 0; tiles_max = 0;
+        });
   };
 
   std::vector<double> h_var((size_t)n_live * rank_max);
@@ -522,37 +478,21 @@ int icp_region_weights_many(int32_t n_items, int device, const int32_t* n_points
   int rc = guard([&] {
     require(n_items >= 1 && n_items <= 65535, "n_items must lie in [1, 65535]");
     require(n_points && points && n_region && region_points && stddev && weights_out && status, "null argument");
-    item_status.assign(n_items, ICP_OK);
-    std::vector<int> live;
-    for (int b = 0; b < n_items; ++b) {
-      auto good = [&] {
-        if (!points[b] || !region_points[b] || !weights_out[b]) return false;
-        const long long N = n_points[b], M = n_region[b];
-        if (N < 1 || 3 * N > (long long)INT32_MAX || M < 1 || 3 * M > (long long)INT32_MAX) return false;
-        if (!(std::isfinite(stddev[b]) && stddev[b] > 0.0 && std::isfinite(stddev[b] * stddev[b]) && stddev[b] * stddev[b] > 0.0)) return false;
-        for (long long i = 0; i < 3 * N; ++i)
-          if (!std::isfinite(points[b][i])) return false;
-        for (long long i = 0; i < 3 * M; ++i)
-          if (!std::isfinite(region_points[b][i])) return false;
-        return true;
-      };
-      if (good()) live.push_back(b);
-      else item_status[b] = ICP_ERR_INVALID_ARG;
-    }
+    const std::vector<int> live = live_items(n_items, item_status, [&](int b) {
+      if (!points[b] || !region_points[b] || !weights_out[b]) return false;
+      const long long N = n_points[b], M = n_region[b];
+      if (N < 1 || 3 * N > (long long)INT32_MAX || M < 1 || 3 * M > (long long)INT32_MAX) return false;
+      if (!(std::isfinite(stddev[b]) && stddev[b] > 0.0 && std::isfinite(stddev[b] * stddev[b]) && stddev[b] * stddev[b] > 0.0)) return false;
+      for (long long i = 0; i < 3 * N; ++i)
+        if (!std::isfinite(points[b][i])) return false;
+      for (long long i = 0; i < 3 * M; ++i)
+        if (!std::isfinite(region_points[b][i])) return false;
+      return true;
+    });
     const int n_live = (int)live.size();
     if (n_live == 0) return;
-    int ndev = 0;
-    hipError_t e = hipGetDeviceCount(&ndev);
-    if (e != hipSuccess || ndev <= 0)
-      fail(ICP_ERR_DEVICE, std::string("no usable HIP device (this library has no CPU fallback): ") + hipGetErrorString(e));
-    if (device < 0) {
-      const char* lr = std::getenv("LOCAL_RANK");
-      device = lr ? std::atoi(lr) % ndev : 0;
-    }
-    require(device < ndev, "device ordinal out of range");
-    DeviceScope _dev(device);
-    StreamScope _st(device);
-    hipStream_t st = _st.st;
+    PoolCall call(device);
+    hipStream_t st = call.st;
     // every item's points, then every item's region, in ONE upload; the weights come back as one copy per item
     std::vector<size_t> off_p(n_live + 1, 0), off_r(n_live + 1, 0), off_o(n_live + 1, 0);
     int n_max = 1;

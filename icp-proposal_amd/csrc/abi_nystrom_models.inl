@@ -2,11 +2,12 @@
 // many in one call (kernels_nystrom_model.hip).  Item b: K = k(S, S) on its n sample points, K = U·Λ·Uᵀ by a two-sided
 // block Jacobi iteration on the device, and the model (λ/n, k(X, S)·u·√n/λ) on its mesh points.
 //
-// Every argument of every item is checked before the device is touched.  The live items then go through the device kNysGroup at a
+// Every argument of every item is checked before the device is touched (live_items, then PoolCall's device and stream:
+// abi_pool_many.inl).  The live items then go through the device kNysGroup at a
 // time: ONE upload (points, samples, weights), the kernel matrices in one launch, and the iteration — three launches per round of the
 // tournament, each carrying every item of the group, an item that has converged returning at once — with one synchronisation per sweep,
 // in which the host reads ONE word: how many items still iterate.  Behind it the eigenvalues' order, the operands, and the rows of the
-// bases through ONE chunk buffer, round by round (abi_gp_models.inl's streaming).  An item's bits depend neither on the other items,
+// bases through ONE chunk buffer, round by round (the pieces are RowPieces' of icp_round_plan.hpp).  An item's bits depend neither on the other items,
 // nor on their order, nor on how its rows fall into rounds.
 
 namespace {
@@ -21,59 +22,43 @@ void nys_models_run(int32_t n_items, int device, const int32_t* n_points, const 
                     std::vector<int>& item_status) {
   const int B = n_items;
   // ---- validation, item by item, before the device is touched
-  item_status.assign(B, ICP_OK);
-  std::vector<int> live;
-  for (int b = 0; b < B; ++b) {
-    auto good = [&] {
-      if (!points[b] || !samples[b] || !terms[b]) return false;
-      const long long N = n_points[b], n = n_samples[b];
-      if (N < 1 || 3 * N > (long long)INT32_MAX) return false;
-      if (n < 1 || 3 * n > (long long)kNysMaxRows) return false;
-      if (n_terms[b] < 1 || n_terms[b] > kGpmMaxTerms) return false;
-      if (!(rank[b] >= 1 && rank[b] <= kNysMaxRank && (long long)rank[b] <= 3 * n)) return false;
-      if (min_variance && !(min_variance[b] >= 0.0 && std::isfinite(min_variance[b]))) return false;
-      double lattice = 0.0;
-      for (long long i = 0; i < 3 * N; ++i) {
-        if (!std::isfinite(points[b][i])) return false;
-        lattice = std::max(lattice, std::fabs(points[b][i]));
+  const std::vector<int> live = live_items(B, item_status, [&](int b) {
+    if (!points[b] || !samples[b] || !terms[b]) return false;
+    const long long N = n_points[b], n = n_samples[b];
+    if (N < 1 || 3 * N > (long long)INT32_MAX) return false;
+    if (n < 1 || 3 * n > (long long)kNysMaxRows) return false;
+    if (n_terms[b] < 1 || n_terms[b] > kGpmMaxTerms) return false;
+    if (!(rank[b] >= 1 && rank[b] <= kNysMaxRank && (long long)rank[b] <= 3 * n)) return false;
+    if (min_variance && !(min_variance[b] >= 0.0 && std::isfinite(min_variance[b]))) return false;
+    double lattice = 0.0;
+    for (long long i = 0; i < 3 * N; ++i) {
+      if (!std::isfinite(points[b][i])) return false;
+      lattice = std::max(lattice, std::fabs(points[b][i]));
+    }
+    for (long long i = 0; i < 3 * n; ++i) {
+      if (!std::isfinite(samples[b][i])) return false;
+      lattice = std::max(lattice, std::fabs(samples[b][i]));
+    }
+    for (int t = 0; t < n_terms[b]; ++t) {
+      if (!gpm_term_good(terms[b][t], N, lattice)) return false;
+      if (!terms[b][t].weights) continue;
+      // a weighted term needs its region weights at the sample points as well
+      const double* w = sample_weights && sample_weights[b] ? sample_weights[b][t] : nullptr;
+      if (!w) return false;
+      bool positive = false;
+      for (long long i = 0; i < n; ++i) {
+        if (!(std::isfinite(w[i]) && w[i] >= 0.0)) return false;
+        positive = positive || w[i] > 0.0;
       }
-      for (long long i = 0; i < 3 * n; ++i) {
-        if (!std::isfinite(samples[b][i])) return false;
-        lattice = std::max(lattice, std::fabs(samples[b][i]));
-      }
-      for (int t = 0; t < n_terms[b]; ++t) {
-        if (!gpm_term_good(terms[b][t], N, lattice)) return false;
-        if (!terms[b][t].weights) continue;
-        // a weighted term needs its region weights at the sample points as well
-        const double* w = sample_weights && sample_weights[b] ? sample_weights[b][t] : nullptr;
-        if (!w) return false;
-        bool positive = false;
-        for (long long i = 0; i < n; ++i) {
-          if (!(std::isfinite(w[i]) && w[i] >= 0.0)) return false;
-          positive = positive || w[i] > 0.0;
-        }
-        if (!positive) return false;
-      }
-      return true;
-    };
-    if (good()) live.push_back(b);
-    else item_status[b] = ICP_ERR_INVALID_ARG;
-  }
+      if (!positive) return false;
+    }
+    return true;
+  });
   const int n_live = (int)live.size();
   if (n_live == 0) return;
 
-  int ndev = 0;
-  hipError_t e = hipGetDeviceCount(&ndev);
-  if (e != hipSuccess || ndev <= 0)
-    fail(ICP_ERR_DEVICE, std::string("no usable HIP device (this library has no CPU fallback): ") + hipGetErrorString(e));
-  if (device < 0) {
-    const char* lr = std::getenv("LOCAL_RANK");
-    device = lr ? std::atoi(lr) % ndev : 0;
-  }
-  require(device < ndev, "device ordinal out of range");
-  DeviceScope _dev(device);
-  StreamScope _st(device);
-  hipStream_t st = _st.st;
+  PoolCall call(device);
+  hipStream_t st = call.st;
 
   int rank_max = 1;
   for (int b : live) rank_max = std::max(rank_max, (int)rank[b]);
@@ -156,17 +141,9 @@ void nys_models_run(int32_t n_items, int device, const int32_t* n_points, const 
         const int b = live[g0 + q];
         NysItem& it = h_items[q];
         for (int t = 0; t < it.n_terms; ++t) {
-          GpmTerm& tm = it.terms[t];
           const icp_kernel_term_general& k = terms[b][t];
-          tm.scale = k.scale;
-          std::memcpy(tm.A, k.A, sizeof(tm.A));
-          tm.kind = k.kind; tm.axis = k.mirror_axis; tm.gain = k.mirror_gain;
-          if (k.kind == ICP_KERNEL_GAUSSIAN) tm.sigma2 = k.sigma * k.sigma;
-          else tm.c = std::ldexp(1.0, k.level);
-          if (k.weights) {
-            tm.w = d_in.p + w0 + o_w[(size_t)q * kGpmMaxTerms + t];
-            it.sw[t] = d_in.p + w0 + o_sw[(size_t)q * kGpmMaxTerms + t];
-          }
+          it.terms[t] = gpm_term_record(k, k.weights ? d_in.p + w0 + o_w[(size_t)q * kGpmMaxTerms + t] : nullptr);
+          if (k.weights) it.sw[t] = d_in.p + w0 + o_sw[(size_t)q * kGpmMaxTerms + t];
           it.general = it.general || !gpm_term_plain(k);
         }
         it.pts = d_in.p + o_pts[q]; it.smp = d_in.p + o_pts[G] + o_smp[q];
@@ -217,47 +194,36 @@ void nys_models_run(int32_t n_items, int device, const int32_t* n_points, const 
       }
     }
     // ---- the rows of the group's bases through the chunk buffer: pieces that fill it are a round (product, copies back, synchronisation)
-    struct Back { double* dev; double* host; size_t n; };
     std::vector<NysPiece> pcs;
-    std::vector<Back> back;
     DBuf<NysPiece> d_pcs;
-    size_t used = 0;
+    HostCopies back;
     int rows_max = 0, tiles_max = 0;
-    auto flush = [&] {
-      if (pcs.empty()) return;
-      {
-        NullStreamBatch _nb;
-        d_pcs.upload(pcs.data(), pcs.size());
-      }
-      launch_nys_basis(st, (int)pcs.size(), rows_max, tiles_max, d_pcs.p);
-      HostCopies cp;
-      for (const Back& k : back) cp.add(k.dev, k.host, k.n);
-      cp.issue(st, false);
-      HIP_OK(hipStreamSynchronize(st));
-      pcs.clear(); back.clear();
-      used = 0; rows_max = 0; tiles_max = 0;
-    };
-    for (int q = 0; q < G; ++q) {
-      const int b = live[g0 + q];
-      if (!(basis_out && basis_out[b])) continue;
-      const NysItem& it = h_items[q];
-      const size_t per_q = (size_t)kNysRowQuantum * it.rank;
-      const int rows_all = 3 * it.N;
-      for (int row0 = 0; row0 < rows_all;) {
-        if (cap - used < per_q || (int)pcs.size() == kNysMaxPieces) flush();
-        const size_t fit = (cap - used) / per_q * kNysRowQuantum;
-        const int rows = (int)std::min<size_t>(fit, (size_t)(rows_all - row0));
-        NysPiece pc{};
-        pc.item = d_items.p + q; pc.row0 = row0; pc.rows = rows; pc.out = chunk.p + used;
-        used += (size_t)rows * it.rank;
-        back.push_back(Back{pc.out, basis_out[b] + (size_t)row0 * it.rank, (size_t)rows * it.rank});
-        rows_max = std::max(rows_max, rows);
-        tiles_max = std::max(tiles_max, it.kp / 16);
-        pcs.push_back(pc);
-        row0 += rows;
-      }
-    }
-    flush();
+    RowPieces{cap, kNysRowQuantum, kNysMaxPieces}.cut(
+        0, G,
+        [&](int q) {
+          const int b = live[g0 + q];
+          return RowPieces::Item{3 * h_items[q].N, (size_t)h_items[q].rank, basis_out && basis_out[b]};
+        },
+        [&](int q, int row0, int rows, size_t at) {
+          const NysItem& it = h_items[q];
+          NysPiece pc{};
+          pc.item = d_items.p + q; pc.row0 = row0; pc.rows = rows; pc.out = chunk.p + at;
+          back.add(pc.out, basis_out[live[g0 + q]] + (size_t)row0 * it.rank, (size_t)rows * it.rank);
+          rows_max = std::max(rows_max, rows);
+          tiles_max = std::max(tiles_max, it.kp / 16);
+          pcs.push_back(pc);
+        },
+        [&] {
+          {
+            NullStreamBatch _nb;
+            d_pcs.upload(pcs.data(), pcs.size());
+          }
+          launch_nys_basis(st, (int)pcs.size(), rows_max, tiles_max, d_pcs.p);
+          back.issue(st, false);
+          HIP_OK(hipStreamSynchronize(st));
+          pcs.clear();
+          rows_max = 0; tiles_max = 0;
+        });
   }
 }
 }  // namespace

@@ -3,8 +3,9 @@
 // gpa_iterations rounds of alignment to the mean shape, four launches a round for every item of the call and no synchronisation
 // between them (an item that has stopped returns from every later launch); the centring launch; ONE synchronisation (rounds run, the
 // last RMS, the transforms, the mean shapes, the partials of trace G); then the m-space half of the GP models (gpm_mspace_run of
-// abi_gp_models.inl) on the centred columns, with the rank decided on the device.  An item's bits depend neither on the other items,
-// nor on their order, nor on how its rows fall into the chunk buffer.
+// abi_gp_models.inl) on the centred columns, with the rank decided on the device.  It takes no context: the live items, the device and
+// the stream are abi_pool_many.inl's.  An item's bits depend neither on the other items, nor on their order, nor on how its rows fall
+// into the chunk buffer.
 
 namespace {
 constexpr double kPcaDataFloor = 0x1p-80;  // (2⁻⁴⁰)²: see icp_proposal.h, "τ₀"
@@ -22,7 +23,6 @@ int icp_pca_models_many(int32_t n_items, int device, int32_t n_pool, const int32
     require(n_pool >= 1 && pool_points && pool && n_meshes && mesh_ids && rank && gpa_iterations && halt_distance && status, "null argument");
     const int B = n_items;
     // ---- validation, item by item, before the device is touched; a pool mesh is looked at once, when the first item names it
-    item_status.assign(B, ICP_OK);
     std::vector<signed char> pool_good(n_pool, -1);  // -1: not looked at yet
     auto mesh_good = [&](int k) {
       if (pool_good[k] >= 0) return pool_good[k] == 1;
@@ -31,42 +31,27 @@ int icp_pca_models_many(int32_t n_items, int device, int32_t n_pool, const int32
       pool_good[k] = ok ? 1 : 0;
       return ok;
     };
-    std::vector<int> live;
-    for (int b = 0; b < B; ++b) {
-      auto good = [&] {
-        const int n = n_meshes[b];
-        if (n < 2 || n > kGpmMaxPivots || !mesh_ids[b]) return false;
-        if (!(rank[b] >= 1 && rank[b] <= n - 1)) return false;
-        if (gpa_iterations[b] < 0 || gpa_iterations[b] > kPcaMaxRounds) return false;
-        if (!(std::isfinite(halt_distance[b]) && halt_distance[b] >= 0.0)) return false;
-        for (int j = 0; j < n; ++j) {
-          const int k = mesh_ids[b][j];
-          if (k < 0 || k >= n_pool || !mesh_good(k)) return false;
-          if (pool_points[k] != pool_points[mesh_ids[b][0]]) return false;
-        }
-        if (reference && reference[b])
-          for (long long i = 0; i < 3 * (long long)pool_points[mesh_ids[b][0]]; ++i)
-            if (!std::isfinite(reference[b][i])) return false;
-        return true;
-      };
-      if (good()) live.push_back(b);
-      else item_status[b] = ICP_ERR_INVALID_ARG;
-    }
-    int n_live = (int)live.size();
+    const std::vector<int> live = live_items(B, item_status, [&](int b) {
+      const int n = n_meshes[b];
+      if (n < 2 || n > kGpmMaxPivots || !mesh_ids[b]) return false;
+      if (!(rank[b] >= 1 && rank[b] <= n - 1)) return false;
+      if (gpa_iterations[b] < 0 || gpa_iterations[b] > kPcaMaxRounds) return false;
+      if (!(std::isfinite(halt_distance[b]) && halt_distance[b] >= 0.0)) return false;
+      for (int j = 0; j < n; ++j) {
+        const int k = mesh_ids[b][j];
+        if (k < 0 || k >= n_pool || !mesh_good(k)) return false;
+        if (pool_points[k] != pool_points[mesh_ids[b][0]]) return false;
+      }
+      if (reference && reference[b])
+        for (long long i = 0; i < 3 * (long long)pool_points[mesh_ids[b][0]]; ++i)
+          if (!std::isfinite(reference[b][i])) return false;
+      return true;
+    });
+    const int n_live = (int)live.size();
     if (n_live == 0) return;
 
-    int ndev = 0;
-    hipError_t e = hipGetDeviceCount(&ndev);
-    if (e != hipSuccess || ndev <= 0)
-      fail(ICP_ERR_DEVICE, std::string("no usable HIP device (this library has no CPU fallback): ") + hipGetErrorString(e));
-    if (device < 0) {
-      const char* lr = std::getenv("LOCAL_RANK");
-      device = lr ? std::atoi(lr) % ndev : 0;
-    }
-    require(device < ndev, "device ordinal out of range");
-    DeviceScope _dev(device);
-    StreamScope _st(device);
-    hipStream_t st = _st.st;
+    PoolCall call(device);
+    hipStream_t st = call.st;
 
     // ---- the pool meshes a live item names, in ONE upload; every item's records
     std::vector<size_t> pool_off(n_pool, (size_t)-1);

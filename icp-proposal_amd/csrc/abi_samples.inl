@@ -7,8 +7,9 @@
 // rounds of at most kSmpRoundWords 8-byte words (an item above that has a round of its own), in three regions: the inputs (ONE upload),
 // the work arrays, the outputs (ONE copy back).  Per round: three launches for the integer weights and their prefix, one for the picks,
 // and — only if an item of the round asks for vertex ids — one for the nearest vertices; no synchronisation between them.  Neither
-// entry point takes a context: a stream and buffers from the pools, as icp_decimate_many.  An item's bits depend neither on the other
-// items, nor on their order, nor on the rounds, nor on which outputs are asked for.
+// entry point takes a context: the live items, the device and the stream are abi_pool_many.inl's, the rounds and every item's place in
+// their regions RegionRounds' (icp_round_plan.hpp), a term's device record gpm_term_record's.  An item's bits depend neither on the
+// other items, nor on their order, nor on the rounds, nor on which outputs are asked for.
 
 namespace {
 constexpr size_t kSmpRoundWords = (size_t)ICP_SURFACE_SAMPLES_ROUND_BYTES / sizeof(double);
@@ -20,22 +21,20 @@ constexpr int kTvMaxPoints = 1 << 24;
 
 // where an item's arrays lie, in 8-byte words from the start of its part of the round's region: inputs, work arrays, outputs
 struct SmpLayout {
-  size_t in_words, work_words, out_words;
+  size_t words[3];                      // the regions' lengths: kPoolIn, kPoolWork, kPoolOut
   size_t pts, tris;                     // inputs
   size_t a2, tmax, C, tblk, tcnt, Q;    // work arrays
   size_t info, opts, ocells, obary, oids;  // outputs
   SmpLayout(size_t M, size_t T, size_t n) {
     const size_t tiles = (T + kScanTile - 1) / kScanTile;
-    size_t at = 0;
-    auto take = [&](size_t bytes) { const size_t o = at; at += scan_words(bytes); return o; };
-    pts = take(24 * M); tris = take(12 * T);
-    in_words = at; at = 0;
-    a2 = take(8 * T); tmax = take(8 * tiles); C = take(8 * T); tblk = take(8 * tiles); tcnt = take(4 * tiles); Q = take(8);
-    work_words = at; at = 0;
-    info = take(32); opts = take(24 * n); ocells = take(4 * n); obary = take(24 * n); oids = take(4 * n);
-    out_words = at;
+    RegionCursor c;
+    pts = c.take(24 * M); tris = c.take(12 * T);
+    words[kPoolIn] = c.close();
+    a2 = c.take(8 * T); tmax = c.take(8 * tiles); C = c.take(8 * T); tblk = c.take(8 * tiles); tcnt = c.take(4 * tiles); Q = c.take(8);
+    words[kPoolWork] = c.close();
+    info = c.take(32); opts = c.take(24 * n); ocells = c.take(4 * n); obary = c.take(24 * n); oids = c.take(4 * n);
+    words[kPoolOut] = c.close();
   }
-  size_t words() const { return in_words + work_words + out_words; }
 };
 }  // namespace
 
@@ -52,71 +51,32 @@ int icp_surface_samples_many(int32_t n_items, int device, const int32_t* n_point
     require(points_out || cells_out || bary_out || vertex_ids_out || info_out, "null argument: at least one output");
     const int B = n_items;
     // ---- validation, item by item, before the device is touched
-    item_status.assign(B, ICP_OK);
-    std::vector<int> live;
-    for (int b = 0; b < B; ++b) {
-      auto good = [&] {
-        const long long M = n_points[b], T = n_triangles[b], n = n_samples[b];
-        if (M < 1 || M > kSmpMaxVertices || T < 1 || T > kSmpMaxTriangles || n < 1 || n > kSmpMaxSamples) return false;
-        if (!points[b] || !cells[b]) return false;
-        for (size_t i = 0; i < 3 * (size_t)M; ++i)
-          if (!(std::fabs(points[b][i]) <= kSmpMaxMagnitude)) return false;
-        for (long long i = 0; i < 3 * T; ++i)
-          if (cells[b][i] < 0 || cells[b][i] >= M) return false;
-        return true;
-      };
-      if (good()) live.push_back(b);
-      else item_status[b] = ICP_ERR_INVALID_ARG;
-    }
+    const std::vector<int> live = live_items(B, item_status, [&](int b) {
+      const long long M = n_points[b], T = n_triangles[b], n = n_samples[b];
+      if (M < 1 || M > kSmpMaxVertices || T < 1 || T > kSmpMaxTriangles || n < 1 || n > kSmpMaxSamples) return false;
+      if (!points[b] || !cells[b]) return false;
+      return all_within(points[b], 3 * (size_t)M, kSmpMaxMagnitude) && ids_in_range(cells[b], 3 * (size_t)T, M);
+    });
     const int n_live = (int)live.size();
     if (n_live == 0) return;
 
-    int ndev = 0;
-    hipError_t e = hipGetDeviceCount(&ndev);
-    if (e != hipSuccess || ndev <= 0)
-      fail(ICP_ERR_DEVICE, std::string("no usable HIP device (this library has no CPU fallback): ") + hipGetErrorString(e));
-    if (device < 0) {
-      const char* lr = std::getenv("LOCAL_RANK");
-      device = lr ? std::atoi(lr) % ndev : 0;
-    }
-    require(device < ndev, "device ordinal out of range");
-    DeviceScope _dev(device);
-    StreamScope _st(device);
-    hipStream_t st = _st.st;
+    PoolCall call(device);
+    hipStream_t st = call.st;
 
     // ---- the plan: every item's layout; rounds = ranges of consecutive live items whose footprints fit the budget
-    const size_t cap = test_chunk_doubles("ICP_TEST_SAMPLES_CHUNK_DOUBLES", kSmpRoundWords);
-    struct Round { int q0, q1; size_t in_words, work_words, out_words; };
     std::vector<SmpLayout> lay;
-    std::vector<Round> rounds;
     lay.reserve(n_live);
-    size_t buffer_words = 1, stage_in_words = 1, stage_out_words = 1;
-    {
-      size_t used = 0;
-      for (int q = 0; q < n_live; ++q) {
-        const int b = live[q];
-        lay.emplace_back((size_t)n_points[b], (size_t)n_triangles[b], (size_t)n_samples[b]);
-        const SmpLayout& l = lay.back();
-        if (rounds.empty() || used + l.words() > cap) {  // (an item above the budget: a round of its own)
-          rounds.push_back(Round{q, q, 0, 0, 0});
-          used = 0;
-        }
-        Round& rd = rounds.back();
-        rd.q1 = q + 1;
-        rd.in_words += l.in_words; rd.work_words += l.work_words; rd.out_words += l.out_words;
-        used += l.words();
-        buffer_words = std::max(buffer_words, used);
-        stage_in_words = std::max(stage_in_words, rd.in_words);
-        stage_out_words = std::max(stage_out_words, rd.out_words);
-      }
+    RegionRounds<3> plan(test_chunk_doubles("ICP_TEST_SAMPLES_CHUNK_DOUBLES", kSmpRoundWords), n_live);
+    using Round = RegionRounds<3>::Round;
+    for (int b : live) {
+      lay.emplace_back((size_t)n_points[b], (size_t)n_triangles[b], (size_t)n_samples[b]);
+      plan.add(lay.back().words);
     }
     DBuf<double> chunk;
     DBuf<SmpItem> d_items;
     std::vector<SmpItem> h_items(n_live);
-    std::vector<size_t> in_at(n_live), out_at(n_live);  // an item's parts, from the start of its round's regions
-    chunk.alloc(buffer_words);
-    for (const Round& rd : rounds) {
-      size_t in = 0, w = 0, o = 0;
+    chunk.alloc(plan.buffer_words);
+    for (const Round& rd : plan.rounds) {
       for (int q = rd.q0; q < rd.q1; ++q) {
         const int b = live[q];
         const SmpLayout& l = lay[q];
@@ -126,26 +86,25 @@ int icp_surface_samples_many(int32_t n_items, int device, const int32_t* n_point
         it.tiles = (it.T + kScanTile - 1) / kScanTile;
         it.want_ids = vertex_ids_out && vertex_ids_out[b] ? 1 : 0;
         it.seed = seeds[b];
-        double* ib = chunk.p + in;
-        double* wb = chunk.p + rd.in_words + w;
-        double* ob = chunk.p + rd.in_words + rd.work_words + o;
+        const auto& at = plan.at[q];  // the item's parts, from the start of its round's regions
+        double* ib = chunk.p + rd.base(kPoolIn) + at[kPoolIn];
+        double* wb = chunk.p + rd.base(kPoolWork) + at[kPoolWork];
+        double* ob = chunk.p + rd.base(kPoolOut) + at[kPoolOut];
         it.pts = ib + l.pts; it.tris = (const int*)(ib + l.tris);
         it.a2 = wb + l.a2; it.tmax = wb + l.tmax; it.C = (unsigned long long*)(wb + l.C); it.tblk = (unsigned long long*)(wb + l.tblk);
         it.tcnt = (int*)(wb + l.tcnt); it.Q = (unsigned long long*)(wb + l.Q);
         it.info = ob + l.info; it.opts = ob + l.opts; it.ocells = (int*)(ob + l.ocells); it.obary = ob + l.obary;
         it.oids = (int*)(ob + l.oids);
-        in_at[q] = in; out_at[q] = o;
-        in += l.in_words; w += l.work_words; o += l.out_words;
       }
     }
     {
       NullStreamBatch _nb;
       d_items.upload(h_items.data(), h_items.size());
     }
-    std::vector<double> stage_in(stage_in_words), stage_out(stage_out_words);
+    std::vector<double> stage_in(plan.stage_words[kPoolIn]), stage_out(plan.stage_words[kPoolOut]);
 
     // ---- the rounds
-    for (const Round& rd : rounds) {
+    for (const Round& rd : plan.rounds) {
       const int n = rd.q1 - rd.q0;
       const SmpItem* items = d_items.p + rd.q0;
       int t_max = 0, n_max = 0, n_ids_max = 0;
@@ -155,21 +114,21 @@ int icp_surface_samples_many(int32_t n_items, int device, const int32_t* n_point
         const SmpLayout& l = lay[q];
         t_max = std::max(t_max, it.T); n_max = std::max(n_max, it.n);
         if (it.want_ids) n_ids_max = std::max(n_ids_max, it.n);
-        double* blk = stage_in.data() + in_at[q];
+        double* blk = stage_in.data() + plan.at[q][kPoolIn];
         std::memcpy(blk + l.pts, points[b], sizeof(double) * 3 * (size_t)it.M);
         std::memcpy(blk + l.tris, cells[b], sizeof(int) * 3 * (size_t)it.T);
       }
-      HIP_OK(hipMemcpyAsync(chunk.p, stage_in.data(), sizeof(double) * rd.in_words, hipMemcpyHostToDevice, st));
+      HIP_OK(hipMemcpyAsync(chunk.p, stage_in.data(), sizeof(double) * rd.words[kPoolIn], hipMemcpyHostToDevice, st));
       launch_smp_weights(st, n, t_max, items);
       launch_smp_pick(st, n, n_max, items);
       if (n_ids_max > 0) launch_smp_nearest(st, n, n_ids_max, items);
-      HIP_OK(hipMemcpyAsync(stage_out.data(), chunk.p + rd.in_words + rd.work_words, sizeof(double) * rd.out_words, hipMemcpyDeviceToHost, st));
+      HIP_OK(hipMemcpyAsync(stage_out.data(), chunk.p + rd.base(kPoolOut), sizeof(double) * rd.words[kPoolOut], hipMemcpyDeviceToHost, st));
       HIP_OK(hipStreamSynchronize(st));
       for (int q = rd.q0; q < rd.q1; ++q) {
         const int b = live[q];
         const SmpLayout& l = lay[q];
         const size_t ns = (size_t)h_items[q].n;
-        const double* blk = stage_out.data() + out_at[q];
+        const double* blk = stage_out.data() + plan.at[q][kPoolOut];
         double info[4];
         std::memcpy(info, blk + l.info, sizeof(info));
         if (!(info[0] >= 1.0)) item_status[b] = ICP_ERR_NOT_FINITE;  // no triangle has a weight: NaN and -1 are what the device wrote
@@ -200,45 +159,29 @@ int icp_kernel_total_variance_many(int32_t n_items, int device, const int32_t* n
     const int B = n_items;
     // ---- validation, item by item, before the device is touched (a term's `weights` field is not read: the weights at these points
     // are point_weights[b][t])
-    item_status.assign(B, ICP_OK);
-    std::vector<int> live;
     auto weights_of = [&](int b, int t) -> const double* { return point_weights && point_weights[b] ? point_weights[b][t] : nullptr; };
-    for (int b = 0; b < B; ++b) {
-      auto good = [&] {
-        if (!points[b] || !terms[b]) return false;
-        const long long n = n_points[b];
-        if (n < 1 || n > kTvMaxPoints) return false;
-        if (n_terms[b] < 1 || n_terms[b] > kGpmMaxTerms) return false;
-        double lattice = 0.0;
-        for (long long i = 0; i < 3 * n; ++i) {
-          if (!std::isfinite(points[b][i])) return false;
-          lattice = std::max(lattice, std::fabs(points[b][i]));
-        }
-        for (int t = 0; t < n_terms[b]; ++t) {
-          icp_kernel_term_general k = terms[b][t];
-          k.weights = weights_of(b, t);
-          if (!gpm_term_good(k, n, lattice)) return false;
-        }
-        return true;
-      };
-      if (good()) live.push_back(b);
-      else item_status[b] = ICP_ERR_INVALID_ARG;
-    }
+    const std::vector<int> live = live_items(B, item_status, [&](int b) {
+      if (!points[b] || !terms[b]) return false;
+      const long long n = n_points[b];
+      if (n < 1 || n > kTvMaxPoints) return false;
+      if (n_terms[b] < 1 || n_terms[b] > kGpmMaxTerms) return false;
+      double lattice = 0.0;
+      for (long long i = 0; i < 3 * n; ++i) {
+        if (!std::isfinite(points[b][i])) return false;
+        lattice = std::max(lattice, std::fabs(points[b][i]));
+      }
+      for (int t = 0; t < n_terms[b]; ++t) {
+        icp_kernel_term_general k = terms[b][t];
+        k.weights = weights_of(b, t);
+        if (!gpm_term_good(k, n, lattice)) return false;
+      }
+      return true;
+    });
     const int n_live = (int)live.size();
     if (n_live == 0) return;
 
-    int ndev = 0;
-    hipError_t e = hipGetDeviceCount(&ndev);
-    if (e != hipSuccess || ndev <= 0)
-      fail(ICP_ERR_DEVICE, std::string("no usable HIP device (this library has no CPU fallback): ") + hipGetErrorString(e));
-    if (device < 0) {
-      const char* lr = std::getenv("LOCAL_RANK");
-      device = lr ? std::atoi(lr) % ndev : 0;
-    }
-    require(device < ndev, "device ordinal out of range");
-    DeviceScope _dev(device);
-    StreamScope _st(device);
-    hipStream_t st = _st.st;
+    PoolCall call(device);
+    hipStream_t st = call.st;
 
     // every item's points, then every term's weights, in ONE upload; the block sums and the results behind them in one buffer
     std::vector<size_t> off_p(n_live + 1, 0), off_s(n_live + 1, 0);
@@ -276,16 +219,8 @@ int icp_kernel_total_variance_many(int32_t n_items, int device, const int32_t* n
         TvItem& it = h_items[q];
         it = TvItem{};
         it.n = n_points[b]; it.n_terms = n_terms[b]; it.nblk = cdiv(it.n, kTvBlock);
-        for (int t = 0; t < it.n_terms; ++t) {
-          GpmTerm& tm = it.terms[t];
-          const icp_kernel_term_general& k = terms[b][t];
-          tm.scale = k.scale;
-          std::memcpy(tm.A, k.A, sizeof(tm.A));
-          tm.kind = k.kind; tm.axis = k.mirror_axis; tm.gain = k.mirror_gain;
-          if (k.kind == ICP_KERNEL_GAUSSIAN) tm.sigma2 = k.sigma * k.sigma;
-          else tm.c = std::ldexp(1.0, k.level);
-          if (weights_of(b, t)) tm.w = d_in.p + w0 + off_w[(size_t)q * kGpmMaxTerms + t];
-        }
+        for (int t = 0; t < it.n_terms; ++t)
+          it.terms[t] = gpm_term_record(terms[b][t], weights_of(b, t) ? d_in.p + w0 + off_w[(size_t)q * kGpmMaxTerms + t] : nullptr);
         it.pts = d_in.p + off_p[q];
         it.bsum = d_sum.p + off_s[q];
         it.out = d_sum.p + off_s[n_live] + q;

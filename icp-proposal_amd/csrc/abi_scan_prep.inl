@@ -10,8 +10,9 @@
 // the caller's arrays get.  A round of small items (at most kScanPackWords of input and of output an item on average) packs its
 // inputs into ONE upload and fetches its outputs as ONE copy each for the output and the flag regions: at femur size the eight
 // copies an item would take cost more than everything else.  Per round: one fill, the uploads, seven launches, the copies back, ONE
-// synchronisation.  It takes no context: a stream and buffers
-// from the pools, as icp_gp_models_many.  An item's bits depend neither on the other items, nor on their order, nor on the rounds.
+// synchronisation.  It takes no context: the live items, the device and the stream are abi_pool_many.inl's, the rounds and every
+// item's place in their regions RegionRounds' (icp_round_plan.hpp).  An item's bits depend neither on the other items, nor on their
+// order, nor on the rounds.
 
 namespace {
 constexpr size_t kScanRoundWords = (size_t)ICP_SCAN_PREP_ROUND_BYTES / sizeof(double);
@@ -20,38 +21,32 @@ constexpr int kScanMaxPoints = 1 << 26;
 constexpr double kScanMaxMagnitude = 0x1p400;
 static_assert(kScanMaxCuts == ICP_SCAN_MAX_CUTS, "header and kernels agree on the cuts per item");
 
-size_t scan_words(size_t bytes) { return (bytes + 7) / 8; }
+enum { kScanZero, kScanIn, kScanWork, kScanOut };  // the regions of a round's buffer, in their order
 
 // where an item's arrays lie, in 8-byte words from the start of its part of the round's region: zeroed bytes, inputs, work arrays,
 // outputs (`counts` and what follows it: the late block, which depends on the counts)
 struct ScanLayout {
-  size_t zero_words, in_words, work_words, out_words;
+  size_t words[4];                                      // the regions' lengths
   size_t flags, used;                                   // zeroed region
   size_t pts, lms, tris, mask;                          // inputs
   size_t keys, thr, keep, vpre, tpre, vblk, tblk;       // work arrays
   size_t aligned, lm_out, counts, kept, ptris, ppts;    // outputs
   ScanLayout(size_t M, size_t T, size_t L, size_t n_cuts, size_t n_mask) {
-    size_t at = 0;
-    auto take = [&](size_t bytes) { const size_t o = at; at += scan_words(bytes); return o; };
-    flags = take(M); used = take(M);
-    zero_words = at; at = 0;
-    pts = take(24 * M); lms = take(24 * L); tris = take(12 * T); mask = take(4 * n_mask);
-    in_words = at; at = 0;
-    keys = take(8 * n_cuts * M); thr = take(16 * n_cuts); keep = take(T); vpre = take(4 * M); tpre = take(4 * T);
-    vblk = take(4 * ((M + kScanTile - 1) / kScanTile)); tblk = take(4 * ((T + kScanTile - 1) / kScanTile));
-    work_words = at; at = 0;
-    aligned = take(24 * M); lm_out = take(24 * L); counts = take(8); kept = take(4 * M); ptris = take(12 * T); ppts = take(24 * M);
-    out_words = at;
+    RegionCursor c;
+    flags = c.take(M); used = c.take(M);
+    words[kScanZero] = c.close();
+    pts = c.take(24 * M); lms = c.take(24 * L); tris = c.take(12 * T); mask = c.take(4 * n_mask);
+    words[kScanIn] = c.close();
+    keys = c.take(8 * n_cuts * M); thr = c.take(16 * n_cuts); keep = c.take(T); vpre = c.take(4 * M); tpre = c.take(4 * T);
+    vblk = c.take(4 * ((M + kScanTile - 1) / kScanTile)); tblk = c.take(4 * ((T + kScanTile - 1) / kScanTile));
+    words[kScanWork] = c.close();
+    aligned = c.take(24 * M); lm_out = c.take(24 * L); counts = c.take(8); kept = c.take(4 * M); ptris = c.take(12 * T); ppts = c.take(24 * M);
+    words[kScanOut] = c.close();
   }
-  size_t words() const { return zero_words + in_words + work_words + out_words; }
-  size_t late_words() const { return out_words - counts; }
+  size_t late_words() const { return words[kScanOut] - counts; }
 };
 
-bool scan_small(const double* v, size_t n) {  // finite and at most 2^400 in magnitude
-  for (size_t i = 0; i < n; ++i)
-    if (!(std::fabs(v[i]) <= kScanMaxMagnitude)) return false;
-  return true;
-}
+bool scan_small(const double* v, size_t n) { return all_within(v, n, kScanMaxMagnitude); }  // finite and at most 2^400 in magnitude
 bool scan_small_scaled(double s, const double* v, size_t n) {
   for (size_t i = 0; i < n; ++i)
     if (!(std::fabs(s * v[i]) <= kScanMaxMagnitude)) return false;
@@ -74,82 +69,47 @@ int icp_scans_prepare_many(int32_t n_items, int device, const int32_t* n_points,
     require(n_points && points && n_triangles && transforms && n_landmarks && n_cuts && n_mask_ids && status, "null argument");
     const int B = n_items;
     // ---- validation, item by item, before the device is touched
-    item_status.assign(B, ICP_OK);
-    std::vector<int> live;
-    for (int b = 0; b < B; ++b) {
-      auto good = [&] {
-        const long long M = n_points[b], T = n_triangles[b], L = n_landmarks[b], nc = n_cuts[b], nm = n_mask_ids[b];
-        if (M < 1 || M > kScanMaxPoints || T < 0 || T > kScanMaxPoints || L < 0 || nc < 0 || nc > kScanMaxCuts || nm < 0) return false;
-        if (!points[b] || (T > 0 && !(triangles && triangles[b])) || (L > 0 && !(landmarks && landmarks[b]))) return false;
-        if (nc > 0 && !(cut_landmark && cut_landmark[b] && cut_count && cut_count[b])) return false;
-        if (nm > 0 && !(mask_ids && mask_ids[b])) return false;
-        const icp_scan_transform& tf = transforms[b];
-        if (tf.struct_size != sizeof(icp_scan_transform)) return false;
-        if (!(std::isfinite(tf.pre_scale) && tf.pre_scale > 0.0)) return false;
-        if (!scan_small(tf.rotation, 9) || !scan_small(tf.centre, 3) || !scan_small(tf.translation, 3)) return false;
-        if (!scan_small(points[b], 3 * (size_t)M) || !scan_small_scaled(tf.pre_scale, points[b], 3 * (size_t)M)) return false;
-        if (L > 0 && (!scan_small(landmarks[b], 3 * (size_t)L) || !scan_small_scaled(tf.pre_scale, landmarks[b], 3 * (size_t)L))) return false;
-        for (long long i = 0; i < 3 * T; ++i)
-          if (triangles[b][i] < 0 || triangles[b][i] >= M) return false;
-        for (int j = 0; j < nc; ++j)
-          if (cut_landmark[b][j] < 0 || cut_landmark[b][j] >= L || cut_count[b][j] < 0) return false;
-        for (long long i = 0; i < nm; ++i)
-          if (mask_ids[b][i] < 0) return false;
-        return true;
-      };
-      if (good()) live.push_back(b);
-      else item_status[b] = ICP_ERR_INVALID_ARG;
-    }
+    const std::vector<int> live = live_items(B, item_status, [&](int b) {
+      const long long M = n_points[b], T = n_triangles[b], L = n_landmarks[b], nc = n_cuts[b], nm = n_mask_ids[b];
+      if (M < 1 || M > kScanMaxPoints || T < 0 || T > kScanMaxPoints || L < 0 || nc < 0 || nc > kScanMaxCuts || nm < 0) return false;
+      if (!points[b] || (T > 0 && !(triangles && triangles[b])) || (L > 0 && !(landmarks && landmarks[b]))) return false;
+      if (nc > 0 && !(cut_landmark && cut_landmark[b] && cut_count && cut_count[b])) return false;
+      if (nm > 0 && !(mask_ids && mask_ids[b])) return false;
+      const icp_scan_transform& tf = transforms[b];
+      if (tf.struct_size != sizeof(icp_scan_transform)) return false;
+      if (!(std::isfinite(tf.pre_scale) && tf.pre_scale > 0.0)) return false;
+      if (!scan_small(tf.rotation, 9) || !scan_small(tf.centre, 3) || !scan_small(tf.translation, 3)) return false;
+      if (!scan_small(points[b], 3 * (size_t)M) || !scan_small_scaled(tf.pre_scale, points[b], 3 * (size_t)M)) return false;
+      if (L > 0 && (!scan_small(landmarks[b], 3 * (size_t)L) || !scan_small_scaled(tf.pre_scale, landmarks[b], 3 * (size_t)L))) return false;
+      if (T > 0 && !ids_in_range(triangles[b], 3 * (size_t)T, M)) return false;
+      for (int j = 0; j < nc; ++j)
+        if (cut_landmark[b][j] < 0 || cut_landmark[b][j] >= L || cut_count[b][j] < 0) return false;
+      for (long long i = 0; i < nm; ++i)
+        if (mask_ids[b][i] < 0) return false;
+      return true;
+    });
     const int n_live = (int)live.size();
     if (n_live == 0) return;
 
-    int ndev = 0;
-    hipError_t e = hipGetDeviceCount(&ndev);
-    if (e != hipSuccess || ndev <= 0)
-      fail(ICP_ERR_DEVICE, std::string("no usable HIP device (this library has no CPU fallback): ") + hipGetErrorString(e));
-    if (device < 0) {
-      const char* lr = std::getenv("LOCAL_RANK");
-      device = lr ? std::atoi(lr) % ndev : 0;
-    }
-    require(device < ndev, "device ordinal out of range");
-    DeviceScope _dev(device);
-    StreamScope _st(device);
-    hipStream_t st = _st.st;
+    PoolCall call(device);
+    hipStream_t st = call.st;
 
     // ---- the plan: every item's layout; rounds = ranges of consecutive live items whose footprints fit the budget
-    const size_t cap = test_chunk_doubles("ICP_TEST_SCAN_PREP_CHUNK_DOUBLES", kScanRoundWords);
-    struct Round { int q0, q1; size_t zero_words, in_words, work_words, out_words; };
     std::vector<ScanLayout> lay;
-    std::vector<Round> rounds;
     lay.reserve(n_live);
-    size_t buffer_words = 1, stage_in_words = 1, stage_out_words = 1, stage_zero_words = 1;
-    {
-      size_t used = 0;
-      for (int q = 0; q < n_live; ++q) {
-        const int b = live[q];
-        lay.emplace_back((size_t)n_points[b], (size_t)n_triangles[b], (size_t)n_landmarks[b], (size_t)n_cuts[b], (size_t)n_mask_ids[b]);
-        const ScanLayout& l = lay.back();
-        if (rounds.empty() || used + l.words() > cap) {  // (an item above the budget: a round of its own)
-          rounds.push_back(Round{q, q, 0, 0, 0, 0});
-          used = 0;
-        }
-        Round& rd = rounds.back();
-        rd.q1 = q + 1;
-        rd.zero_words += l.zero_words; rd.in_words += l.in_words; rd.work_words += l.work_words; rd.out_words += l.out_words;
-        used += l.words();
-        buffer_words = std::max(buffer_words, used);
-        stage_in_words = std::max(stage_in_words, rd.in_words);
-        stage_out_words = std::max(stage_out_words, rd.out_words);
-        stage_zero_words = std::max(stage_zero_words, rd.zero_words);
-      }
+    RegionRounds<4> plan(test_chunk_doubles("ICP_TEST_SCAN_PREP_CHUNK_DOUBLES", kScanRoundWords), n_live);
+    using Round = RegionRounds<4>::Round;
+    for (int b : live) {
+      lay.emplace_back((size_t)n_points[b], (size_t)n_triangles[b], (size_t)n_landmarks[b], (size_t)n_cuts[b], (size_t)n_mask_ids[b]);
+      plan.add(lay.back().words);
     }
+    const size_t stage_zero_words = plan.stage_words[kScanZero], stage_in_words = plan.stage_words[kScanIn],
+                 stage_out_words = plan.stage_words[kScanOut];
     DBuf<double> chunk;
     DBuf<ScanItem> d_items;
     std::vector<ScanItem> h_items(n_live);
-    std::vector<size_t> zero_at(n_live), in_at(n_live), out_at(n_live);  // an item's parts, from the start of its round's regions
-    chunk.alloc(buffer_words);
-    for (const Round& rd : rounds) {
-      size_t z = 0, in = 0, w = 0, o = 0;
+    chunk.alloc(plan.buffer_words);
+    for (const Round& rd : plan.rounds) {
       for (int q = rd.q0; q < rd.q1; ++q) {
         const int b = live[q];
         const ScanLayout& l = lay[q];
@@ -167,10 +127,11 @@ int icp_scans_prepare_many(int32_t n_items, int device, const int32_t* n_points,
           it.c[d] = tf.centre[d];
           it.o[d] = tf.centre[d] + tf.translation[d];
         }
-        double* zb = chunk.p + z;
-        double* ib = chunk.p + rd.zero_words + in;
-        double* wb = chunk.p + rd.zero_words + rd.in_words + w;
-        double* ob = chunk.p + rd.zero_words + rd.in_words + rd.work_words + o;
+        const auto& at = plan.at[q];  // the item's parts, from the start of its round's regions
+        double* zb = chunk.p + rd.base(kScanZero) + at[kScanZero];
+        double* ib = chunk.p + rd.base(kScanIn) + at[kScanIn];
+        double* wb = chunk.p + rd.base(kScanWork) + at[kScanWork];
+        double* ob = chunk.p + rd.base(kScanOut) + at[kScanOut];
         it.flags = (unsigned char*)(zb + l.flags); it.used = (unsigned char*)(zb + l.used);
         it.pts = ib + l.pts; it.lms = ib + l.lms; it.tris = (const int*)(ib + l.tris); it.mask = (const int*)(ib + l.mask);
         it.keys = (unsigned long long*)(wb + l.keys); it.thr = (unsigned long long*)(wb + l.thr);
@@ -178,8 +139,6 @@ int icp_scans_prepare_many(int32_t n_items, int device, const int32_t* n_points,
         it.vblk = (int*)(wb + l.vblk); it.tblk = (int*)(wb + l.tblk);
         it.aligned = ob + l.aligned; it.lm_out = ob + l.lm_out;
         it.counts = (int*)(ob + l.counts); it.kept = (int*)(ob + l.kept); it.ptris = (int*)(ob + l.ptris); it.ppts = ob + l.ppts;
-        zero_at[q] = z; in_at[q] = in; out_at[q] = o;
-        z += l.zero_words; in += l.in_words; w += l.work_words; o += l.out_words;
       }
     }
     {
@@ -190,11 +149,12 @@ int icp_scans_prepare_many(int32_t n_items, int device, const int32_t* n_points,
     const bool direct_only = dev_env("ICP_TEST_SCAN_PREP_DIRECT_COPIES") != nullptr;  // test-hooks build: small items take the large ones' copies
 
     // ---- the rounds
-    for (const Round& rd : rounds) {
+    for (const Round& rd : plan.rounds) {
       const int n = rd.q1 - rd.q0;
-      double* in_dev = chunk.p + rd.zero_words;
-      double* out_dev = chunk.p + rd.zero_words + rd.in_words + rd.work_words;
-      const bool packed = !direct_only && rd.in_words <= kScanPackWords * (size_t)n && rd.out_words <= kScanPackWords * (size_t)n;
+      const size_t zero_words = rd.words[kScanZero], in_words = rd.words[kScanIn], out_words = rd.words[kScanOut];
+      double* in_dev = chunk.p + rd.base(kScanIn);
+      double* out_dev = chunk.p + rd.base(kScanOut);
+      const bool packed = !direct_only && in_words <= kScanPackWords * (size_t)n && out_words <= kScanPackWords * (size_t)n;
       auto wants_late = [&](int b) {
         return counts_out || (partial_points_out && partial_points_out[b]) || (partial_triangles_out && partial_triangles_out[b]) ||
                (kept_ids_out && kept_ids_out[b]);
@@ -208,7 +168,7 @@ int icp_scans_prepare_many(int32_t n_items, int device, const int32_t* n_points,
         m_max = std::max(m_max, it.M); t_max = std::max(t_max, it.T);
         any_flags = any_flags || (cut_flags_out && cut_flags_out[live[q]]);
       }
-      HIP_OK(hipMemsetAsync(chunk.p, 0, sizeof(double) * rd.zero_words, st));
+      HIP_OK(hipMemsetAsync(chunk.p, 0, sizeof(double) * zero_words, st));
       HostCopies up, back;
       if (packed) {
         stage_in.resize(stage_in_words);
@@ -216,13 +176,13 @@ int icp_scans_prepare_many(int32_t n_items, int device, const int32_t* n_points,
           const int b = live[q];
           const ScanItem& it = h_items[q];
           const ScanLayout& l = lay[q];
-          double* blk = stage_in.data() + in_at[q];
+          double* blk = stage_in.data() + plan.at[q][kScanIn];
           std::memcpy(blk + l.pts, points[b], sizeof(double) * 3 * (size_t)it.M);
           if (it.L > 0) std::memcpy(blk + l.lms, landmarks[b], sizeof(double) * 3 * (size_t)it.L);
           if (it.T > 0) std::memcpy(blk + l.tris, triangles[b], sizeof(int) * 3 * (size_t)it.T);
           if (it.n_mask > 0) std::memcpy(blk + l.mask, mask_ids[b], sizeof(int) * (size_t)it.n_mask);
         }
-        up.add(in_dev, stage_in.data(), rd.in_words);
+        up.add(in_dev, stage_in.data(), in_words);
         up.issue(st, true);
       } else {
         for (int q = rd.q0; q < rd.q1; ++q) {
@@ -247,10 +207,10 @@ int icp_scans_prepare_many(int32_t n_items, int device, const int32_t* n_points,
       launch_scan_prefix(st, n, std::max(m_max, t_max), items);
       launch_scan_scatter(st, n, std::max(m_max, t_max), items);
       if (packed) {
-        back.add(out_dev, stage_out.data(), rd.out_words);
+        back.add(out_dev, stage_out.data(), out_words);
         if (any_flags) {
           stage_zero.resize(stage_zero_words);
-          back.add(chunk.p, stage_zero.data(), rd.zero_words);
+          back.add(chunk.p, stage_zero.data(), zero_words);
         }
         back.issue(st, false);
       } else {
@@ -260,7 +220,7 @@ int icp_scans_prepare_many(int32_t n_items, int device, const int32_t* n_points,
           const ScanLayout& l = lay[q];
           if (aligned_out && aligned_out[b]) back.add(it.aligned, aligned_out[b], 3 * (size_t)it.M);
           if (it.L > 0 && landmarks_out && landmarks_out[b]) back.add(it.lm_out, landmarks_out[b], 3 * (size_t)it.L);
-          if (wants_late(b)) back.add(out_dev + out_at[q] + l.counts, stage_out.data() + out_at[q] + l.counts, l.late_words());
+          if (wants_late(b)) back.add(out_dev + plan.at[q][kScanOut] + l.counts, stage_out.data() + plan.at[q][kScanOut] + l.counts, l.late_words());
         }
         back.issue(st, false);
         for (int q = rd.q0; q < rd.q1; ++q) {
@@ -274,11 +234,11 @@ int icp_scans_prepare_many(int32_t n_items, int device, const int32_t* n_points,
         const int b = live[q];
         const ScanLayout& l = lay[q];
         const ScanItem& it = h_items[q];
-        const double* blk = stage_out.data() + out_at[q];
+        const double* blk = stage_out.data() + plan.at[q][kScanOut];
         if (packed) {
           if (aligned_out && aligned_out[b]) std::memcpy(aligned_out[b], blk + l.aligned, sizeof(double) * 3 * (size_t)it.M);
           if (it.L > 0 && landmarks_out && landmarks_out[b]) std::memcpy(landmarks_out[b], blk + l.lm_out, sizeof(double) * 3 * (size_t)it.L);
-          if (cut_flags_out && cut_flags_out[b]) std::memcpy(cut_flags_out[b], stage_zero.data() + zero_at[q] + l.flags, (size_t)it.M);
+          if (cut_flags_out && cut_flags_out[b]) std::memcpy(cut_flags_out[b], stage_zero.data() + plan.at[q][kScanZero] + l.flags, (size_t)it.M);
         }
         if (!wants_late(b)) continue;
         int cnt[2];

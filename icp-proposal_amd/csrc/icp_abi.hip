@@ -15,6 +15,7 @@
 #include "abi_context.inl"  // C ABI: contexts — create / destroy / set_target / set_rotation, counters, profiling, geometry entry points
 #include "abi_methods.inl"  // C ABI: per-method entry points — proposals, evaluators, deterministic fit, variability maps, metrics, icp_chain_eval_step
 #include "abi_many.inl"  // what the batched entry points below share: context locks, argument checks, instance plan, status epilogue
+#include "abi_pool_many.inl"  // what the context-free entry points below share: device choice, pooled stream, live items, argument loops, a kernel term's record; the round and piece plans of icp_round_plan.hpp
 #include "abi_fit_many.inl"  // C ABI: icp_fit_deterministic_many (many deterministic fits in lockstep, kernels_fit.hip)
 #include "abi_metrics_many.inl"  // C ABI: icp_mesh_metrics_many (registration metrics and Dice of many meshes, kernels_metrics.hip)
 #include "abi_variability_many.inl"  // C ABI: icp_posterior_variability_many (variability maps of many chains, kernels_variability.hip)
